@@ -12,21 +12,35 @@ is 128 = configs[3] as BASELINE.json states it (global 1024 at N=8); N=1 stays a
 "configs[3] per GPU" secondary leg (128 x 3 x 224 x 224 on one GPU) -- the like-for-like denominator of the N>1 values.
 Synthetic paste-and-crop frames, random-init weights; inputs are resident in HBM before timing.
 
-At N = 1 with the default workload the same process then measures the other single-GPU configurations of BASELINE.json as
-short SECONDARY legs -- configs[2] (bf16 storage arm, 128 x 3 x 512 x 512) and one GPU's share of configs[4] (ResNet-50
-localizer, bf16, 64 x 3 x 512 x 512) -- and reports them under "secondary" in the same line, each with its own roofline; the
-primary keys describe the fp32 leg alone (its timed region is closed before a secondary leg starts).
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline figure needs: set up, W warm-up steps, K timed
+steps, the outputs of the last timed step if --dump-outputs DIR is given, and ONE JSON line (rank 0) with the contract keys
+(metric, value, unit, n_gpus, steps, warmup, ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config);
+`roofline` is null there.
 
-Prints ONE JSON line (rank 0), COMPACT (a few KB: `compact_line`), with the contract keys plus
+--full measures everything else as well, in the same process:
   roofline     : the ResNet-18 conv-forward MFMA roofline, measured live with HIP events
                  around the forward implicit-GEMM launches (21 convs) of every timed step
                  (minus the time a bracket of two events takes with nothing in it)
   cpu_baseline : the CPU oracle ("port": NumPy restatement of the Chainer graph) timed on
                  the host cores on a bounded sample (B=8) of the same workload (N=1 only)
-  secondary    : per leg value / ms_per_step / dtype / baseline_config / roofline_frac / binding_frac only.
-Everything else (per-layer binding tables, per-class tables, allocator diagnostics, the full secondary legs) goes to
---detail-file (default bench_detail.json beside this script; round 5's line carried all of it, grew to 26.5 KB and the
-driver could not parse it).
+  secondary    : at N = 1 with the default workload, the other single-GPU configurations of BASELINE.json as short SECONDARY
+                 legs -- configs[2] (bf16 storage arm, 128 x 3 x 512 x 512), one GPU's share of configs[4] (ResNet-50
+                 localizer, bf16, 64 x 3 x 512 x 512), ... -- per leg value / ms_per_step / dtype / baseline_config /
+                 roofline_frac / binding_frac; the primary keys describe the fp32 leg alone (its timed region is closed before
+                 a secondary leg starts).
+The line stays COMPACT (a few KB: `compact_line`); everything else (per-layer binding tables, per-class tables, allocator
+diagnostics, the full secondary legs) goes to --detail-file (default bench_detail.json beside this script; round 5's line
+carried all of it, grew to 26.5 KB and the driver could not parse it).
+
+The step runs both Adam-AMSGrad updates at step size ADAM_ALPHA = 0: every launch of a training step, on the same bytes, while the
+parameters stay at their seeded values (see ADAM_ALPHA); config.workload says so.
+
+--dump-outputs DIR writes what the timed path computed in its last timed step -- the two losses the step reports, the updated
+state of both models (parameters and BN statistics, Chainer key paths) and both optimisers' Adam state, which holds the step's
+gradients (step_outputs), as DIR/<name>.npy in float32 -- so that two builds can be
+compared output for output: the inputs are seeded, identical from run to run for the same arguments, and every step computes
+from the same parameters (ADAM_ALPHA), so two runs agree to rounding.  An array of more than DUMP_SAMPLE elements is written as a
+fixed, seeded sample of that many (DIR/<name>.sample.npy).
 """
 import argparse
 import json
@@ -61,6 +75,12 @@ FP32_MFMA_PEAK_TFLOPS = 157.3                   # MI355X_MICROARCH.md: v_mfma_f3
 BF16_MFMA_PEAK_TFLOPS = 2500.0                  # MI355X_MICROARCH.md: dense bf16 MFMA (not the 2:1-sparsity figure)
 HBM_ACHIEVABLE_TBS = 6.3                        # MI355X_MICROARCH.md: what a streaming kernel reaches of the 8 TB/s spec
 HBM_READ_TBS, HBM_WRITE_TBS = 6.5, 4.6          # measured on this chip by tools/chip_peaks (profiles/r2_chip_peaks.txt): plain read / fill kernels
+# The optimisers' step size.  Every launch of the step runs as in training -- both Adam-AMSGrad updates included, on the same
+# bytes -- but the parameters keep their seeded values, so every step (warm-up and timed) computes the same thing from the same
+# inputs and two runs agree to rounding.  With a step size > 0 the run is a trajectory from a random start, and the atomics of the
+# step (split-K, BN statistics, the crop gradient) change its last bits from run to run; Adam turns that into up to one step size
+# per step on every parameter whose gradient is rounding noise, and the losses of two runs part by tens of percent within 25 steps.
+ADAM_ALPHA = 0.0
 
 
 def parse():
@@ -100,7 +120,16 @@ def parse():
                          "stdout is its compact form")
     ap.add_argument('--cpu-batch', type=int, default=8)
     ap.add_argument('--cpu-iters', type=int, default=4)
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help="measure everything beyond the headline figure too: the roofline (HIP events inside the timed steps), "
+                         "host enqueue time, allocator diagnostics, the secondary legs, the CPU baseline and the detail file; "
+                         "--no-secondary / --no-cpu-baseline / --secondary* / --cpu-* / --traffic-file / --detail-file act on it")
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help="write the losses and the updated model state of the last timed step as DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def cpu_baseline(args, hw, crop):
@@ -381,9 +410,12 @@ def whole_step_binding(w, class_count, ms_per_step, world):
         out["kernel_ms_sum"] = round(sum(v for v in measured.values()), 3)
     return out
 
-def run_workload(w, comm, local_rank, retune):
+def run_workload(w, comm, local_rank, retune, full=True, dump=False):
     """One leg: build the models of workload `w`, W warm-up steps, exactly K timed steps between barrier + synchronize on
-    both sides, max over ranks.  Returns (rank 0) the dict of that leg: value, ms_per_step, config, roofline."""
+    both sides, max over ranks.  Returns (rank 0) the dict of that leg: value, ms_per_step, config, roofline.
+    full=False (a plain bench.py run): no HIP events, FLOP / class accounting or allocator snapshots around the timed steps and
+    no host-enqueue steps after them -- roofline is None.  dump=True: the leg also carries `outputs` (step_outputs) of its
+    last timed step."""
     import loans_amd
     from loans_amd import ops, parallel
     from loans_amd.datasets import synthetic
@@ -424,8 +456,8 @@ def run_workload(w, comm, local_rank, retune):
     comm.bcast_data(localizer)
     comm.bcast_data(discriminator)
 
-    opt_gen = parallel.create_multi_node_optimizer(loans_amd.Adam(alpha=1e-3, amsgrad=True).setup(localizer), comm)
-    opt_dis = parallel.create_multi_node_optimizer(loans_amd.Adam(alpha=1e-3, amsgrad=True).setup(discriminator), comm)
+    opt_gen = parallel.create_multi_node_optimizer(loans_amd.Adam(alpha=ADAM_ALPHA, amsgrad=True).setup(localizer), comm)
+    opt_dis = parallel.create_multi_node_optimizer(loans_amd.Adam(alpha=ADAM_ALPHA, amsgrad=True).setup(discriminator), comm)
     updater = loans_amd.SheepAssessor(
         models=[localizer, discriminator],
         iterator={'main': training.DeviceBatchIterator([frames_d]),
@@ -442,19 +474,26 @@ def run_workload(w, comm, local_rank, retune):
     # ---- timed region: exactly K steps between barrier + synchronize ----
     # HIP events around the conv-forward launches (not under a hipGraph: a replay runs no host code, and events recorded while
     # the step is being captured cannot be read)
-    ops.EVENT_LOG = [] if (rank == 0 and not w.graph) else None
-    ops.FLOP_COUNT = {} if rank == 0 else None         # algorithmic FLOP of every convolution launch of the timed steps
-    ops.CLASS_COUNT = {} if rank == 0 else None        # algorithmic FLOP / bytes of EVERY launch, per kernel class
+    ops.EVENT_LOG = [] if (full and rank == 0 and not w.graph) else None
+    ops.FLOP_COUNT = {} if (full and rank == 0) else None     # algorithmic FLOP of every convolution launch of the timed steps
+    ops.CLASS_COUNT = {} if (full and rank == 0) else None    # algorithmic FLOP / bytes of EVERY launch, per kernel class
     comm.barrier()
     torch.cuda.synchronize()
-    mem0 = torch.cuda.memory_stats(dev)
-    arena = ops.step_arena_state(dev)
+    if full:
+        mem0 = torch.cuda.memory_stats(dev)
+        arena = ops.step_arena_state(dev)
     t0 = time.perf_counter()
     for _ in range(w.steps):
         updater.update()
     torch.cuda.synchronize()
     comm.barrier()
     elapsed = comm.allreduce_max(time.perf_counter() - t0)
+    # what the last timed step computed, taken before anything else runs a step
+    outputs = step_outputs(localizer, discriminator, opt_gen, opt_dis) if (dump and rank == 0) else None
+    if rank == 0 and w.tune_file and not tune_loaded:
+        ops.save_tune_table(w.tune_file)
+    if not full:
+        return leg_result(w, world, comm, elapsed, init_steps, tune_loaded, tune_file, None, outputs=outputs) if rank == 0 else None
     mem1 = torch.cuda.memory_stats(dev)
     # diagnostics only (measurement hygiene): device allocations / allocator retries INSIDE the timed region -- a
     # steady-state step should make none (everything comes from torch's cache); a hipMalloc / hipFree there synchronises the device
@@ -493,28 +532,99 @@ def run_workload(w, comm, local_rank, retune):
 
     if rank != 0:
         return None
-    if w.tune_file and not tune_loaded:
-        ops.save_tune_table(w.tune_file)
     ms_per_step = elapsed / w.steps * 1e3
-    value = B * world * w.steps / elapsed
     roofline = conv_forward_roofline(w, log, flop_count, ev_overhead_ms, ms_per_step, world) if log else None
     if roofline is not None and class_count:
         roofline.setdefault("whole_step", {})["binding"] = whole_step_binding(w, class_count, ms_per_step, world)
+    return leg_result(w, world, comm, elapsed, init_steps, tune_loaded, tune_file, roofline, outputs=outputs,
+                      host_enqueue_ms_per_step=round(host_enqueue_ms, 3), allocator_in_timed_region=allocator)
+
+
+def leg_result(w, world, comm, elapsed, init_steps, tune_loaded, tune_file, roofline, outputs=None, **diagnostics):
+    """the dict of one leg (rank 0); `diagnostics` (--full only) go into its config"""
+    B, hw, crop = w.batch, w.image_size, w.target_size
+    ms_per_step = elapsed / w.steps * 1e3
+    value = B * world * w.steps / elapsed
     backbone = "ResNet-50" if w.resnet50 else "ResNet-18"
-    return {
+    config = {"workload": "LoANs joint step: %s localizer + STN crop + assessor, fwd+bwd+2xAdam-AMSGrad at step size %g "
+                          "(ADAM_ALPHA: parameters stay at their seeded values)" % (backbone, ADAM_ALPHA),
+              "per_gpu_batch": B, "global_batch": B * world, "frame": "3x%dx%d" % (hw, hw),
+              "crop": "3x%dx%d" % (crop, crop), "parallelism": "dp%d" % world, "world_size": world, "dist_backend": comm.backend,
+              "baseline_config": config_label(w, world), "hip_graph": bool(w.graph), "init_steps": init_steps}
+    config.update(diagnostics)
+    config["activation_storage"] = w.storage
+    config["tune_table"] = ("read %d shapes from %s" % (tune_loaded, os.path.relpath(tune_file, ROOT))) if tune_loaded \
+        else "autotuned in this run"
+    out = {
         "value": round(value, 2), "unit": "images/s", "steps": w.steps, "warmup": w.warmup, "ms_per_step": round(ms_per_step, 3),
-        "dtype": w.dtype,
-        "config": {"workload": "LoANs joint step: %s localizer + STN crop + assessor, fwd+bwd+2xAdam-AMSGrad" % backbone,
-                   "per_gpu_batch": B, "global_batch": B * world, "frame": "3x%dx%d" % (hw, hw),
-                   "crop": "3x%dx%d" % (crop, crop), "parallelism": "dp%d" % world, "world_size": world, "dist_backend": comm.backend,
-                   "baseline_config": config_label(w, world), "hip_graph": bool(w.graph), "init_steps": init_steps,
-                   "host_enqueue_ms_per_step": round(host_enqueue_ms, 3),
-                   "allocator_in_timed_region": allocator,
-                   "activation_storage": w.storage,
-                   "tune_table": ("read %d shapes from %s" % (tune_loaded, os.path.relpath(tune_file, ROOT))) if tune_loaded
-                   else "autotuned in this run"},
-        "roofline": roofline,
+        "dtype": w.dtype, "config": config, "roofline": roofline,
     }
+    if outputs is not None:
+        out["outputs"] = outputs
+    return out
+
+
+DUMP_SAMPLE = 1 << 17               # elements kept of a larger array by --dump-outputs (a fixed, seeded sample)
+DUMP_LIMIT = 64 << 20               # bytes of all the arrays --dump-outputs writes
+
+
+def _sample(a, name, seed_name=None):
+    """a itself, or (above DUMP_SAMPLE elements) a fixed sample of it drawn by a generator seeded by `seed_name` (default: the
+    array's name) -- the same elements in every run and every build -- and the name marked '.sample'"""
+    import zlib
+    if a.size <= DUMP_SAMPLE:
+        return a, name
+    idx = np.random.Generator(np.random.PCG64(zlib.crc32((seed_name or name).encode()))).choice(a.size, DUMP_SAMPLE, replace=False)
+    return a.ravel()[np.sort(idx)], name + '.sample'
+
+
+def _logical_concat(model, flat):
+    """an arena-shaped buffer (gradient, Adam moment) of `model` in Chainer layout: every parameter's slice converted to its
+    logical shape, raveled and concatenated in key order -- independent of the arena's physical layout and padding"""
+    arena = model.arena
+    offset = {id(p): o for p, o in zip(arena.params, arena.offsets)}
+    host = flat.detach().float().cpu().numpy()
+    parts = []
+    for _, p in sorted(model.namedparams(), key=lambda kv: kv[0]):
+        o = offset[id(p)]
+        parts.append(np.ravel(p._to_logical(host[o:o + p.size].reshape(p.physical_shape))))
+    return np.concatenate(parts).astype(np.float32)
+
+
+def step_outputs(localizer, discriminator, opt_gen=None, opt_dis=None):
+    """{name: float32 array}: what the timed step computed --
+      loss_localizer, loss_dis            : the two losses it reports;
+      <model>.<key path>                  : the updated state of both models (parameters and BN persistents, Chainer key paths);
+      <model>.adam_m / adam_v / adam_vhat : the Adam-AMSGrad state of both optimisers, Chainer layout, parameters concatenated
+                                            in key order; with every step at the same parameters (ADAM_ALPHA) the step's
+                                            gradient is g = adam_m / (1 - beta1^t) and g^2 = adam_v / (1 - beta2^t) up to
+                                            rounding (the localizer's gradient arena itself is cleared by the step);
+      <model>.adam_t                      : t, the number of Adam steps taken.
+    Arrays above DUMP_SAMPLE elements are cut to a fixed, seeded sample (_sample); the three Adam arrays of a model share theirs."""
+    from loans_amd.runtime.core import reporter
+    out = {}
+    for key in ('loss_localizer', 'loss_dis'):
+        v = reporter.observation[key]
+        v = getattr(v, 'data', v)
+        out[key] = np.asarray(v.detach().float().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float32)
+    for prefix, model, opt in (('localizer', localizer, opt_gen), ('assessor', discriminator, opt_dis)):
+        for key, v in sorted(model.state_dict_chainer().items()):
+            a, name = _sample(np.asarray(v, dtype=np.float32), prefix + '.' + key.replace('/', '.'))
+            out[name] = a
+        if opt is not None and opt._state is not None:
+            for kind, flat in zip(('adam_m', 'adam_v', 'adam_vhat'), opt._state):
+                a, name = _sample(_logical_concat(model, flat), '%s.%s' % (prefix, kind), seed_name=prefix + '.adam')
+                out[name] = a
+            out[prefix + '.adam_t'] = np.asarray(opt.t, dtype=np.float32)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT, ('--dump-outputs would write %d bytes' % total)
+    return out
+
+
+def write_outputs(path, outputs):
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def _pick(d, keys):
@@ -611,11 +721,12 @@ def main():
     torch.cuda.set_device(local_rank)
 
     primary_w = workload_of(args)
-    primary = run_workload(primary_w, comm, local_rank, retune)
+    primary = run_workload(primary_w, comm, local_rank, retune, full=args.full, dump=bool(args.dump_outputs))
+    outputs = primary.pop("outputs", None) if primary else None
     secondary = {}
     is_default = STD_WORKLOADS.get((primary_w.image_size, primary_w.batch, primary_w.dtype, primary_w.storage,
                                     primary_w.target_size, primary_w.resnet50)) == 'b256' and not primary_w.graph
-    if world == 1 and (is_default or args.secondary_shape) and not args.no_secondary:
+    if args.full and world == 1 and (is_default or args.secondary_shape) and not args.no_secondary:
         for label, over in secondary_legs(args):
             gc.collect()
             torch.cuda.empty_cache()
@@ -647,15 +758,18 @@ def main():
     }
     if secondary:
         out["secondary"] = secondary
-    if world == 1 and not args.no_cpu_baseline and not args.resnet50 and args.dtype == 'f32':
+    if args.full and world == 1 and not args.no_cpu_baseline and not args.resnet50 and args.dtype == 'f32':
         out["cpu_baseline"] = cpu_baseline(args, args.image_size, args.target_size)
-    detail = args.detail_file
-    try:
-        with open(detail, 'w') as f:
-            json.dump(out, f)
-    except OSError as err:                      # a read-only tree: the line still goes out
-        print('bench.py: could not write %s: %s' % (detail, err), file=sys.stderr)
-        detail = None
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
+    detail = args.detail_file if args.full else None
+    if detail:
+        try:
+            with open(detail, 'w') as f:
+                json.dump(out, f)
+        except OSError as err:                      # a read-only tree: the line still goes out
+            print('bench.py: could not write %s: %s' % (detail, err), file=sys.stderr)
+            detail = None
     print(json.dumps(compact_line(out, detail)), flush=True)
     parallel.shutdown()
 

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -21,6 +22,15 @@ def _run(script, args, **env):
                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
 
 
+def _free_port():
+    """a port nobody listens on now (what loans_amd/launch.py gives its ranks): a fixed one collides with any other process on
+    the host that holds it, another test session's rank included"""
+    import socket
+    with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
+        s.bind(('127.0.0.1', 0))
+        return str(s.getsockname()[1])
+
+
 def _one_line(r):
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith('{')]
@@ -29,7 +39,7 @@ def _one_line(r):
 
 
 def test_bench_two_ranks_through_the_launcher():
-    out = _one_line(_run('bench.py', ['--gpus', '2'] + TINY, LOANS_DIST_BACKEND='gloo'))
+    out = _one_line(_run('bench.py', ['--gpus', '2', '--full'] + TINY, LOANS_DIST_BACKEND='gloo'))
     assert out['n_gpus'] == 2 and out['config']['world_size'] == 2 and out['config']['dist_backend'] == 'gloo'
     assert out['config']['global_batch'] == 8 and out['scaling'] == 'weak'
     assert out['value'] > 0 and abs(out['value'] - 8 * 1e3 / out['ms_per_step']) < 1e-2 * out['value']
@@ -41,10 +51,50 @@ def test_bench_single_process():
     assert out['n_gpus'] == 1 and out['config']['dist_backend'] is None and out['value'] > 0
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) times the primary leg alone -- no roofline, no secondary legs, no detail file -- and
+    --dump-outputs writes the losses and model state of its last timed step.  A second run with the same arguments starts from
+    the same inputs and every step computes from the same parameters (bench.ADAM_ALPHA), so the two dumps agree to rounding --
+    on the default kernels, whose atomics change the last bits from run to run."""
+    detail = os.path.join(str(tmp_path), 'detail.json')
+    dumps = []
+    for run in range(2):
+        d = os.path.join(str(tmp_path), 'out%d' % run)
+        line = _one_line(_run('bench.py', ['--gpus', '1', '--dump-outputs', d, '--detail-file', detail] + TINY))
+        assert line['steps'] == 2 and line['warmup'] == 1 and line['value'] > 0 and line['roofline'] is None
+        assert abs(line['value'] - 4 * 1e3 / line['ms_per_step']) < 1e-2 * line['value']
+        assert 'secondary' not in line and 'cpu_baseline' not in line and 'detail' not in line and not os.path.exists(detail)
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert set(a) == set(b) and {'loss_localizer', 'loss_dis'} <= set(a)
+    assert any(k.startswith('localizer.') for k in a) and any(k.startswith('assessor.') for k in a)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype == np.float32 and a[k].shape == b[k].shape and np.isfinite(a[k]).all(), k
+        err = float(np.abs(a[k].astype(np.float64) - b[k]).max()) if a[k].size else 0.0
+        # the Adam moments carry the gradients, whose atomic sums cancel in the BN backward: their rounding reaches ~1e-4 of the
+        # largest gradient at this batch of 4 (a wrong gradient is off by O(1)); everything else agrees to ~1e-6
+        rel = 2e-3 if '.adam_' in k else 1e-4
+        assert err <= rel * float(np.abs(a[k]).max(initial=0)) + 1e-7, (k, err)
+    # the dump sees what the step computed, not only the seeded state: BN running statistics moved off their initial values, and
+    # both optimisers' moments hold the step's gradient -- at fixed parameters the same g every step, so after t steps
+    # adam_m = (1 - 0.9^t) g and adam_v = adam_vhat = (1 - 0.999^t) g^2, up to rounding
+    assert any(np.abs(v).max() > 0 for k, v in a.items() if '.avg_mean' in k)
+    for model in ('localizer', 'assessor'):
+        t = float(a[model + '.adam_t'])
+        assert t == 1 + 2, t                                   # warm-up 1 + 2 timed steps
+        m, v, vhat = (a.get('%s.adam_%s.sample' % (model, kind), a.get('%s.adam_%s' % (model, kind))).astype(np.float64)
+                      for kind in ('m', 'v', 'vhat'))
+        g, g2 = m / (1 - 0.9 ** t), v / (1 - 0.999 ** t)
+        assert g2.max() > 0, model
+        assert np.abs(g * g - g2).max() <= 1e-2 * g2.max(), model
+        assert np.abs(vhat - v).max() <= 1e-5 * v.max(), model
+
+
 def test_bench_rccl_at_world_size_one():
     """LOANS_DIST_SELFTEST=1: every collective of the data-parallel step is issued even at world size 1 -- the RCCL (nccl backend)
     path on a one-GPU box: process group, parameter broadcast, the staged all-reduce of both gradient arenas"""
-    e = dict(os.environ, LOANS_DIST_SELFTEST='1', RANK='0', WORLD_SIZE='1', LOCAL_RANK='0', MASTER_ADDR='127.0.0.1', MASTER_PORT='29731')
+    e = dict(os.environ, LOANS_DIST_SELFTEST='1', RANK='0', WORLD_SIZE='1', LOCAL_RANK='0', MASTER_ADDR='127.0.0.1', MASTER_PORT=_free_port())
     e.pop('LOANS_SPLITK', None)
     e.pop('LOANS_DIST_BACKEND', None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1'] + TINY, cwd=ROOT, env=e, timeout=900,
@@ -57,7 +107,7 @@ def test_bench_rccl_at_world_size_one_captured_step():
     """the same with --graph: the data-parallel step captured as hipGraph SEGMENTS with the RCCL exchanges issued between them
     (sheep_updater.py: localizer chain | all-reduce + Adam | assessor chain | all-reduce + Adam) -- until round 6 only the eager
     step had met RCCL"""
-    e = dict(os.environ, LOANS_DIST_SELFTEST='1', RANK='0', WORLD_SIZE='1', LOCAL_RANK='0', MASTER_ADDR='127.0.0.1', MASTER_PORT='29733')
+    e = dict(os.environ, LOANS_DIST_SELFTEST='1', RANK='0', WORLD_SIZE='1', LOCAL_RANK='0', MASTER_ADDR='127.0.0.1', MASTER_PORT=_free_port())
     e.pop('LOANS_SPLITK', None)
     e.pop('LOANS_DIST_BACKEND', None)
     args = ['--gpus', '1', '--graph'] + [a if a != '2' else '4' for a in TINY]          # 4 timed steps: capture happens in warm-up
@@ -77,7 +127,7 @@ def test_bench_secondary_legs_schema(tmp_path):
     and tables in --detail-file; here on tiny shapes (2 x 3 x 320 x 320: res6 and res7 active) behind a tiny primary leg; the
     primary keys stay those of the fp32 leg."""
     detail = os.path.join(str(tmp_path), 'detail.json')
-    r = _run('bench.py', ['--gpus', '1', '--secondary-shape', '2,320', '--secondary-steps', '2',
+    r = _run('bench.py', ['--gpus', '1', '--full', '--secondary-shape', '2,320', '--secondary-steps', '2',
                           '--secondary-warmup', '1', '--detail-file', detail] + TINY)
     line = _one_line(r)
     assert len(r.stdout.strip().splitlines()[-1]) < 4096 and line['detail'] == detail

@@ -13,7 +13,7 @@ for r in $(seq 1 "$reps"); do
   for k in $(seq 0 $((n - 1))); do
     setting=${settings[$(( (k + r - 1) % n ))]}
     i=$((i + 1))
-    ms=$(env $setting python3 bench.py --no-secondary --no-cpu-baseline $args 2>/dev/null | grep '^{' | tail -1 | python3 -c "import json,sys; d=json.load(sys.stdin); print(d['ms_per_step'], d['roofline'].get('conv_fwd_ms_per_step', ''))")
+    ms=$(env $setting python3 bench.py --full --no-secondary --no-cpu-baseline $args 2>/dev/null | grep '^{' | tail -1 | python3 -c "import json,sys; d=json.load(sys.stdin); print(d['ms_per_step'], d['roofline'].get('conv_fwd_ms_per_step', ''))")
     echo "round $r | $setting | $ms" | tee -a "$out"
   done
 done

@@ -4,7 +4,7 @@
 out=$1; reps=$2; args=$3; shift 3
 for r in $(seq 1 "$reps"); do
   for lib in "$@"; do
-    ms=$(python3 tools/ab_lib.py $lib --no-secondary --no-cpu-baseline $args 2>/dev/null | grep '^{' | tail -1 | python3 -c "import json,sys; d=json.load(sys.stdin); print(d['ms_per_step'], d['roofline'].get('conv_fwd_ms_per_step', ''))")
+    ms=$(python3 tools/ab_lib.py $lib --full --no-secondary --no-cpu-baseline $args 2>/dev/null | grep '^{' | tail -1 | python3 -c "import json,sys; d=json.load(sys.stdin); print(d['ms_per_step'], d['roofline'].get('conv_fwd_ms_per_step', ''))")
     echo "round $r | $args | $(basename $lib) | $ms" | tee -a "$out"
   done
 done
