@@ -402,7 +402,8 @@ int loans_maxpool_relu_bwd_bf16(const void* gy, const uint8_t* idx, const void* 
                                 int32_t B, int32_t H, int32_t W, int32_t C, int32_t OH, int32_t OW, void* stream);
 
 /* backward reductions: sums[0][c] += sum g, sums[1][c] += sum g*xhat  with g = gy*(mask>0) (mask may be
- * NULL), xhat = (x-mean)*rstd. If x2 != NULL also sums[2], sums[3] for (x2, mean2, rstd2). */
+ * NULL), xhat = (x-mean)*rstd. If x2 != NULL also sums[2], sums[3] for (x2, mean2, rstd2).
+ * C % 4 == 0 and C / 4 <= 256 or a multiple of 256 (LOANS_EINVAL otherwise); the same holds for loans_colsum_*. */
 int loans_bn_bwd_reduce_f32(const float* gy, const float* mask, const float* x, const float* mean,
                             const float* rstd, const float* x2, const float* mean2, const float* rstd2,
                             double* sums, int64_t rows, int32_t C, void* stream);

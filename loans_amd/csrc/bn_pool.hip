@@ -1029,6 +1029,14 @@ bool reduce_channels_ok(int C) {
     return c4 <= 256 ? (256 % c4 == 0) : (c4 % 256 == 0);
 }
 
+// bn_bwd_reduce_kernel and colsum_kernel leave the threads beyond RL * C4 idle (`rl < RL`), so they take ANY C / 4 <= 256, not
+// only the divisors of 256: the channel counts the 16-byte-unit kernels do not tile (96, 192, ...) have to end here, the BN
+// backward has no other reduction.  (The other entry points keep reduce_channels_ok, which ops.py mirrors.)
+bool reduce_rows_ok(int C) {
+    if (C < 4 || (C & 3)) return false;
+    return C / 4 <= 256 || (C / 4) % 256 == 0;
+}
+
 }  // namespace
 
 extern "C" int loans_bn_finalize_f32(const double* stats, int32_t C, int64_t count, float eps, float decay,
@@ -1277,7 +1285,7 @@ static int bn_bwd_reduce_impl(const T* gy, const T* mask, const T* x, const floa
                               double* sums, int64_t rows, int32_t C, void* stream,
                               const float* scale = nullptr, const float* shift = nullptr, bool bits = false, int replicas = 1) {
     if (!gy || !x || !mean || !rstd || !sums || rows <= 0) return LOANS_EINVAL;
-    if (!reduce_channels_ok(C)) return LOANS_EINVAL;
+    if (!reduce_rows_ok(C)) return LOANS_EINVAL;
     if (x2 && (!mean2 || !rstd2)) return LOANS_EINVAL;
     if (scale && (!shift || mask || x2)) return LOANS_EINVAL;
     hipStream_t st = as_stream(stream);
@@ -1492,7 +1500,7 @@ extern "C" int loans_bn_bwd_apply_xmask_bf16(const void* gy, const void* x, cons
 }
 
 extern "C" int loans_colsum_f32(const float* x, float* out, int64_t rows, int32_t C, void* stream) {
-    if (!x || !out || rows <= 0 || !reduce_channels_ok(C)) return LOANS_EINVAL;
+    if (!x || !out || rows <= 0 || !reduce_rows_ok(C)) return LOANS_EINVAL;
     int rpb, c4b, slabs;
     const int grid = reduce_geometry(rows, C, &rpb, &c4b, &slabs);
     hipLaunchKernelGGL(colsum_kernel<float>, dim3(grid, slabs), dim3(256), 0, as_stream(stream), x, out, rows, c4b, C / 4, rpb);
@@ -1501,7 +1509,7 @@ extern "C" int loans_colsum_f32(const float* x, float* out, int64_t rows, int32_
 }
 
 extern "C" int loans_colsum_bf16(const void* x, float* out, int64_t rows, int32_t C, void* stream) {
-    if (!x || !out || rows <= 0 || !reduce_channels_ok(C)) return LOANS_EINVAL;
+    if (!x || !out || rows <= 0 || !reduce_rows_ok(C)) return LOANS_EINVAL;
     int rpb, c4b, slabs;
     const int grid = reduce_geometry(rows, C, &rpb, &c4b, &slabs);
     hipLaunchKernelGGL(colsum_kernel<__bf16>, dim3(grid, slabs), dim3(256), 0, as_stream(stream), static_cast<const __bf16*>(x), out, rows, c4b, C / 4, rpb);

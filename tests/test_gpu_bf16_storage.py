@@ -889,3 +889,31 @@ def test_bottleneck_with_bn_on_load_is_the_materialised_form(monkeypatch):
     assert torch.equal(o1, o0) and torch.equal(g1, g0)
     for k in p0:
         np.testing.assert_array_equal(p1[k], p0[k], err_msg=k)
+
+
+# ---- the BN / pool kernels on bf16 tensors against the fp64 oracle (NOT against their fp32 twins) over the case grid of
+# tests/bn_cases.py: the fp32 bound plus one round-to-nearest-even of the result; inputs rounded to bf16 first
+from tests import bn_cases
+
+
+@pytest.mark.parametrize("case", bn_cases.bn_grid(), ids=bn_cases.case_id)
+def test_bn_case_grid_bf16_storage(case):
+    bn_cases.assert_paths(case[1], True)
+    bn_cases.report('bn bf16 ' + bn_cases.case_id(case), bn_cases.run_bn_case, bn_cases.HipImpl(True), case)
+
+
+@pytest.mark.parametrize("case", bn_cases.pool_grid(), ids=bn_cases.case_id)
+def test_pool_case_grid_bf16_storage(case):
+    bn_cases.assert_paths(case[1], True)
+    bn_cases.report('pool bf16 ' + bn_cases.case_id(case), bn_cases.check_pool, bn_cases.HipImpl(True), case)
+
+
+@pytest.mark.parametrize("case", [(s, c) for s in bn_cases.POOL_SHAPES for c in (4, 64, 1024)], ids=bn_cases.case_id)
+def test_pool_apply_bias_gradient_without_replicas_bf16_storage(case):
+    bn_cases.report('pool-plain bf16 ' + bn_cases.case_id(case), bn_cases.check_pool_apply_plain, bn_cases.HipImpl(True), case)
+
+
+@pytest.mark.parametrize("C_", [64, 96, 2048])
+def test_colsum_at_the_grid_row_counts_bf16_storage(C_):
+    for b, h, w in bn_cases.SHAPES[:4] + (((3, 150, 147),) if C_ < 2048 else ()):
+        bn_cases.report('colsum bf16 %d C%d' % (b * h * w, C_), bn_cases.check_colsum, bn_cases.HipImpl(True), b * h * w, C_)

@@ -906,3 +906,63 @@ def test_crop_dgrad_one_launch(shape, g16):
         ops.CROP_DGRAD = old
     # (on bf16 gradients the VALU kernel reads the fp32 master weights, this one their bf16 roundings: 2^-9 per weight)
     assert rel_err(out.cpu().numpy(), ref.cpu().numpy()) < (4e-3 if g16 else 5e-6)
+
+
+# ---- the BN / pool kernels against the fp64 oracle over the case grid of tests/bn_cases.py -------------------
+# fp32 tensors; the bf16 instantiations run the same checks at the end of tests/test_gpu_bf16_storage.py.  Every bound is derived
+# in tests/bn_cases.py and proven on its fp32 restatement by tests/test_host_cpu.py; `BN_RATIOS` lines print error / bound.
+from tests import bn_cases
+
+
+@pytest.mark.parametrize("C_", [4, 64, 96])
+@pytest.mark.parametrize("count", bn_cases.FINALIZE_COUNTS)
+def test_bn_finalize_case_grid(count, C_):
+    bn_cases.report('finalize f32 %d C%d' % (count, C_), bn_cases.run_finalize_case, bn_cases.HipImpl(False), count, C_)
+
+
+@pytest.mark.parametrize("case", bn_cases.bn_grid(), ids=bn_cases.case_id)
+def test_bn_case_grid(case):
+    """bn_finalize -> bn_apply (modes 0 / 1 / 2 x relu x sign bits) -> bn_backward (mask none / tensor / own ReLU / sign bits x
+    single / dual, accumulators pre-filled), the second BN with its own x2, statistics and gamma / beta"""
+    bn_cases.assert_paths(case[1], False)
+    bn_cases.report('bn f32 ' + bn_cases.case_id(case), bn_cases.run_bn_case, bn_cases.HipImpl(False), case)
+
+
+@pytest.mark.parametrize("case", bn_cases.pool_grid(), ids=bn_cases.case_id)
+def test_pool_case_grid(case):
+    """bn_relu_maxpool (+ want_sel), maxpool_relu_bwd, pool_bn_backward: gathering sums, xsel sums, the three-pass form where
+    the fused pair does not tile C; gbias pre-filled"""
+    bn_cases.assert_paths(case[1], False)
+    bn_cases.report('pool f32 ' + bn_cases.case_id(case), bn_cases.check_pool, bn_cases.HipImpl(False), case)
+
+
+@pytest.mark.parametrize("case", [(s, c) for s in bn_cases.POOL_SHAPES for c in (4, 64, 1024)], ids=bn_cases.case_id)
+def test_pool_apply_bias_gradient_without_replicas(case):
+    bn_cases.report('pool-plain f32 ' + bn_cases.case_id(case), bn_cases.check_pool_apply_plain, bn_cases.HipImpl(False), case)
+
+
+@pytest.mark.parametrize("C_", [64, 96, 2048])
+def test_colsum_at_the_grid_row_counts(C_):
+    for b, h, w in bn_cases.SHAPES[:4] + (((3, 150, 147),) if C_ < 2048 else ()):
+        bn_cases.report('colsum f32 %d C%d' % (b * h * w, C_), bn_cases.check_colsum, bn_cases.HipImpl(False), b * h * w, C_)
+
+
+def test_bn_backward_channel_counts_the_launchers_take_or_refuse():
+    """C = 96 (no 16-byte-unit tiling in either storage type) runs on the fall-back reduction -- the launcher used to answer
+    LOANS_EINVAL for it, ops.bn_backward raised; a count no kernel tiles (C / 4 = 384) is refused by return code"""
+    from loans_amd import ops
+    lib = ops._lib.load()
+    for tdt in (torch.float32, torch.bfloat16):
+        for C_, want in ((96, 0), (192, 0), (1536, -1)):
+            assert not ops.bn_units_ok(C_, tdt == torch.bfloat16)
+            x = torch.ones((8, C_), device='cuda', dtype=tdt)
+            vec = torch.ones(C_, device='cuda')
+            sums = torch.zeros((2, C_), device='cuda', dtype=torch.float64)
+            fn = lib.loans_bn_bwd_reduce_bf16 if tdt == torch.bfloat16 else lib.loans_bn_bwd_reduce_f32
+            rc = fn(ops._ptr(x), None, ops._ptr(x), ops._ptr(vec), ops._ptr(vec), None, None, None, ops._ptr(sums), 8, C_, ops._stream())
+            assert rc == want, (C_, tdt, rc)
+            if want == 0:
+                assert torch.equal(sums[0], torch.full((C_,), 8.0, device='cuda', dtype=torch.float64)) and not sums[1].any()
+            out = torch.zeros(C_, device='cuda')
+            fn = lib.loans_colsum_bf16 if tdt == torch.bfloat16 else lib.loans_colsum_f32
+            assert fn(ops._ptr(x), ops._ptr(out), 8, C_, ops._stream()) == want

@@ -573,3 +573,41 @@ def test_tune_file_named_by_the_environment_is_loaded_at_import(tmp_path):
         out = subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, timeout=300, cwd=root)
         assert out.returncode == 0, out.stderr[-2000:]
         assert out.stdout.strip().splitlines()[-1] == want, (env_value, out.stdout)
+
+
+def test_bn_case_grid_covers_every_dispatch_cell():
+    """tests/bn_cases.py: the channel counts select the paths the grid lists them for (ops.bn_units_ok / reduce_channels_ok), and
+    every path meets the one-row, the sub-block, the odd and the big shape"""
+    from tests import bn_cases
+    bn_cases.assert_grid_covers_every_path()
+    for C_ in bn_cases.PATHS:
+        for bf16 in (False, True):
+            bn_cases.assert_paths(C_, bf16)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_bn_case_grid_restatement_is_inside_the_derived_bounds(dtype):
+    """Before any GPU run: an fp32 NumPy restatement of every form the -m gpu grid tests check (tests/bn_cases.py: NumpyImpl)
+    stays inside the derived bounds on EVERY generated case, and the share of elements whose ReLU sign / argmax is excluded
+    from the exact comparisons is at most 1e-4 (asserted inside the checks).  The largest ratios are the table of DESIGN 3."""
+    from tests import bn_cases
+    impl = bn_cases.NumpyImpl(dtype == "bf16")
+    worst = {}
+    def run(fn, *args):
+        for k, v in bn_cases.report('%s restatement' % dtype, fn, impl, *args).items():
+            worst[k] = max(worst.get(k, 0.0), v)
+    for count in bn_cases.FINALIZE_COUNTS:
+        for C_ in (4, 64, 96):
+            run(bn_cases.run_finalize_case, count, C_)
+    for case in bn_cases.bn_grid():
+        run(bn_cases.run_bn_case, case)
+    for case in bn_cases.pool_grid():
+        run(bn_cases.check_pool, case)
+    for case in [(s, c) for s in bn_cases.POOL_SHAPES for c in (4, 64, 1024)]:
+        run(bn_cases.check_pool_apply_plain, case)
+    for C_ in (64, 96, 2048):
+        for b, h, w in bn_cases.SHAPES[:4] + (((3, 150, 147),) if C_ < 2048 else ()):
+            run(bn_cases.check_colsum, b * h * w, C_)
+    print('BN_RATIOS_WORST %s %s' % (dtype, __import__('json').dumps(worst, sort_keys=True)))
+    assert worst and max(v for k, v in worst.items() if not k.startswith('share:')) <= 1.0
+    assert max([v for k, v in worst.items() if k.startswith('share:')] + [0.0]) <= bn_cases.MAX_AMBIGUOUS_SHARE
