@@ -1125,14 +1125,25 @@ struct WgradArgs {
     loans_igemm_desc d;
     int M, Ktot, tiles_co, tiles_j, splits, chunks_per_split;
     int bf16;
+    int dbg;            // experiment bits (LOANS_EXPERIMENT builds only; 0 in the product library)
     unsigned x_bytes, gy_bytes;
+    // the loader's 32-pixel advance (set by the launcher, see wgrad_advance()): a row's input coordinates and byte offsets
+    // move by a constant, plus a correction when the pixel passes the end of a grid row and one when it passes the last row
+    struct Adv {
+        int ix, ix_wrap;                // input column: + ix, and - ix_wrap once it is past the row end
+        int iy, iy_carry, iy_wrap;      // input row: + iy (+ iy_carry instead past the row end), and - iy_wrap once it is past the last row
+        unsigned g, g_carry, g_wrap;    // gy byte offset: + g (+ g_carry instead past the row end), + g_wrap past the last row
+        unsigned x, x_carry, x_wrap;    // x byte offset, likewise
+    } adv;
 };
 
 // BF16 = true: fragments are packed to bf16 after the (fp32, conflict-free) LDS reads and contracted on the
 // 32x32x16 bf16 MFMA; staging and accumulation stay fp32.
 // GY16 = true (LOANS_F_GY_BF16, the stem of the bf16-storage arm): gy is a bf16 tensor; a thread fetches its four
 // channels as 8 bytes and widens them while staging, the LDS image and everything behind it are unchanged.
-template <int BCO, int BJ, bool RELU, bool BF16, bool GY16 = false>   // BCO (output channels) x BJ (tap-channel columns) block tile, 4 waves as 2 x 2
+// STANDIN (LOANS_EXPERIMENT builds, LOANS_DBG bit 1; wrong results on purpose): the loader's offsets advance by a constant --
+// the same loads without the row-end / image-end corrections, the floor of what the loader's address arithmetic can cost.
+template <int BCO, int BJ, bool RELU, bool BF16, bool GY16 = false, bool STANDIN = false>   // BCO (output channels) x BJ (tap-channel columns) block tile, 4 waves as 2 x 2
 __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a) {
     static_assert(BCO <= BJ, "the loader's thread map follows the wider (X) tile");
     constexpr int TM = BCO / 2 / 32, TN = BJ / 2 / 32;   // MFMA tiles per wave
@@ -1175,46 +1186,56 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a) {
     const int total_chunks = (a.M + 31) / 32;
     if (c_end > total_chunks) c_end = total_chunks;
 
-    // (b, y, x) of this thread's NP rows, advanced by 32 pixels per chunk without divisions
-    int pb[NP], py[NP], px[NP];
+    // Per chunk row of this thread: the tap-shifted input coordinates and the byte offsets of its two loads, computed from
+    // (b, y, x) once, here, and from then on ADVANCED by 32 pixels per chunk.  32 = q * gridW + r with r < gridW, so x + r
+    // passes the row end at most once; q = n * gridH + s with s < gridH, so y + s + carry passes the last row at most once
+    // (a.adv holds the steps, wgrad_advance()).  The loop is left with adds, compares and selects: no multiply, no division.
+    int pix[NP], piy[NP];
+    unsigned pgo[NP], pxo[NP];
+    const int ix_end = d.gridW * d.isx + dx, iy_end = d.gridH * d.isy + dy;     // first ix / iy behind the grid, for this tap
+    const WgradArgs::Adv adv = a.adv;           // in registers: a select between two kernel arguments would become a load
     {
         const int gHW = d.gridH * d.gridW;
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
             const int m = c_begin * 32 + prow + RPP * p;
-            pb[p] = m / gHW;
-            const int rem = m - pb[p] * gHW;
-            py[p] = rem / d.gridW;
-            px[p] = rem - py[p] * d.gridW;
+            const int b = m / gHW;
+            const int rem = m - b * gHW;
+            const int y = rem / d.gridW;
+            const int x = rem - y * d.gridW;
+            const int pixel = (b * d.outH + y * d.osy + d.oy0) * d.outW + x * d.osx + d.ox0;
+            pgo[p] = (unsigned)(pixel * d.Cout + yco) * (GY16 ? 2u : 4u);
+            piy[p] = y * d.isy + dy;
+            pix[p] = x * d.isx + dx;
+            pxo[p] = (unsigned)(((b * d.inH + piy[p]) * d.inW + pix[p]) * ucin + xc4 * 4) * 4u;
         }
     }
-    const float inv_gw = 1.f / (float)d.gridW, inv_gh = 1.f / (float)d.gridH;
 
     f32x4 ry[NP], rx[NP];
-    // one loader piece = one chunk row of this thread: two bounds-checked loads + the coordinate advance
-    auto load_row = [&](int p) {
-        const int b = pb[p], y = py[p], x = px[p];
-        const bool rv = b < d.B;
-        const int pix = (b * d.outH + y * d.osy + d.oy0) * d.outW + x * d.osx + d.ox0;
-        const unsigned goff = ((unsigned)(pix * d.Cout + yco) * (GY16 ? 2u : 4u)) | ((unsigned)(rv & yv) - 1u);
+    // one loader piece = one row of chunk c for this thread: two bounds-checked loads + the advance to chunk c + 1
+    auto load_row = [&](int p, int c) {
+        const bool rv = prow + RPP * p < a.M - c * 32;          // rows behind the last image load nothing
+        const unsigned goff = (rv & yv) ? pgo[p] : ~0u;
         if constexpr (GY16) {
             ry[p] = __builtin_convertvector(__builtin_bit_cast(bf16x4_t, __builtin_amdgcn_raw_buffer_load_b64(rs_g, (int)goff, 0, 0)), f32x4);
         } else {
             ry[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_g, (int)goff, 0, 0));
         }
-        const int iy = y * d.isy + dy, ix = x * d.isx + dx;
-        const unsigned ok = (unsigned)(rv & xtv) & (unsigned)((unsigned)iy < (unsigned)d.inH) &
-                            (unsigned)((unsigned)ix < (unsigned)d.inW);
-        const unsigned xoff = ((unsigned)(((b * d.inH + iy) * d.inW + ix) * ucin + xc4 * 4) * 4u) | (ok - 1u);
+        const bool ok = rv & xtv & ((unsigned)piy[p] < (unsigned)d.inH) & ((unsigned)pix[p] < (unsigned)d.inW);
+        const unsigned xoff = ok ? pxo[p] : ~0u;
         rx[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, (int)xoff, 0, 0));
-        // advance 32 pixels: exact floor((v + .5) / n) for the small integers involved
-        int nx = x + 32;
-        const int qx = (int)(((float)nx + 0.5f) * inv_gw);
-        nx -= qx * d.gridW;
-        int ny = y + qx;
-        const int qy = (int)(((float)ny + 0.5f) * inv_gh);
-        ny -= qy * d.gridH;
-        px[p] = nx; py[p] = ny; pb[p] = b + qy;
+        if constexpr (STANDIN) {
+            pix[p] += adv.ix; piy[p] += adv.iy; pgo[p] += adv.g; pxo[p] += adv.x;
+        } else {
+            const int nx = pix[p] + adv.ix;
+            const bool carry = nx >= ix_end;
+            pix[p] = nx - (carry ? adv.ix_wrap : 0);
+            const int ny = piy[p] + (carry ? adv.iy_carry : adv.iy);
+            const bool wrap = ny >= iy_end;
+            piy[p] = ny - (wrap ? adv.iy_wrap : 0);
+            pgo[p] += (carry ? adv.g_carry : adv.g) + (wrap ? adv.g_wrap : 0u);
+            pxo[p] += (carry ? adv.x_carry : adv.x) + (wrap ? adv.x_wrap : 0u);
+        }
     };
     auto store_y = [&](int buf, int p) {
         if (ythread) *reinterpret_cast<f32x4*>(Ys + (buf * 32 + prow + RPP * p) * BCO + unit * 4) = ry[p];
@@ -1258,7 +1279,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a) {
     float fa0[TM], fb0[TN], fa1[TM], fb1[TN];
     if (c_begin < c_end) {
 #pragma unroll
-        for (int p = 0; p < NP; ++p) load_row(p);
+        for (int p = 0; p < NP; ++p) load_row(p, c_begin);
 #pragma unroll
         for (int p = 0; p < NP; ++p) { store_y(0, p); store_x(0, p); }
     }
@@ -1271,7 +1292,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a) {
             const bool more = (c + 1) < c_end;
             if (more) {
 #pragma unroll
-                for (int p = 0; p < NP; ++p) load_row(p);
+                for (int p = 0; p < NP; ++p) load_row(p, c + 1);
             }
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
@@ -1316,7 +1337,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a) {
                 for (int q = 0; q < NMMA; ++q) {
                     if (s & 1) mma_one(q, fa1, fb1); else mma_one(q, fa0, fb0);
                     if (q == 0) {
-                        if (s < NP) load_row(s);
+                        if (s < NP) load_row(s, c + 1);
                         if (s >= 7 && s < 7 + 2 * NP) {        // all LDS writes land before step 15's barrier
                             const int w = s - 7;
                             if (w & 1) store_x(buf ^ 1, w >> 1); else store_y(buf ^ 1, w >> 1);
@@ -1356,12 +1377,42 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a) {
         }
 }
 
+// the steps of the loader's 32-pixel advance (WgradArgs::Adv); byte offsets are taken modulo 2^32 like the kernel's own
+void wgrad_advance(WgradArgs& a, unsigned gy_elem_bytes) {
+    const loans_igemm_desc& d = a.d;
+    const int q = 32 / d.gridW, r = 32 % d.gridW;         // 32 pixels = q grid rows + r pixels
+    const int n = q / d.gridH, s = q % d.gridH;           // q grid rows = n images + s rows
+    const unsigned ucin = (d.flags & LOANS_F_DENSE) ? 1u : (unsigned)d.Cin;
+    const unsigned gpix = (unsigned)d.Cout * gy_elem_bytes, xpix = ucin * 4u;       // bytes per gy pixel / per unit of ix
+    const unsigned outW = d.outW, outH = d.outH, inW = d.inW, inH = d.inH;
+    WgradArgs::Adv& v = a.adv;
+    v.ix = r * d.isx;
+    v.ix_wrap = d.gridW * d.isx;
+    v.iy = s * d.isy;
+    v.iy_carry = (s + 1) * d.isy;
+    v.iy_wrap = d.gridH * d.isy;
+    v.g = ((n * outH + (unsigned)(s * d.osy)) * outW + (unsigned)(r * d.osx)) * gpix;
+    v.g_carry = v.g + ((unsigned)d.osy * outW - (unsigned)(d.gridW * d.osx)) * gpix;          // one row down, gridW pixels back
+    v.g_wrap = (outH * outW - (unsigned)(d.gridH * d.osy) * outW) * gpix;                     // one image on, gridH rows back
+    v.x = ((n * inH + (unsigned)(s * d.isy)) * inW + (unsigned)(r * d.isx)) * xpix;
+    v.x_carry = v.x + ((unsigned)d.isy * inW - (unsigned)(d.gridW * d.isx)) * xpix;
+    v.x_wrap = (inH * inW - (unsigned)(d.gridH * d.isy) * inW) * xpix;
+}
+
 template <int BCO, int BJ, bool RELU, bool BF16, bool GY16 = false>
 int launch_wgrad_r(WgradArgs& a, int splits_req, hipStream_t st) {
     static loans_device_once lds_limit_set;       // per template instance = per kernel, one bit per device
     constexpr size_t lds = (size_t)2 * 32 * (BCO + BJ) * 4;
     auto kern = wgrad_kernel<BCO, BJ, RELU, BF16, GY16>;
     if (int rc_ = loans_raise_lds_limit(lds_limit_set, reinterpret_cast<const void*>(kern), lds)) return rc_;
+#ifdef LOANS_EXPERIMENT
+    if (a.dbg & 1) {
+        static loans_device_once standin_lds_limit_set;
+        kern = wgrad_kernel<BCO, BJ, RELU, BF16, GY16, true>;
+        if (int rc_ = loans_raise_lds_limit(standin_lds_limit_set, reinterpret_cast<const void*>(kern), lds)) return rc_;
+    }
+#endif
+    wgrad_advance(a, GY16 ? 2u : 4u);
     a.tiles_co = (a.d.Cout + BCO - 1) / BCO;
     a.tiles_j = (a.Ktot + BJ - 1) / BJ;
     const int total_chunks = (a.M + 31) / 32;
@@ -1425,6 +1476,10 @@ static int wgrad_impl(const float* x, const float* gy, float* dw, const loans_ig
     WgradArgs a;
     a.x = x; a.gy = gy; a.dw = dw; a.d = *d;
     a.bf16 = bf16;
+    a.dbg = 0;
+#ifdef LOANS_EXPERIMENT
+    if (const char* e = getenv("LOANS_DBG")) a.dbg = atoi(e);
+#endif
     a.M = d->B * d->gridH * d->gridW;
     a.Ktot = d->ntaps * d->Cin;
     {
