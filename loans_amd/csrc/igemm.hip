@@ -18,6 +18,7 @@
 //   MFMAs of chunk c and written to the other LDS buffer after them (one barrier per chunk).
 #include "common.h"
 #include <stdlib.h>
+#include <type_traits>
 
 #ifdef LOANS_STAMPS
 // Diagnostic build only (tools/stamp_build.sh): per-wave cycle sums of the K-loop phases of the
@@ -294,6 +295,35 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
     }
     unsigned toff = (unsigned)taps[min(tap, LOANS_MAX_TAPS - 1)] + (unsigned)c4 * 16u;   // prefetched one chunk ahead
 
+    // Per-tap loader state (fp32 arms, Cin % 32 == 0, not LOANS_F_DENSE: every 64- to 512-channel layer, forward and data
+    // gradient).  A 32-deep chunk then lies inside ONE tap, the tap is the same for the whole block and Ktot has no tail, so
+    // nothing per lane changes from chunk to chunk within a tap: the per-lane offsets below are made once per tap (A) or
+    // once per launch (B), and the walk along K is a wave-uniform byte count in the buffer loads' scalar offset.  A lane
+    // whose offset is the all-ones mask stays out of range whatever the scalar offset adds on top: it still reads zeros.
+    const bool per_tap = !BF16 && !dense && (d.Cin & 31) == 0;
+    const int cpc = d.Cin >> 5;                 // chunks per tap
+    int ktap = 0, kcw = 0;                      // tap and chunk within the tap of the chunk loaded next (SGPRs)
+    unsigned sof_a = 0, sof_b = 0;              // scalar offsets: 128 * kcw into the tap's channels, 128 * chunk along a weight row
+    unsigned voff_a[RA], voff_b[RB], rowlane[RA];
+    auto tap_voff = [&](int i) {                // the general loader's formula, once per tap: all ones where the tap is masked
+        const int tc = min(ktap, LOANS_MAX_TAPS - 1);
+        const unsigned bad = 0u - ((unsigned)(badmask[i] >> tc) & 1u);
+        voff_a[i] = (rowlane[i] + (unsigned)taps[tc]) | bad;
+    };
+    auto tap_begin = [&]() {                    // called on the per-tap path only: nothing of it is live on the other one
+        ktap = c_begin / cpc;
+        kcw = c_begin - ktap * cpc;
+        sof_a = 128u * (unsigned)kcw;
+        sof_b = 128u * (unsigned)c_begin;
+#pragma unroll
+        for (int i = 0; i < RA; ++i) {
+            rowlane[i] = rowoff[i] + (unsigned)lu * 16u;
+            tap_voff(i);
+        }
+#pragma unroll
+        for (int i = 0; i < RB; ++i) voff_b[i] = (woff[i] + (unsigned)lu * 16u) | wbad[i];
+    };
+
     f32x4 ra[RA], rb[RB];
     // The loader is cut into RA + RB + 1 independent pieces (one buffer load each, then the advance) so
     // that the K loop can drop one piece behind each MFMA of group 0: no waits, no branches.
@@ -338,6 +368,34 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
 #pragma unroll
         for (int i = 0; i < RB; ++i) load_b(i);
         advance();
+    };
+    // The per-tap loader's pieces.  0 .. RA + RB - 1: one buffer load each (into registers, or by LDS-DMA into stage `buf`),
+    // no address arithmetic.  RA + RB: the advance -- scalar adds and one block-uniform branch, taken when the chunk loaded
+    // next starts a new tap: it holds no MFMA, reads the tap table and makes the A offsets of that tap, behind the loads
+    // that still use the old ones.
+    auto tap_piece = [&](int buf, int p) {
+        if (p < RA) {
+            if constexpr (DMA)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_ptr_t)(As + (buf * BM + 32 * p + 8 * wave_u) * BK), 16, (int)voff_a[p], (int)sof_a, 0, 0);
+            else if (!DBGSKIP(16))
+                ra[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)voff_a[p], (int)sof_a, 0));
+        } else if (p < RA + RB) {
+            const int i = p - RA;
+            if constexpr (DMA)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_ptr_t)(Bs + (buf * BN + 32 * i + 8 * wave_u) * BK), 16, (int)voff_b[i], (int)sof_b, 0, 0);
+            else if (!DBGSKIP(16))
+                rb[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_w, (int)voff_b[i], (int)sof_b, 0));
+        } else if (p == RA + RB) {
+            sof_b += 128u;
+            sof_a += 128u;
+            if (++kcw == cpc) {
+                kcw = 0;
+                sof_a = 0u;
+                ++ktap;
+#pragma unroll
+                for (int i = 0; i < RA; ++i) tap_voff(i);
+            }
+        }
     };
     auto store_a = [&](int buf, int i) {
         if (RELU) {
@@ -456,8 +514,16 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
         else if (p == RA + RB) advance();
     };
     f32x4 fa0[TM], fb0[TN], fa1[TM], fb1[TN];
+    // the K loop with the general loader or (block-uniform choice, FAST) the per-tap loader, whose K has no tail
+    auto k_loop = [&](auto fast_tag) {
+    constexpr bool FAST = decltype(fast_tag)::value;
+    auto piece = [&](int buf, int p) {
+        if constexpr (FAST) tap_piece(buf, p);
+        else dma_piece(buf, p);
+    };
+    if constexpr (FAST) tap_begin();
 #pragma unroll
-    for (int p = 0; p < NPIECE; ++p) dma_piece(0, p);
+    for (int p = 0; p < NPIECE; ++p) piece(0, p);
     __syncthreads();
     read_frag(0, 0, fa0, fb0);
     __builtin_amdgcn_s_setprio(0);
@@ -470,7 +536,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
 #pragma unroll
         for (int s = 0; s < NMMA; ++s) {
             mma_one(s, fa0, fb0);
-            dma_piece(buf ^ 1, s);
+            piece(buf ^ 1, s);
             __builtin_amdgcn_sched_barrier(0);
         }
         read_frag(buf, 2, fa0, fb0);
@@ -479,7 +545,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
 #pragma unroll
         for (int s = 0; s < NMMA; ++s) {
             mma_one(s, fa1, fb1);
-            dma_piece(buf ^ 1, NMMA + s);
+            piece(buf ^ 1, NMMA + s);
             __builtin_amdgcn_sched_barrier(0);
         }
         read_frag(buf, 3, fa1, fb1);
@@ -496,7 +562,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
     }
     {   // last chunk (see the register-staged loop)
         const int buf = c & 1;
-        const int tg = tail_groups;
+        const int tg = FAST ? 4 : tail_groups;
         if (tg > 1) read_frag(buf, 1, fa1, fb1);
         relu_frag(fa0);
         mma(fa0, fb0);
@@ -512,6 +578,9 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
             }
         }
     }
+    };
+    if (per_tap) k_loop(std::true_type{});
+    else k_loop(std::false_type{});
     } else {
     // MFMA number s (0 .. NMMA-1) of a k group
     auto mma_one = [&](int s, const f32x4 (&af)[TM], const f32x4 (&bf)[TN]) {
@@ -542,7 +611,16 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
         else if (p < RA + RB) store_b(buf, p - RA);
     };
     f32x4 fa0[TM], fb0[TN], fa1[TM], fb1[TN];
-    load_chunk();
+    // the K loop with the general loader or (block-uniform choice, FAST) the per-tap loader, whose K has no tail
+    auto k_loop = [&](auto fast_tag) {
+    constexpr bool FAST = decltype(fast_tag)::value;
+    if constexpr (FAST) {
+        tap_begin();
+#pragma unroll
+        for (int p = 0; p < NPIECE; ++p) tap_piece(0, p);
+    } else {
+        load_chunk();
+    }
     store_chunk(0);
     __syncthreads();
     read_frag(0, 0, fa0, fb0);
@@ -560,7 +638,10 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
         for (int s = 0; s < NMMA; ++s) {
             mma_one(s, fa0, fb0);
 #pragma unroll
-            for (int p = s * PPG; p < (s + 1) * PPG; ++p) load_piece(p);
+            for (int p = s * PPG; p < (s + 1) * PPG; ++p) {
+                if constexpr (FAST) tap_piece(0, p);
+                else load_piece(p);
+            }
             __builtin_amdgcn_sched_barrier(0);
         }
         STAMP(t1);
@@ -595,7 +676,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
     {   // last chunk: nothing left to stage; 8-deep groups that lie wholly beyond Ktot hold zeros on both sides
         // and are skipped (block-uniform branch): exact, and a quarter of the stem's K is such padding
         const int buf = c & 1;
-        const int tg = tail_groups;
+        const int tg = FAST ? 4 : tail_groups;
         if (tg > 1) read_frag(buf, 1, fa1, fb1);
         mma(fa0, fb0);
         if (tg > 1) {
@@ -608,6 +689,9 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
             }
         }
     }
+    };
+    if (per_tap) k_loop(std::true_type{});
+    else k_loop(std::false_type{});
     }   // fp32 / bf16 K loop
 #ifdef LOANS_STAMPS
     unsigned long long t_loop_end = 0;
