@@ -152,7 +152,11 @@ typedef struct loans_igemm_desc {
                                       own halo image, own vmcnt, own staging slab): no block barrier after the weights have landed */
 #define LOANS_TILE_WGHALO_64   38  /* loans_wgrad_bf16s, stride-1 3 x 3 forward geometries with Cin % 64 == 0, Cout % 64 == 0: a block owns 64 output x 64
                                       input channels x ALL nine taps and walks 8 x 16 pixel tiles; gradient tile and input halo tile staged once per
-                                      tile, a tap is a window shift in LDS (csrc/wgrad_halo_bf16.hip).  splits = blocks per channel-tile pair */
+                                      tile, a tap is a window shift in LDS (csrc/wgrad_halo_bf16.hip).  splits = blocks per channel-tile pair.
+                                      loans_wgrad_f32 (flags RELU_IN or none): the same ownership on v_mfma_f32_32x32x2_f32, the reduction
+                                      index is the pixel (csrc/wgrad_halo_f32.hip); pixel tiles are 7 x 14, or 7 x 8 where that covers the
+                                      frame with fewer padded pixels (ceil(H/7) ceil(W/8) 56 < ceil(H/7) ceil(W/14) 98: the 7 x 7 frame);
+                                      fp32 atomics into dw.  LOANS_EINVAL, dw untouched, for any other geometry */
 #define LOANS_TILE_WGHALO_128  39  /* the same with 128 output channels per block on eight waves (Cout % 128 == 0) */
 #define LOANS_TILE_PW          40  /* loans_igemm_bf16s, 1 x 1 / 1 forward geometries with Cin in {64, 128}, Cout % 64 == 0, Cout <= 512, or Cin = 256,
                                       Cout % 128 == 0, Cout <= 1024; flags STATS or none (ResNet-50's res2 / res3 / res4 bottleneck expansions): a wave owns 32-pixel strips, operands go global -> VGPR

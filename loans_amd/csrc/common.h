@@ -134,6 +134,12 @@ int loans_halo16_launch(const void* in, const void* w, void* out, const float* b
 int loans_pw16_covers(const loans_igemm_desc* d);
 int loans_pw16_launch(const void* in, const void* w, void* out, double* stats, const float* aff, const loans_igemm_desc* d, hipStream_t st);
 
+// wgrad_halo_f32.hip: weight gradient of stride-1 3 x 3 convolutions on fp32 tensors with all taps in one block
+// (LOANS_TILE_WGHALO_64; internal, reached through loans_wgrad_f32)
+int loans_wgrad_halo32_covers(const loans_igemm_desc* d);
+int loans_wgrad_halo32_launch(const float* x, const float* gy, float* dw, const loans_igemm_desc* d, int splits,
+                              unsigned x_bytes, unsigned gy_bytes, hipStream_t st);
+
 // wgrad_halo_bf16.hip: weight gradient of stride-1 3 x 3 convolutions on bf16 storage with all taps in one block
 // (LOANS_TILE_WGHALO_*; internal, reached through loans_wgrad_bf16s)
 int loans_wgrad_halo16_covers(const loans_igemm_desc* d, int tile);

@@ -1581,6 +1581,8 @@ static int wgrad_impl(const float* x, const float* gy, float* dw, const loans_ig
     if (tile == LOANS_TILE_64x64) return launch_wgrad<64, 64>(a, splits, st);
     if (tile == LOANS_TILE_128x128) return launch_wgrad<128, 128>(a, splits, st);
     if (tile == LOANS_TILE_64x128) return launch_wgrad<64, 128>(a, splits, st);
+    if (tile == LOANS_TILE_WGHALO_64)       // all nine taps of a stride-1 3 x 3 layer in one block (wgrad_halo_f32.hip)
+        return bf16 ? LOANS_EINVAL : loans_wgrad_halo32_launch(x, gy, dw, d, splits, a.x_bytes, a.gy_bytes, st);
     return LOANS_EINVAL;
 }
 

@@ -1495,25 +1495,37 @@ TILE_WGHALO_64, TILE_WGHALO_128 = 38, 39
 WGHALO = True
 
 
+def wghalo_f32_ntiles(B, H, W):
+    """pixel tiles the fp32 kernel walks on B frames of H x W (csrc/wgrad_halo_f32.hip: pair_tile, narrow_tile): image pairs up to
+    7 x 7 pixels, else 7 x 14 tiles unless 7 x 8 ones cover the frame with fewer padded pixels"""
+    if H <= 7 and W <= 7:
+        return (B + 1) // 2
+    wide = ((H + 6) // 7) * ((W + 13) // 14)
+    narrow = ((H + 6) // 7) * ((W + 7) // 8)
+    return B * (narrow if narrow * 56 < wide * 98 else wide)
+
+
 @_memo
-def wghalo_tiles(geo):
-    """the halo weight-gradient tiles that cover this geometry (loans_wgrad_halo16_covers), where an 8 x 16 pixel tile is not
-    mostly empty"""
+def wghalo_tiles(geo, f32=False):
+    """the halo weight-gradient tiles that cover this geometry (loans_wgrad_halo16_covers; f32: loans_wgrad_halo32_covers),
+    where an 8 x 16 pixel tile (f32: a 7 x 8 one) is not mostly empty"""
     if not WGHALO or geo.dense or geo.k != 3 or geo.stride != 1 or geo.Cin % 64 or geo.Cout % 64 or (geo.Ho, geo.Wo) != (geo.H, geo.W):
         return ()
+    if f32:
+        return (TILE_WGHALO_64,) if geo.H >= 5 and geo.W >= 6 else ()
     if geo.H < 6 or geo.W < 12:
         return ()
     return (TILE_WGHALO_64,) + ((TILE_WGHALO_128,) if geo.Cout % 128 == 0 else ())
 
 
 @_memo
-def _wghalo_candidates(geo):
+def _wghalo_candidates(geo, f32=False):
     """(tile | blocks per channel-tile pair << 8): whole rounds of the machine's block slots (two 4-wave blocks or one 8-wave
-    block per CU), 0 = the library's default"""
+    block per CU), 0 = the library's default.  f32: the fp32 arm's tile (two blocks per CU, its own pixel tiles)"""
     cus = side_stream_cus()
-    ntiles = geo.B * ((geo.H + 7) // 8) * ((geo.W + 15) // 16)
+    ntiles = wghalo_f32_ntiles(geo.B, geo.H, geo.W) if f32 else geo.B * ((geo.H + 7) // 8) * ((geo.W + 15) // 16)
     out = []
-    for t in wghalo_tiles(geo):
+    for t in wghalo_tiles(geo, f32):
         bco, per_cu = (64, 2) if t == TILE_WGHALO_64 else (128, 1)
         npairs = (geo.Cout // bco) * (geo.Cin // 64)
         cand = {0}
@@ -1600,6 +1612,8 @@ def _conv_wgrad(x, gy, dw, geo, relu_in, splits, tile, stream=None, in_affine=No
             cands = _wgrad_candidates(geo, cands, 32, _WGRAD16_TILE_DIMS if s16 else None)
             if s16:
                 cands = tuple(cands) + _wghalo_candidates(geo)
+            elif wfn is lib.loans_wgrad_f32:
+                cands = tuple(cands) + _wghalo_candidates(geo, True)
         stem = fl == F_DENSE and ((stem_wgrad_ok(geo) and wfn is lib.loans_wgrad_f32) or (s16 and stem16_wgrad_ok(geo)))
         if stem:
             cands = tuple(cands) + (TILE_STEM,)

@@ -86,7 +86,9 @@ def main():
         cases = []
         for mode in args.modes.split(','):
             for t, dbg in [(t, g) for t in tiles for g in args.dbg.split(',')]:
-                if mode == 'wgrad' and t not in (0, 1, 3, 5):
+                if mode == 'wgrad' and (t & 0xFF) not in (0, 1, 3, 5, 38):      # 38 | blocks << 8: the nine-tap tile (wgrad_halo_f32.hip)
+                    continue
+                if mode == 'wgrad' and (t & 0xFF) == 38 and (s16 or args.compute != 'f32' or not ops.wghalo_tiles(geo, True)):
                     continue
                 if mode != 'wgrad' and t == 5 or (mode == 'dgrad' and ((t & 15) in (4, 6) or t == 8) and not s16):
                     continue
