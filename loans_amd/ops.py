@@ -158,13 +158,23 @@ def _conv_bytes(geo, x, w, out):
     return n + w.numel() * w.element_size(), out.numel() * out.element_size()
 
 
-def _sum_bytes(a, b):
-    return a[0] + b[0], a[1] + b[1]
+def _fprop_bytes(convs):
+    """_conv_bytes summed over the forward convolutions (geo, x, w, out) of one launch"""
+    rd = wr = 0
+    for c in convs:
+        r, w = _conv_bytes(*c)
+        rd, wr = rd + r, wr + w
+    return rd, wr
+
+
+def _conv_flop(geo):
+    """algorithmic FLOPs: logical input channels (3 for the RGB stem), no padding, no im2col redundancy"""
+    return 2 * geo.rows * geo.Cout * geo.k * geo.k * geo.cin_logical
 
 
 def _count_flops(kind, geo):
     if FLOP_COUNT is not None:
-        FLOP_COUNT[kind] = FLOP_COUNT.get(kind, 0) + 2 * geo.B * geo.Ho * geo.Wo * geo.Cout * geo.k * geo.k * geo.cin_logical
+        FLOP_COUNT[kind] = FLOP_COUNT.get(kind, 0) + _conv_flop(geo)
 
 
 # When bench.py sets this to a dict, every wrapper adds the ALGORITHMIC work of its launch(es) under a kernel class --
@@ -196,8 +206,34 @@ def _acct(cls, flop=0, rd=0, wr=0):
         e[3] += max(flop / ROOFLINE_MFMA[COMPUTE], (rd + wr) / ROOFLINE_HBM)       # this launch at the roofline that binds IT
 
 
-def _conv_flop(geo):
-    return 2 * geo.B * geo.Ho * geo.Wo * geo.Cout * geo.k * geo.k * geo.cin_logical
+def _fprop_account(addend, *convs):
+    """FLOP_COUNT and CLASS_COUNT of one forward launch: convs = (geo, x, w, out) per convolution in it (x = None: the input is
+    shared with the convolution before); byte counts are taken only when the classes are counted"""
+    if FLOP_COUNT is not None:
+        for c in convs:
+            _count_flops('fprop', c[0])
+    if CLASS_COUNT is not None:
+        rd, wr = _fprop_bytes(convs)
+        _acct('conv', sum(_conv_flop(c[0]) for c in convs), rd + _nbytes(addend), wr)
+
+
+def _event_begin():
+    """opens the EVENT_LOG bracket of a forward launch: (start, end) events with the start one recorded on the launch stream,
+    None while nothing is logged"""
+    if EVENT_LOG is None:
+        return None
+    ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev[0].record()
+    return ev
+
+
+def _event_end(ev, stats, launches, *convs):
+    """closes it (callers test `ev is not None` first) and appends what bench.py reads: (tag, algorithmic FLOPs, start, end, kernel
+    launches, convolutions, (bytes read, written)) for the convolutions (geo, x, w, out) of the launch"""
+    ev[1].record()
+    EVENT_LOG.append(('fprop_bn' if stats else 'fprop', sum(_conv_flop(c[0]) for c in convs), ev[0], ev[1], launches, len(convs),
+                      _fprop_bytes(convs)))
+
 
 BN_EPS = 2e-5          # chainer.links.BatchNormalization default (sheep/resnet.py:44)
 BN_DECAY = 0.9
@@ -205,11 +241,24 @@ BN_DECAY = 0.9
 RUNNING_VAR_INCLUDES_EPS = 1
 
 
+def _switches():
+    """the module switches that candidate lists and launch plans depend on (_variant adds TUNE_POLICY and PW, _memo adds PW)"""
+    return (SPLITK, HALO, WGHALO, CLASS_LAUNCH, FINETAIL, STEM_DIRECT, COMPUTE, STORAGE)
+
+
+_variant_keys = {}
+
+
 def _variant(geo, *what):
     """key of geo.tuned under which a wrapper keeps the tile it resolved for one call variant (which flags, which switches):
     later calls skip building the candidate lists, the mode string and the tuning closure -- pure host time, 600 convolution
-    calls per ResNet-50 step.  Lives in geo.tuned, so whatever clears a shape's picks clears these too; never saved to a table."""
-    return '~%r' % ((what, SPLITK, HALO, WGHALO, CLASS_LAUNCH, FINETAIL, STEM_DIRECT, COMPUTE, STORAGE, TUNE_POLICY, PW),)
+    calls per ResNet-50 step.  Lives in geo.tuned, so whatever clears a shape's picks clears these too; never saved to a table.
+    (The strings are kept: formatting one took 1.7 us of every tuned call, the variants of a process are a few dozen.)"""
+    key = (what,) + _switches() + (TUNE_POLICY, PW)
+    s = _variant_keys.get(key)
+    if s is None:
+        s = _variant_keys[key] = '~%r' % (key,)
+    return s
 
 
 _raw_stream = getattr(torch._C, '_cuda_getCurrentRawStream', None) or (lambda idx: torch.cuda.current_stream(idx).cuda_stream)
@@ -231,8 +280,7 @@ def _memo(fn):
     def wrapped(*args, **kw):
         if kw:
             return fn(*args, **kw)
-        key = (tuple(id(a) if isinstance(a, dict) else a for a in args), SPLITK, HALO, WGHALO, CLASS_LAUNCH, FINETAIL,
-               STEM_DIRECT, COMPUTE, STORAGE, PW)
+        key = (tuple(id(a) if isinstance(a, dict) else a for a in args),) + _switches() + (PW,)
         try:
             return cache[key]
         except KeyError:
@@ -337,6 +385,8 @@ class ConvGeometry:
         self.B, self.H, self.W, self.Cin, self.Cout = B, H, W, Cin, Cout
         self.k, self.stride, self.pad = k, stride, pad
         self.Ho, self.Wo = conv_outsize(H, k, stride, pad), conv_outsize(W, k, stride, pad)
+        self.rows = B * self.Ho * self.Wo                   # output pixels: the M of the forward GEMM
+        self.out_shape = (B, self.Ho, self.Wo, Cout)
         self.dense = dense
         self.base_flags = 0
         self.cin_logical = 3 if Cin == 4 else Cin
@@ -348,6 +398,7 @@ class ConvGeometry:
             return
         self.in_numel = B * H * W * Cin
         self.w_numel = Cout * k * k * Cin
+        self.kchunks = (k * k * Cin + 31) // 32             # 32-deep K steps of the fp32 forward GEMM
         d = IgemmDesc()
         d.B, d.inH, d.inW, d.Cin = B, H, W, Cin
         d.outH, d.outW, d.Cout = self.Ho, self.Wo, Cout
@@ -392,7 +443,6 @@ class ConvGeometry:
                 self.dgrad.append((g, tapsel, off))
                 off += Cin * len(taps) * Cout
         self.dgrad_weight_floats = off
-        self.flops_fwd = 2 * B * self.Ho * self.Wo * Cout * k * k * Cin
 
     def _init_dense(self):
         """LOANS_F_DENSE (include/loans_hip.h): the RGB stem reads packed 3-channel rows of a zero-padded frame, so
@@ -406,6 +456,7 @@ class ConvGeometry:
         self.Wp += self.Wp & 1                  # even: every K row starts on an 8-byte boundary
         self.in_numel = B * self.Hp * self.Wp * 3
         self.w_numel = self.Cout * k * self.kwp * 3
+        self.kchunks = (k * self.kwp * 3 + 31) // 32
         self.base_flags = F_DENSE
         d = IgemmDesc()
         d.B, d.inH, d.inW, d.Cin = B, self.Hp, self.Wp * 3, self.kwp * 3
@@ -419,7 +470,6 @@ class ConvGeometry:
             d.dy[t], d.dx[t] = t, 0
         self.fwd = d
         self.dgrad, self.dgrad_has_empty_class, self.dgrad_weight_floats = [], False, 0      # frames get no gradient
-        self.flops_fwd = 2 * B * self.Ho * self.Wo * self.Cout * k * k * 3
         self._wmask = None
 
     def wmask(self, device):
@@ -501,29 +551,16 @@ def conv_fprop_affine(x, st, w, geo, stats=None):
     bit bn_apply(x, st, relu=True) followed by conv_fprop(..., tile=TILE_PW)"""
     assert affine_in_ok(geo, x) and x.numel() == geo.in_numel
     lib = _lib.load()
-    out = _empty((geo.B, geo.Ho, geo.Wo, geo.Cout), device=x.device, dtype=BF16)
+    out = _empty(geo.out_shape, device=x.device, dtype=BF16)
     w16 = w if _is16(w) else _bf16_shadow(w)
     if w16 is None:
         w16 = cast_bf16(w)
     flags = F_AFFINE_IN | (F_STATS if stats is not None else 0)
-    _count_flops('fprop', geo)
-    if CLASS_COUNT is not None:
-        rd, wr = _conv_bytes(geo, x, w16, out)
-        _acct('conv', _conv_flop(geo), rd, wr)
-    log = EVENT_LOG
-    if log is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    packs = PW_PACK_CALLS
-    wp = _pw_packed(lib, w, w16, geo, _stream())
-    packs = PW_PACK_CALLS - packs
-    check(lib.loans_igemm_bf16s(_ptr(x), _ptr(wp), _ptr(out), _ptr(st.affine()), _ptr(stats), 0, 0,
-                                C.byref(_with_flags(geo.fwd, flags, TILE_PW)), _stream()), 'loans_igemm_bf16s[fprop, bn on load]')
-    if log is not None:
-        ev1.record()
-        log.append(('fprop_bn' if stats is not None else 'fprop',
-                    2 * geo.B * geo.Ho * geo.Wo * geo.Cout * geo.k * geo.k * geo.cin_logical, ev0, ev1, 1 + packs, 1,
-                    _conv_bytes(geo, x, w16, out)))
+    _fprop_account(None, (geo, x, w16, out))
+    ev = _event_begin()
+    launches = _fprop16_launch(lib, x, w, w16, out, geo, flags, TILE_PW, st.affine(), stats, None)    # (the table travels in the bias slot)
+    if ev is not None:
+        _event_end(ev, stats is not None, launches, (geo, x, w16, out))
     return out
 
 
@@ -707,6 +744,18 @@ def _tuned_tile(geo, mode, run, candidates, cold=False):
     return tile
 
 
+def _resolved_tile(geo, tile, what, plan):
+    """the tile of one wrapper call: the caller's, else the one kept in geo.tuned under _variant(geo, *what), else -- the first
+    call of a variant -- plan() -> (mode, run, candidates, cold) goes to _tuned_tile and its pick is kept.  A tuned call builds
+    no candidate list, mode string or tuning closure: that is what the variant key is for."""
+    if tile == 0:
+        vkey = _variant(geo, *what)
+        tile = geo.tuned.get(vkey, 0)
+        if tile == 0:
+            tile = geo.tuned[vkey] = _tuned_tile(geo, *plan())
+    return tile
+
+
 def reduce_channels_ok(C_):
     """channel counts the row-reduction kernels (and loans_igemm_finalize_f32) tile: C/4 divides 256 or is a multiple of it"""
     c4 = C_ // 4
@@ -841,6 +890,15 @@ def _igemm_launches(M, Cout, tile, device, nchunks=0):
     return 2 if 0 < rows_big < M else 1
 
 
+def _fprop_launch(lib, x, w, out, geo, flags, tile, bias, stats, addend):
+    """one forward convolution of fp32 tensors: split-K (tile id >> 8 = slices) with its finalize pass, or the plain launch"""
+    if tile >> 8:
+        _igemm_splitk(lib, x, w, out, [(geo.fwd, w)], flags, tile, bias, stats, None, addend, geo.rows, geo.Cout, _stream())
+    else:
+        check(_igemm_fn(lib)(_ptr(x), _ptr(w), _ptr(out), _ptr(bias), _ptr(stats), 0, _ptr(addend),
+                             C.byref(_with_flags(geo.fwd, flags, tile)), _stream()), 'loans_igemm[fprop]')
+
+
 def conv_fprop(x, w, geo, out=None, bias=None, stats=None, relu_in=False, addend=None, tile=0, out_bf16=False):
     """out[B,Ho,Wo,Cout] = conv(x[B,H,W,Cin], w[Cout,k,k,Cin]) (+bias) (+addend); optional BN statistics.
     out_bf16 (bf16 compute arm, fp32 input): write a bf16 tensor -- the stem conv of the bf16-storage arm."""
@@ -849,65 +907,37 @@ def conv_fprop(x, w, geo, out=None, bias=None, stats=None, relu_in=False, addend
         return _conv_fprop16(lib, x, w, geo, out, bias, stats, relu_in, addend, tile)
     if out_bf16:
         assert COMPUTE == 'bf16' and addend is None and out is None
-        out = _empty((geo.B, geo.Ho, geo.Wo, geo.Cout), device=x.device, dtype=BF16)
+    odtype = BF16 if out_bf16 else torch.float32
     if out is None:
-        out = _empty((geo.B, geo.Ho, geo.Wo, geo.Cout), device=x.device, dtype=torch.float32)
+        out = _empty(geo.out_shape, device=x.device, dtype=odtype)
     flags = (F_RELU_IN if relu_in else 0) | (F_BIAS if bias is not None else 0) | (F_OUT_BF16 if out_bf16 else 0) | \
             (F_STATS if stats is not None else 0) | (F_ADDEND if addend is not None else 0) | geo.base_flags
     assert x.numel() == geo.in_numel and w.numel() == geo.w_numel
-    if tile == 0:
-        vkey = _variant(geo, 'fprop', stats is not None, out_bf16, addend is None, relu_in, bias is not None)
-        tile = geo.tuned.get(vkey, 0)
-    if tile == 0:
+
+    def plan():
         tflags = flags & (F_RELU_IN | F_STATS | F_DENSE | F_OUT_BF16)
         sstats = stats_buffer(geo.Cout, x.device) if stats is not None else None
 
         def run(t):
-            scratch = _empty((geo.B, geo.Ho, geo.Wo, geo.Cout), device=x.device, dtype=BF16 if out_bf16 else torch.float32)
-            if t >> 8:
-                _igemm_splitk(lib, x, w, scratch, [(geo.fwd, w)], tflags, t, None, sstats, None, None,
-                              geo.B * geo.Ho * geo.Wo, geo.Cout, _stream())
-                return
-            check(_igemm_fn(lib)(_ptr(x), _ptr(w), _ptr(scratch), 0, _ptr(sstats), 0, 0,
-                                      C.byref(_with_flags(geo.fwd, tflags, t)), _stream()), 'loans_igemm_f32[tune]')
-        M_ = geo.B * geo.Ho * geo.Wo
-        nch = (geo.w_numel // geo.Cout + 31) // 32
-        sk = () if (out_bf16 or not reduce_channels_ok(geo.Cout)) else _splitk_candidates(M_, geo.Cout, nch)
+            _fprop_launch(lib, x, w, _empty(geo.out_shape, device=x.device, dtype=odtype), geo, tflags, t, None, sstats, None)
+        sk = () if (out_bf16 or not reduce_channels_ok(geo.Cout)) else _splitk_candidates(geo.rows, geo.Cout, geo.kchunks)
         # LOANS_TILE_FINETAIL slices its last tiles along K (atomics): offered under the same switch as split-K
         ft = ()
         if SPLITK and FINETAIL and COMPUTE == 'f32' and not out_bf16 and addend is None and reduce_channels_ok(geo.Cout) \
-                and _finetail_plan(M_, geo.Cout, nch, x.device)[1] > 1:
+                and _finetail_plan(geo.rows, geo.Cout, geo.kchunks, x.device)[1] > 1:
             ft = (TILE_FINETAIL, TILE_FINETAIL | 16)
         stem = ()
         if STEM_DIRECT and not relu_in and addend is None:
             if (stem_tile_rows(geo) if not out_bf16 else stem16_tile_rows(geo)) and (COMPUTE == 'f32') != out_bf16:
                 stem = (TILE_STEM,)
-        tile = _tuned_tile(geo, COMPUTE + 'fprop' + ('_stats' if stats is not None else '') + ('_sk' if sk else '') +
-                           ('_ft' if ft else '') + ('_st' if stem else ''), run,
-                           _FPROP_TILES + sk + ft + stem)   # fp32 scratch output: the tile choice carries over
-        geo.tuned[vkey] = tile
-    d = _with_flags(geo.fwd, flags, tile)
-    _count_flops('fprop', geo)
-    if CLASS_COUNT is not None:
-        rd, wr = _conv_bytes(geo, x, w, out)
-        _acct('conv', _conv_flop(geo), rd + _nbytes(addend), wr)
-    log = EVENT_LOG
-    if log is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    if tile >> 8:
-        _igemm_splitk(lib, x, w, out, [(geo.fwd, w)], flags, tile, bias, stats, None, addend,
-                      geo.B * geo.Ho * geo.Wo, geo.Cout, _stream())
-    else:
-        check(_igemm_fn(lib)(_ptr(x), _ptr(w), _ptr(out), _ptr(bias), _ptr(stats), 0, _ptr(addend),
-                             C.byref(d), _stream()), 'loans_igemm[fprop]')
-    if log is not None:
-        ev1.record()
-        # algorithmic FLOPs: logical input channels (3 for the RGB stem), no padding, no im2col redundancy
-        log.append(('fprop_bn' if stats is not None else 'fprop',
-                    2 * geo.B * geo.Ho * geo.Wo * geo.Cout * geo.k * geo.k * geo.cin_logical, ev0, ev1,
-                    _igemm_launches(geo.B * geo.Ho * geo.Wo, geo.Cout, tile, x.device,
-                                    (geo.w_numel // geo.Cout + 31) // 32), 1, _conv_bytes(geo, x, w, out)))
+        return (COMPUTE + 'fprop' + ('_stats' if stats is not None else '') + ('_sk' if sk else '') + ('_ft' if ft else '') +
+                ('_st' if stem else ''), run, _FPROP_TILES + sk + ft + stem, False)   # fp32 scratch output: the tile choice carries over
+    tile = _resolved_tile(geo, tile, ('fprop', stats is not None, out_bf16, addend is None, relu_in, bias is not None), plan)
+    _fprop_account(addend, (geo, x, w, out))
+    ev = _event_begin()
+    _fprop_launch(lib, x, w, out, geo, flags, tile, bias, stats, addend)
+    if ev is not None:
+        _event_end(ev, stats is not None, _igemm_launches(geo.rows, geo.Cout, tile, x.device, geo.kchunks), (geo, x, w, out))
     return out
 
 
@@ -926,7 +956,7 @@ def fprop_pair_ok(x, geo_a, geo_b):
         # strided units only: at stride 1 each convolution runs faster alone on the halo-staged tiles (res2: 2 x 0.205 ms
         # against 0.455 ms for the pair at 128 x 3 x 512^2)
         return same and PAIR16 and geo_a.stride > 1 and geo_a.Cout == geo_b.Cout and geo_a.Cout % 32 == 0 and geo_a.Cin % 8 == 0 and \
-            2 * geo_a.B * geo_a.Ho * geo_a.Wo * geo_a.Cout * 2 < 0xFFFFFFF0
+            2 * geo_a.rows * geo_a.Cout * 2 < 0xFFFFFFF0
     return same and COMPUTE == 'f32'
 
 
@@ -940,13 +970,11 @@ def conv_fprop_pair(x, w_a, w_b, geo_a, geo_b, stats_a=None, stats_b=None, tile=
     assert fprop_pair_ok(x, geo_a, geo_b) and (stats_a is None) == (stats_b is None)
     if _is16(x):
         return _conv_fprop_pair16(lib, x, w_a, w_b, geo_a, geo_b, stats_a, stats_b, tile)
-    mk = lambda g: _empty((g.B, g.Ho, g.Wo, g.Cout), device=x.device, dtype=torch.float32)      # noqa: E731
+    mk = lambda g: _empty(g.out_shape, device=x.device, dtype=torch.float32)      # noqa: E731
     out_a, out_b = mk(geo_a), mk(geo_b)
     flags = F_STATS if stats_a is not None else 0
-    if tile == 0:
-        vkey = _variant(geo_a, 'pair', geo_b.Cout, flags)
-        tile = geo_a.tuned.get(vkey, 0)
-    if tile == 0:
+
+    def plan():
         sa = stats_buffer(geo_a.Cout, x.device) if flags else None
         sb = stats_buffer(geo_b.Cout, x.device) if flags else None
         ta, tb = mk(geo_a), mk(geo_b)
@@ -954,24 +982,15 @@ def conv_fprop_pair(x, w_a, w_b, geo_a, geo_b, stats_a=None, stats_b=None, tile=
         def run(t):
             check(lib.loans_igemm_pair_f32(_ptr(x), _ptr(w_a), _ptr(ta), _ptr(sa), _ptr(w_b), _ptr(tb), _ptr(sb), geo_b.Cout,
                                            C.byref(_with_flags(geo_a.fwd, flags, t)), _stream()), 'loans_igemm_pair_f32[tune]')
-        tile = _tuned_tile(geo_a, 'f32fprop_pair%d%s' % (geo_b.Cout, '_stats' if flags else ''), run, _PAIR_TILES)
-        geo_a.tuned[vkey] = tile
-    _count_flops('fprop', geo_a)
-    _count_flops('fprop', geo_b)
-    if CLASS_COUNT is not None:
-        rd, wr = _sum_bytes(_conv_bytes(geo_a, x, w_a, out_a), _conv_bytes(geo_b, None, w_b, out_b))
-        _acct('conv', _conv_flop(geo_a) + _conv_flop(geo_b), rd, wr)
-    log = EVENT_LOG
-    if log is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+        return 'f32fprop_pair%d%s' % (geo_b.Cout, '_stats' if flags else ''), run, _PAIR_TILES, False
+    tile = _resolved_tile(geo_a, tile, ('pair', geo_b.Cout, flags), plan)
+    convs = (geo_a, x, w_a, out_a), (geo_b, None, w_b, out_b)
+    _fprop_account(None, *convs)
+    ev = _event_begin()
     check(lib.loans_igemm_pair_f32(_ptr(x), _ptr(w_a), _ptr(out_a), _ptr(stats_a), _ptr(w_b), _ptr(out_b), _ptr(stats_b),
                                    geo_b.Cout, C.byref(_with_flags(geo_a.fwd, flags, tile)), _stream()), 'loans_igemm_pair_f32')
-    if log is not None:
-        ev1.record()
-        fl = 2 * geo_a.B * geo_a.Ho * geo_a.Wo * (geo_a.Cout + geo_b.Cout) * geo_a.k * geo_a.k * geo_a.cin_logical
-        log.append(('fprop_bn' if flags else 'fprop', fl, ev0, ev1, 1, 2,         # one launch, two convolutions
-                    _sum_bytes(_conv_bytes(geo_a, x, w_a, out_a), _conv_bytes(geo_b, None, w_b, out_b))))
+    if ev is not None:
+        _event_end(ev, flags, 1, *convs)         # one launch, two convolutions
     return out_a, out_b
 
 
@@ -982,15 +1001,14 @@ def _conv_fprop_pair16(lib, x, w_a, w_b, geo_a, geo_b, stats_a, stats_b, tile):
     """the bf16-storage pair: weights cast into the two halves of one [2][Cout][K] matrix, outputs two views of one allocation"""
     n = geo_a.w_numel
     w_ab = _empty(2 * n, device=x.device, dtype=BF16)
-    for i, w in enumerate((w_a, w_b)):
+    halves = w_ab[:n], w_ab[n:]
+    for w, w16 in zip((w_a, w_b), halves):
         assert w.numel() == n and not _is16(w)
-        check(lib.loans_cast_bf16(_ptr(w), _ptr(w_ab[i * n:]), n, _stream()), 'loans_cast_bf16')
+        check(lib.loans_cast_bf16(_ptr(w), _ptr(w16), n, _stream()), 'loans_cast_bf16')
     flags = F_STATS if stats_a is not None else 0
-    mk = lambda: _empty((2, geo_a.B, geo_a.Ho, geo_a.Wo, geo_a.Cout), device=x.device, dtype=BF16)      # noqa: E731
-    if tile == 0:
-        vkey = _variant(geo_a, 'pair16', flags)
-        tile = geo_a.tuned.get(vkey, 0)
-    if tile == 0:
+    mk = lambda: _empty((2,) + geo_a.out_shape, device=x.device, dtype=BF16)      # noqa: E731
+
+    def plan():
         sa = stats_buffer(geo_a.Cout, x.device) if flags else None
         sb = stats_buffer(geo_a.Cout, x.device) if flags else None
         scratch = mk()
@@ -998,33 +1016,39 @@ def _conv_fprop_pair16(lib, x, w_a, w_b, geo_a, geo_b, stats_a, stats_b, tile):
         def run(t):
             check(lib.loans_igemm_pair_bf16s(_ptr(x), _ptr(w_ab), _ptr(scratch), _ptr(sa), _ptr(sb),
                                              C.byref(_with_flags(geo_a.fwd, flags, t)), _stream()), 'loans_igemm_pair_bf16s[tune]')
-        tile = _tuned_tile(geo_a, 'bf16s_fprop_pair' + ('_stats' if flags else ''), run,
-                           _PAIR16_TILES + _wide16_tiles(2 * geo_a.Cout, geo_a.B * geo_a.Ho * geo_a.Wo))
-        geo_a.tuned[vkey] = tile
+        return ('bf16s_fprop_pair' + ('_stats' if flags else ''), run,
+                _PAIR16_TILES + _wide16_tiles(2 * geo_a.Cout, geo_a.rows), False)
+    tile = _resolved_tile(geo_a, tile, ('pair16', flags), plan)
     out = mk()
-    _count_flops('fprop', geo_a)
-    _count_flops('fprop', geo_b)
-    if CLASS_COUNT is not None:
-        rd, wr = _sum_bytes(_conv_bytes(geo_a, x, w_ab[:n], out[0]), _conv_bytes(geo_b, None, w_ab[n:], out[1]))
-        _acct('conv', _conv_flop(geo_a) + _conv_flop(geo_b), rd, wr)
-    log = EVENT_LOG
-    if log is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    out_a, out_b = out[0], out[1]
+    convs = (geo_a, x, halves[0], out_a), (geo_b, None, halves[1], out_b)
+    _fprop_account(None, *convs)
+    ev = _event_begin()
     check(lib.loans_igemm_pair_bf16s(_ptr(x), _ptr(w_ab), _ptr(out), _ptr(stats_a), _ptr(stats_b),
                                      C.byref(_with_flags(geo_a.fwd, flags, tile)), _stream()), 'loans_igemm_pair_bf16s')
-    if log is not None:
-        ev1.record()
-        fl = 2 * geo_a.B * geo_a.Ho * geo_a.Wo * 2 * geo_a.Cout * geo_a.k * geo_a.k * geo_a.cin_logical
-        log.append(('fprop_bn' if flags else 'fprop', fl, ev0, ev1, 1, 2,         # one launch, two convolutions
-                    _sum_bytes(_conv_bytes(geo_a, x, w_ab[:n], out[0]), _conv_bytes(geo_b, None, w_ab[n:], out[1]))))
-    return out[0], out[1]
+    if ev is not None:
+        _event_end(ev, flags, 1, *convs)         # one launch, two convolutions
+    return out_a, out_b
+
+
+def _fprop16_launch(lib, x, w, w16, out, geo, flags, tile, bias, stats, addend):
+    """one forward convolution of bf16 tensors; returns its kernel launches: split-K is the partial launch and the finalize pass (the
+    memset is torch's), LOANS_TILE_PW outside a prepared step the packing launch and the convolution"""
+    if tile >> 8:
+        _igemm16_splitk(lib, x, [(geo.fwd, w16)], out, flags, tile, bias, stats, None, addend, geo.rows, geo.Cout, _stream())
+        return 2
+    packs = PW_PACK_CALLS
+    if tile == TILE_PW:
+        w16 = _pw_packed(lib, w, w16, geo, _stream())
+    check(lib.loans_igemm_bf16s(_ptr(x), _ptr(w16), _ptr(out), _ptr(bias), _ptr(stats), 0, _ptr(addend),
+                                C.byref(_with_flags(geo.fwd, flags, tile)), _stream()), 'loans_igemm_bf16s[fprop]')
+    return 1 + PW_PACK_CALLS - packs
 
 
 def _conv_fprop16(lib, x, w, geo, out, bias, stats, relu_in, addend, tile):
     """bf16-storage forward conv: x / out / addend bf16, w fp32 master weights (cast per call) or already bf16."""
     if out is None:
-        out = _empty((geo.B, geo.Ho, geo.Wo, geo.Cout), device=x.device, dtype=BF16)
+        out = _empty(geo.out_shape, device=x.device, dtype=BF16)
     assert out.dtype == BF16 and (addend is None or addend.dtype == BF16)
     assert x.numel() == geo.in_numel and w.numel() == geo.w_numel
     w16 = w if _is16(w) else _bf16_shadow(w)            # inside a step: the arena's bf16 shadow, cast whole at its start
@@ -1032,130 +1056,31 @@ def _conv_fprop16(lib, x, w, geo, out, bias, stats, relu_in, addend, tile):
         w16 = cast_bf16(w)
     flags = (F_RELU_IN if relu_in else 0) | (F_BIAS if bias is not None else 0) | (F_STATS if stats is not None else 0) | \
             (F_ADDEND if addend is not None else 0) | geo.base_flags
-    if tile == 0:
-        vkey = _variant(geo, 'fprop16', stats is not None, relu_in, addend is None, bias is not None)
-        tile = geo.tuned.get(vkey, 0)
-    if tile == 0:
+
+    def plan():
         tflags = flags & (F_STATS | F_RELU_IN | F_DENSE)
         sstats = stats_buffer(geo.Cout, x.device) if stats is not None else None
 
         def run(t):
-            scratch = _empty((geo.B, geo.Ho, geo.Wo, geo.Cout), device=x.device, dtype=BF16)
-            if t >> 8:
-                _igemm16_splitk(lib, x, [(geo.fwd, w16)], scratch, tflags, t, None, sstats, None, None,
-                                geo.B * geo.Ho * geo.Wo, geo.Cout, _stream())
-                return
-            wt = _pw_packed(lib, w, w16, geo, _stream()) if t == TILE_PW else w16
-            check(lib.loans_igemm_bf16s(_ptr(x), _ptr(wt), _ptr(scratch), 0, _ptr(sstats), 0, 0,
-                                        C.byref(_with_flags(geo.fwd, tflags, t)), _stream()), 'loans_igemm_bf16s[tune]')
+            _fprop16_launch(lib, x, w, w16, _empty(geo.out_shape, device=x.device, dtype=BF16), geo, tflags, t, None, sstats, None)
         # where LOANS_TILE_PW is on offer the candidates are timed COLD (a 512 MB fill before every launch): these layers write four
         # times what they read, and a back-to-back repetition flatters the tiles that re-read a cached input -- in the step the
         # 256 x 256 tile takes 0.120 ms on res3's expansion and this one 0.096, timed warm it is 0.107 against 0.110
         pw = _pw_tiles(geo, not relu_in and addend is None and bias is None)
-        halo = _halo_tiles(geo, geo.Cin, geo.Cout, (geo.Ho, geo.Wo), relu_in) + _wide16_tiles(geo.Cout, geo.B * geo.Ho * geo.Wo)
-        sk = () if geo.dense else _splitk16_candidates(geo.B * geo.Ho * geo.Wo, geo.Cout, geo.w_numel // geo.Cout)
+        halo = _halo_tiles(geo, geo.Cin, geo.Cout, (geo.Ho, geo.Wo), relu_in) + _wide16_tiles(geo.Cout, geo.rows)
+        sk = () if geo.dense else _splitk16_candidates(geo.rows, geo.Cout, geo.w_numel // geo.Cout)
         stem = (TILE_STEM,) if (STEM_DIRECT and geo.dense and not relu_in and addend is None and stem16_tile_rows(geo)) else ()
         # (relu_in is part of the key: the weight-stationary tiles do not take it, so a tile tuned without it may not apply)
-        tile = _tuned_tile(geo, 'bf16s_fprop' + ('_stats' if stats is not None else '') + ('_h' if halo else '') +
-                           ('_sk' if sk else '') + ('_st' if stem else '') + ('_relu' if relu_in else '') + ('_pw' if pw else ''), run,
-                           _IGEMM16_TILES + halo + sk + stem + pw, cold=bool(pw))
-        geo.tuned[vkey] = tile
-    d = _with_flags(geo.fwd, flags, tile)
-    _count_flops('fprop', geo)
-    if CLASS_COUNT is not None:
-        rd, wr = _conv_bytes(geo, x, w16, out)
-        _acct('conv', _conv_flop(geo), rd + _nbytes(addend), wr)
-    log = EVENT_LOG
-    if log is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    if tile >> 8:
-        _igemm16_splitk(lib, x, [(geo.fwd, w16)], out, flags, tile, bias, stats, None, addend,
-                        geo.B * geo.Ho * geo.Wo, geo.Cout, _stream())
-    else:
-        if tile == TILE_PW:
-            packs = PW_PACK_CALLS
-            w16 = _pw_packed(lib, w, w16, geo, _stream())
-            packs = PW_PACK_CALLS - packs           # 1 outside a prepared step (the packing launch), else 0
-        check(lib.loans_igemm_bf16s(_ptr(x), _ptr(w16), _ptr(out), _ptr(bias), _ptr(stats), 0, _ptr(addend),
-                                    C.byref(d), _stream()), 'loans_igemm_bf16s[fprop]')
-    if log is not None:
-        ev1.record()
-        log.append(('fprop_bn' if stats is not None else 'fprop',
-                    2 * geo.B * geo.Ho * geo.Wo * geo.Cout * geo.k * geo.k * geo.cin_logical, ev0, ev1,
-                    2 if tile >> 8 else (1 + packs if tile == TILE_PW else 1), 1,
-                    _conv_bytes(geo, x, w16, out)))          # split-K: the partial launch and the finalize pass (the memset is torch's);
-        #                                                      LOANS_TILE_PW outside a prepared step: the packing launch and the convolution
+        return ('bf16s_fprop' + ('_stats' if stats is not None else '') + ('_h' if halo else '') + ('_sk' if sk else '') +
+                ('_st' if stem else '') + ('_relu' if relu_in else '') + ('_pw' if pw else ''), run,
+                _IGEMM16_TILES + halo + sk + stem + pw, bool(pw))
+    tile = _resolved_tile(geo, tile, ('fprop16', stats is not None, relu_in, addend is None, bias is not None), plan)
+    _fprop_account(addend, (geo, x, w16, out))
+    ev = _event_begin()
+    launches = _fprop16_launch(lib, x, w, w16, out, geo, flags, tile, bias, stats, addend)
+    if ev is not None:
+        _event_end(ev, stats is not None, launches, (geo, x, w16, out))
     return out
-
-
-def _conv_dgrad16(lib, gy, w, geo, out, mask_ref, addend, addend_mask_ref, tile, bn_sums=None):
-    if out is None:
-        out = _empty((geo.B, geo.H, geo.W, geo.Cin), device=gy.device, dtype=BF16)
-    assert out.dtype == BF16 and not _is16(w)
-    if geo.dgrad_has_empty_class:
-        assert mask_ref is None and addend_mask_ref is None
-        if addend is None:
-            out.zero_()
-        elif addend.data_ptr() != out.data_ptr():
-            out.copy_(addend)
-        if addend is not None:
-            addend = out
-    flags = (F_MASK if mask_ref is not None else 0) | (F_ADDEND if addend is not None else 0) | \
-            (F_ADDEND_MASK if addend_mask_ref is not None else 0)
-    ref = mask_ref if mask_ref is not None else addend_mask_ref
-    assert not (mask_ref is not None and addend_mask_ref is not None)
-    coef = sums = None
-    if bn_sums is not None:             # LOANS_F_BNSUMS: the epilogue takes the two sums of the BN below (see conv_dgrad)
-        assert flags == 0 and len(geo.dgrad) == 1 and not geo.dgrad_has_empty_class
-        y, bst = bn_sums
-        assert _is16(y) and y.is_contiguous() and y.numel() == out.numel()
-        flags, ref, coef, sums = F_BNSUMS, y, bst.mean, stats_buffer(geo.Cin, gy.device)
-    st = _stream()
-    wp = _prepacked_dgrad_weights(w, geo, True)          # inside a step: made at its start, all layers in one launch
-    if wp is None:
-        wp = _empty(geo.dgrad_weight_floats, device=gy.device, dtype=BF16)
-        for d, tapsel, off in geo.dgrad:
-            check(lib.loans_repack_dgrad_bf16(_ptr(w), _ptr(wp[off:]), geo.Cout, geo.Cin, geo.k * geo.k, tapsel,
-                                              d.ntaps, st), 'loans_repack_dgrad_bf16')
-    dl = [(d, wp[off:]) for d, _, off in geo.dgrad]
-    rows_in = geo.B * geo.H * geo.W
-    # a split-K data gradient finishes in ONE pass over the whole tensor: the tap-less classes of a strided 1x1 (which only
-    # take the addend, handled above by a copy) and an addend aliasing `out` do not go through it
-    sk_ok = not geo.dgrad_has_empty_class and not (addend is not None and addend.data_ptr() == out.data_ptr())
-    if tile == 0:
-        vkey = _variant(geo, 'dgrad16', sk_ok, bn_sums is not None)
-        tile = geo.tuned.get(vkey, 0)
-    if tile == 0:
-        def run(t):
-            scratch = _empty((geo.B, geo.H, geo.W, geo.Cin), device=gy.device, dtype=BF16)
-            if t >> 8:
-                _igemm16_splitk(lib, gy, dl, scratch, 0, t, None, None, None, None, rows_in, geo.Cin, st)
-                return
-            for d, _, off in geo.dgrad:
-                check(lib.loans_igemm_bf16s(_ptr(gy), _ptr(wp[off:]), _ptr(scratch), 0, 0, 0, 0,
-                                            C.byref(_with_flags(d, 0, t)), st), 'loans_igemm_bf16s[tune]')
-        halo = _halo_tiles(geo, geo.Cout, geo.Cin, (geo.H, geo.W)) + _wide16_tiles(geo.Cin, geo.B * min(d.gridH * d.gridW for d, _, _ in geo.dgrad))
-        sk = ()
-        if sk_ok and bn_sums is None:
-            cls_rows = geo.B * min(d.gridH * d.gridW for d, _, _ in geo.dgrad)
-            sk = _splitk16_candidates(cls_rows, geo.Cin, min(d.ntaps for d, _, _ in geo.dgrad) * geo.Cout)
-        if bn_sums is not None:         # ws8_kernel's epilogue does not take the sums
-            halo = tuple(t for t in halo if t != TILE_WS64)
-        tile = _tuned_tile(geo, 'bf16s_dgrad' + ('_h' if halo else '') + ('_sk' if sk else '') + ('_bn' if bn_sums is not None else ''),
-                           run, _IGEMM16_TILES + halo + sk)
-        geo.tuned[vkey] = tile
-    if tile >> 8:
-        assert sk_ok and bn_sums is None
-        _igemm16_splitk(lib, gy, dl, out, flags, tile, None, None, ref, addend, rows_in, geo.Cin, st)
-        return out
-    for d, tapsel, off in geo.dgrad:
-        _with_flags(d, flags, tile)
-        check(lib.loans_igemm_bf16s(_ptr(gy), _ptr(wp[off:]), _ptr(out), _ptr(coef), _ptr(sums), _ptr(ref), _ptr(addend),
-                                    C.byref(d), st), 'loans_igemm_bf16s[dgrad]')
-    return out if bn_sums is None else (out, sums)
-
-
 
 
 def bn_sums_ok(geo, y):
@@ -1165,24 +1090,43 @@ def bn_sums_ok(geo, y):
         geo.Cin % 8 == 0 and y.is_contiguous()
 
 
+def _dgrad_launch(lib, s16, gy, wp, out, geo, flags, tile, coef, sums, ref, addend, st):
+    """one data gradient (bf16 storage: s16) on `tile`: every stride-parity class in ONE launch (TILE_CLASSES), split-K (tile id >> 8
+    = slices: all classes into one workspace, one finalize pass), or a launch per class"""
+    if tile & TILE_CLASSES:
+        _igemm_classes(lib, gy, wp, out, geo, flags, tile & 0xFF, ref, addend, st)
+    elif tile >> 8:
+        dl = [(d, wp[off:]) for d, _, off in geo.dgrad]
+        if s16:
+            _igemm16_splitk(lib, gy, dl, out, flags, tile, None, None, ref, addend, geo.B * geo.H * geo.W, geo.Cin, st)
+        else:
+            _igemm_splitk(lib, gy, None, out, dl, flags, tile, None, None, ref, addend, geo.B * geo.H * geo.W, geo.Cin, st)
+    else:
+        fn = lib.loans_igemm_bf16s if s16 else _igemm_fn(lib)
+        for d, _, off in geo.dgrad:
+            check(fn(_ptr(gy), _ptr(wp[off:]), _ptr(out), _ptr(coef), _ptr(sums), _ptr(ref), _ptr(addend),
+                     C.byref(_with_flags(d, flags, tile)), st), 'loans_igemm_bf16s[dgrad]' if s16 else 'loans_igemm[dgrad]')
+
+
 def conv_dgrad(gy, w, geo, out=None, mask_ref=None, addend=None, addend_mask_ref=None, tile=0, bn_sums=None):
     """gx[B,H,W,Cin] = conv_transpose(gy, w); epilogue: (* (mask_ref>0)), (+ addend [masked by addend_mask_ref>0]).
-    Re-packs w per stride-parity class first (weights change every step).
+    Re-packs w per stride-parity class first (weights change every step).  A bf16 gy makes it the bf16-storage gradient (gx,
+    the references and the addend bf16, w the fp32 masters) -- except w.r.t. a 4-channel input.
     bn_sums=(y, BNState): gx is the gradient that reaches a BatchNormalization (input y, batch coefficients in the BNState)
     followed by its own ReLU; the epilogue also takes that BN's two backward sums from the tile (LOANS_F_BNSUMS) and the call
     returns (gx, sums) with sums = fp64 [replicas][2][C] for bn_backward_from_sums -- the reduction pass over gx disappears."""
     lib = _lib.load()
-    assert gy.numel() == geo.B * geo.Ho * geo.Wo * geo.Cout
+    assert gy.numel() == geo.rows * geo.Cout
+    s16 = _is16(gy) and geo.Cin != 4
+    dtype = BF16 if s16 else torch.float32
     _count_flops('dgrad', geo)
     if CLASS_COUNT is not None:
-        es = 2 if (_is16(gy) and geo.Cin != 4) else 4
         _acct('crop' if geo.Cin == 4 else 'conv', _conv_flop(geo),
               _nbytes(gy, w, mask_ref, addend, addend_mask_ref, bn_sums[0] if bn_sums is not None else None),
-              geo.B * geo.H * geo.W * geo.Cin * es)
-    if _is16(gy) and geo.Cin != 4:
-        return _conv_dgrad16(lib, gy, w, geo, out, mask_ref, addend, addend_mask_ref, tile, bn_sums)
+              geo.B * geo.H * geo.W * geo.Cin * (2 if s16 else 4))
     if out is None:
-        out = _empty((geo.B, geo.H, geo.W, geo.Cin), device=gy.device, dtype=torch.float32)
+        out = _empty((geo.B, geo.H, geo.W, geo.Cin), device=gy.device, dtype=dtype)
+    assert not s16 or (out.dtype == BF16 and not _is16(w))
     if geo.dgrad_has_empty_class:
         # pixels of a tap-less stride class receive only the addend (or zero)
         assert mask_ref is None and addend_mask_ref is None
@@ -1192,74 +1136,69 @@ def conv_dgrad(gy, w, geo, out=None, mask_ref=None, addend=None, addend_mask_ref
             out.copy_(addend)
         if addend is not None:
             addend = out
+    flags = (F_MASK if mask_ref is not None else 0) | (F_ADDEND if addend is not None else 0) | \
+            (F_ADDEND_MASK if addend_mask_ref is not None else 0)
     if geo.Cin == 4 and addend_mask_ref is None and geo.Cout % 32 == 0:
         # gradient w.r.t. a 4-channel (RGB) input: dedicated VALU kernel, forward weights, no re-pack; the crops and
         # their gradient stay fp32 in every arm, the incoming gradient may be a bf16 tensor
-        fl = (F_MASK if mask_ref is not None else 0) | (F_ADDEND if addend is not None else 0)
         fn = lib.loans_dgrad_c4_bf16_f32 if _is16(gy) else lib.loans_dgrad_c4_f32
-        if out is None:
-            out = _empty((geo.B, geo.H, geo.W, geo.Cin), device=gy.device, dtype=torch.float32)
         for d, tapsel, _ in geo.dgrad:
             check(fn(_ptr(gy), _ptr(w), _ptr(out), _ptr(mask_ref), _ptr(addend),
-                     C.byref(_with_flags(d, fl, 0)), tapsel, geo.k * geo.k, _stream()), 'loans_dgrad_c4')
+                     C.byref(_with_flags(d, flags, 0)), tapsel, geo.k * geo.k, _stream()), 'loans_dgrad_c4')
         return out
-    flags = (F_MASK if mask_ref is not None else 0) | (F_ADDEND if addend is not None else 0) | \
-            (F_ADDEND_MASK if addend_mask_ref is not None else 0)
     ref = mask_ref if mask_ref is not None else addend_mask_ref
     assert not (mask_ref is not None and addend_mask_ref is not None)
     coef = sums = None
-    if bn_sums is not None:
+    if bn_sums is not None:             # LOANS_F_BNSUMS: the epilogue takes the two sums of the BN below
         assert flags == 0 and len(geo.dgrad) == 1 and not geo.dgrad_has_empty_class
         y, bst = bn_sums
-        assert not _is16(y) and y.is_contiguous() and y.numel() == out.numel()
+        assert _is16(y) == s16 and y.is_contiguous() and y.numel() == out.numel()
         flags, ref, coef, sums = F_BNSUMS, y, bst.mean, stats_buffer(geo.Cin, gy.device)
     st = _stream()
-    wp = _prepacked_dgrad_weights(w, geo, False)         # inside a step: made at its start, all layers in one launch
+    wp = _prepacked_dgrad_weights(w, geo, s16)          # inside a step: made at its start, all layers in one launch
     if wp is None:
-        wp = _empty(geo.dgrad_weight_floats, device=gy.device, dtype=torch.float32)
+        wp = _empty(geo.dgrad_weight_floats, device=gy.device, dtype=dtype)
+        repack = lib.loans_repack_dgrad_bf16 if s16 else lib.loans_repack_dgrad_f32
         for d, tapsel, off in geo.dgrad:
-            check(lib.loans_repack_dgrad_f32(_ptr(w), _ptr(wp[off:]), geo.Cout, geo.Cin, geo.k * geo.k, tapsel,
-                                             d.ntaps, st), 'loans_repack_dgrad_f32')
-    # split-K adds raw partial sums: a masked conv term cannot land on an addend that already sits in `out`
-    inplace_masked = addend is not None and addend.data_ptr() == out.data_ptr() and mask_ref is not None
-    dl = [(d, wp[off:]) for d, _, off in geo.dgrad]
-    rows_in = geo.B * geo.H * geo.W
-    if tile == 0:
-        vkey = _variant(geo, 'dgrad', bn_sums is not None, inplace_masked)
-        tile = geo.tuned.get(vkey, 0)
-    if tile == 0:
+            check(repack(_ptr(w), _ptr(wp[off:]), geo.Cout, geo.Cin, geo.k * geo.k, tapsel, d.ntaps, st),
+                  'loans_repack_dgrad_bf16' if s16 else 'loans_repack_dgrad_f32')
+    aliased = addend is not None and addend.data_ptr() == out.data_ptr()
+    if s16:
+        # a split-K data gradient finishes in ONE pass over the whole tensor: the tap-less classes of a strided 1x1 (which only
+        # take the addend, handled above by a copy) and an addend aliasing `out` do not go through it
+        sk_ok = not geo.dgrad_has_empty_class and not aliased
+        what = ('dgrad16', sk_ok, bn_sums is not None)
+    else:
+        # split-K adds raw partial sums: a masked conv term cannot land on an addend that already sits in `out`
+        sk_ok = not (aliased and mask_ref is not None)
+        what = ('dgrad', bn_sums is not None, not sk_ok)
+
+    def plan():
         def run(t):
-            scratch = _empty((geo.B, geo.H, geo.W, geo.Cin), device=gy.device, dtype=torch.float32)
-            if t & TILE_CLASSES:
-                _igemm_classes(lib, gy, wp, scratch, geo, 0, t & 0xFF, None, None, st)
-                return
-            if t >> 8:
-                _igemm_splitk(lib, gy, None, scratch, dl, 0, t, None, None, None, None, rows_in, geo.Cin, st)
-                return
-            for d, _, off in geo.dgrad:
-                check(_igemm_fn(lib)(_ptr(gy), _ptr(wp[off:]), _ptr(scratch), 0, 0, 0, 0,
-                                     C.byref(_with_flags(d, 0, t)), st), 'loans_igemm[tune]')
+            scratch = _empty((geo.B, geo.H, geo.W, geo.Cin), device=gy.device, dtype=dtype)
+            _dgrad_launch(lib, s16, gy, wp, scratch, geo, 0, t, None, None, None, None, st)
+        # the smallest class grid decides the split-K offer: (pixels of one parity class) x Cin columns, K = its taps x Cout
+        ktot = min(d.ntaps for d, _, _ in geo.dgrad) * geo.Cout
+        if s16:
+            cls_rows = geo.B * min(d.gridH * d.gridW for d, _, _ in geo.dgrad)
+            halo = _halo_tiles(geo, geo.Cout, geo.Cin, (geo.H, geo.W)) + _wide16_tiles(geo.Cin, cls_rows)
+            sk = _splitk16_candidates(cls_rows, geo.Cin, ktot) if sk_ok and bn_sums is None else ()
+            if bn_sums is not None:         # ws8_kernel's epilogue does not take the sums
+                halo = tuple(t for t in halo if t != TILE_WS64)
+            return ('bf16s_dgrad' + ('_h' if halo else '') + ('_sk' if sk else '') + ('_bn' if bn_sums is not None else ''), run,
+                    _IGEMM16_TILES + halo + sk, False)
         cl = _class_candidates(geo)
         cands, key = _IGEMM_TILES + cl, COMPUTE + 'dgrad' + ('_cl' if cl else '')
         if bn_sums is not None:
             key += '_bn'
-        elif not inplace_masked and reduce_channels_ok(geo.Cin):
-            # the smallest class grid decides: (Ho x Wo pixels of one parity class) x Cin columns, K = its taps x Cout
-            cls_rows = geo.B * geo.dgrad[0][0].gridH * geo.dgrad[0][0].gridW
-            sk = _splitk_candidates(cls_rows, geo.Cin, (min(d.ntaps for d, _, _ in geo.dgrad) * geo.Cout + 31) // 32)
+        elif sk_ok and reduce_channels_ok(geo.Cin):
+            sk = _splitk_candidates(geo.B * geo.dgrad[0][0].gridH * geo.dgrad[0][0].gridW, geo.Cin, (ktot + 31) // 32)
             cands, key = cands + sk, key + ('_sk' if sk else '')
-        tile = _tuned_tile(geo, key, run, cands)
-        geo.tuned[vkey] = tile
-    if tile & TILE_CLASSES:
-        _igemm_classes(lib, gy, wp, out, geo, flags, tile & 0xFF, ref, addend, st)
-        return out
-    if tile >> 8:
-        _igemm_splitk(lib, gy, None, out, dl, flags, tile, None, None, ref, addend, rows_in, geo.Cin, st)
-        return out
-    for d, tapsel, off in geo.dgrad:
-        _with_flags(d, flags, tile)
-        check(_igemm_fn(lib)(_ptr(gy), _ptr(wp[off:]), _ptr(out), _ptr(coef), _ptr(sums), _ptr(ref), _ptr(addend),
-                             C.byref(d), st), 'loans_igemm[dgrad]')
+        return key, run, cands, False
+    tile = _resolved_tile(geo, tile, what, plan)
+    if s16 and tile >> 8:
+        assert sk_ok and bn_sums is None
+    _dgrad_launch(lib, s16, gy, wp, out, geo, flags, tile, coef, sums, ref, addend, st)
     return out if bn_sums is None else (out, sums)
 
 
@@ -1299,14 +1238,14 @@ def crop_dgrad_ok(geo_a, geo_b=None, gy_a=None, gy_b=None):
     for gy, g in ((gy_a, geo_a), (gy_b, geo_b)):
         if gy is not None:
             ok = ok and g is not None and gy.is_contiguous() and gy.dtype in (torch.float32, BF16) \
-                and gy.numel() == g.B * g.Ho * g.Wo * g.Cout
+                and gy.numel() == g.rows * g.Cout
     if gy_a is not None and gy_b is not None:
         ok = ok and gy_a.dtype == gy_b.dtype
     for g in (geo_a, geo_b):
         if g is None:
             continue
         ok = ok and g.Cin == 4 and not g.dense and g.k <= 4 and g.stride <= 2 and g.pad < g.k and g.Cout == 128 \
-            and g.B * g.Ho * g.Wo * g.Cout * 4 < (1 << 31)
+            and g.rows * g.Cout * 4 < (1 << 31)
     if geo_b is not None:
         ok = ok and (geo_a.B, geo_a.H, geo_a.W, geo_a.Cout) == (geo_b.B, geo_b.H, geo_b.W, geo_b.Cout)
     return ok
@@ -1474,7 +1413,7 @@ def _wgrad_candidates(geo, tiles, chunk_px, dims=None):
     block slots decides the tail (res4: 36 tiles x 29 slices = 2.04 rounds of 512 slots runs at 96 TFLOP/s, x 14 = 0.98
     rounds at 118), so slot-aligned counts are offered beside the default and its half / double."""
     K = geo.w_numel // geo.Cout
-    chunks = (geo.B * geo.Ho * geo.Wo + chunk_px - 1) // chunk_px
+    chunks = (geo.rows + chunk_px - 1) // chunk_px
     cus = side_stream_cus()
     out = []
     for t in tiles:
@@ -1578,6 +1517,21 @@ def _wgrad_workspace(lib, geo, desc, tile, splits, device, st):
     return ws, need
 
 
+def _wgrad_launch(lib, wfn, x, gy, dw, geo, d, splits, st, slabs, in_affine=None):
+    """one weight gradient on descriptor d and stream handle st: into slabs of the workspace with the deterministic fold (slabs:
+    bf16 storage under WGRAD_SLABS, where the planner takes the request), else `wfn` with atomics into dw"""
+    ws = _wgrad_workspace(lib, geo, d, d.tile, splits, x.device, st) if slabs else None
+    if in_affine is not None:
+        if ws is None:          # (the workspace planner refused the descriptor: not a 1 x 1 / 1 convolution on a GEMM tile)
+            raise RuntimeError('loans_wgrad_bf16s_affine_ws does not cover this convolution')
+        check(lib.loans_wgrad_bf16s_affine_ws(_ptr(x), _ptr(gy), _ptr(dw), C.byref(d), splits, _ptr(ws[0]), ws[1], _ptr(in_affine.affine()),
+                                              st), 'loans_wgrad_bf16s_affine_ws')
+    elif ws is not None:
+        check(lib.loans_wgrad_bf16s_ws(_ptr(x), _ptr(gy), _ptr(dw), C.byref(d), splits, _ptr(ws[0]), ws[1], st), 'loans_wgrad_bf16s_ws')
+    else:
+        check(wfn(_ptr(x), _ptr(gy), _ptr(dw), C.byref(d), splits, st), 'loans_wgrad')
+
+
 def _conv_wgrad(x, gy, dw, geo, relu_in, splits, tile, stream=None, in_affine=None):
     lib = _lib.load()
     _count_flops('wgrad', geo)
@@ -1591,20 +1545,12 @@ def _conv_wgrad(x, gy, dw, geo, relu_in, splits, tile, stream=None, in_affine=No
     else:
         assert _is16(gy) == s16, 'x and gy must share their storage type'
     wfn = lib.loans_wgrad_bf16s if s16 else (lib.loans_wgrad_bf16_f32 if COMPUTE == 'bf16' else lib.loans_wgrad_f32)
-    if tile == 0:
-        vkey = _variant(geo, 'wgrad', s16, _is16(gy), relu_in, splits)
-        tile = geo.tuned.get(vkey, 0)
-    if tile == 0:
+    slabs = s16 and WGRAD_SLABS
+
+    def plan():
         def run(t):
             scratch = _empty(dw.numel(), device=x.device, dtype=torch.float32)
-            dt = _with_flags(geo.fwd, fl, t & 0xFF)
-            ws = _wgrad_workspace(lib, geo, dt, t & 0xFF, (t >> 8) or splits, x.device, _stream()) if (s16 and WGRAD_SLABS) else None
-            if ws is not None:
-                check(lib.loans_wgrad_bf16s_ws(_ptr(x), _ptr(gy), _ptr(scratch), C.byref(dt), (t >> 8) or splits, _ptr(ws[0]), ws[1],
-                                               _stream()), 'loans_wgrad_bf16s_ws[tune]')
-                return
-            check(wfn(_ptr(x), _ptr(gy), _ptr(scratch), C.byref(dt), (t >> 8) or splits,
-                      _stream()), 'loans_wgrad[tune]')
+            _wgrad_launch(lib, wfn, x, gy, scratch, geo, _with_flags(geo.fwd, fl, t & 0xFF), (t >> 8) or splits, _stream(), slabs)
         cands = _WGRAD16_TILES if s16 else _WGRAD_TILES
         if s16 and geo.Cout % 256 == 0:
             cands = cands + (TILE_256x256,)         # one 512-thread block per CU (csrc/igemm_bf16.hip, wgrad16_kernel<256, 256, 8>)
@@ -1617,29 +1563,18 @@ def _conv_wgrad(x, gy, dw, geo, relu_in, splits, tile, stream=None, in_affine=No
         stem = fl == F_DENSE and ((stem_wgrad_ok(geo) and wfn is lib.loans_wgrad_f32) or (s16 and stem16_wgrad_ok(geo)))
         if stem:
             cands = tuple(cands) + (TILE_STEM,)
-        tile = _tuned_tile(geo, _wgrad_key(x, gy, relu_in) + ('' if splits == 0 else '_s%d' % splits) + ('_st' if stem else ''),
-                           run, cands)
-        geo.tuned[vkey] = tile
+        return _wgrad_key(x, gy, relu_in) + ('' if splits == 0 else '_s%d' % splits) + ('_st' if stem else ''), run, cands, False
+    tile = _resolved_tile(geo, tile, ('wgrad', s16, _is16(gy), relu_in, splits), plan)
     if tile >> 8:
         tile, splits = tile & 0xFF, tile >> 8
         scale = WGRAD_SPLIT_SCALE if s16 else WGRAD_SPLIT_SCALE_F32
         if scale != 1.0:
             splits = max(1, int(splits * scale))
     if in_affine is not None:           # x is the input of the BN in front of the convolution: relu(bn(x)) applied on load
-        assert s16 and WGRAD_SLABS and fl == 0
+        assert slabs and fl == 0
         fl = F_AFFINE_IN
-    d = _with_flags(geo.fwd, fl, tile)
     st = stream if stream is not None else _stream()
-    ws = _wgrad_workspace(lib, geo, d, tile, splits, x.device, st) if (s16 and WGRAD_SLABS) else None
-    if in_affine is not None:
-        if ws is None:          # (the workspace planner refused the descriptor: not a 1 x 1 / 1 convolution on a GEMM tile)
-            raise RuntimeError('loans_wgrad_bf16s_affine_ws does not cover this convolution')
-        check(lib.loans_wgrad_bf16s_affine_ws(_ptr(x), _ptr(gy), _ptr(dw), C.byref(d), splits, _ptr(ws[0]), ws[1], _ptr(in_affine.affine()),
-                                              st), 'loans_wgrad_bf16s_affine_ws')
-    elif ws is not None:
-        check(lib.loans_wgrad_bf16s_ws(_ptr(x), _ptr(gy), _ptr(dw), C.byref(d), splits, _ptr(ws[0]), ws[1], st), 'loans_wgrad_bf16s_ws')
-    else:
-        check(wfn(_ptr(x), _ptr(gy), _ptr(dw), C.byref(d), splits, st), 'loans_wgrad')
+    _wgrad_launch(lib, wfn, x, gy, dw, geo, _with_flags(geo.fwd, fl, tile), splits, st, slabs, in_affine)
     if geo.dense and tile != TILE_STEM:         # the direct kernel never writes those columns
         # the window-padding columns of the dense layout saw real pixels: their "gradient" is not one
         check(lib.loans_mul_f32(_ptr(dw), _ptr(geo.wmask(x.device)), _ptr(dw), dw.numel(), st), 'loans_mul_f32')
