@@ -544,6 +544,24 @@ int loans_linear_fwd_bf16(const void* x, const float* W, const float* b, float* 
 int loans_linear_bwd_bf16(const void* x, const float* W, const float* y, const float* gy,
                           void* gx, float* gW, float* gb,
                           int32_t B, int32_t K, int32_t N, int32_t act_in, int32_t act_out, void* stream);
+/* L.Linear with 9 <= N <= 65536 outputs (the ImageNet heads: fc 512 -> 1000, fc6 2048 -> 1000), fp32 on the matrix cores.
+ * y[B][N] = x[B][K] W[N][K]^T + b (b may be NULL).  Limits: B in [1, 65536], K in [4, 65536] with K % 4 == 0, N in [9, 65536],
+ * every tensor under 2^31 elements; anything else is refused (LOANS_EINVAL / LOANS_ERANGE).  No atomics: two launches on the
+ * same inputs give the same bits. */
+int loans_linear_wide_fwd_f32(const float* x, const float* W, const float* b, float* y,
+                              int32_t B, int32_t K, int32_t N, void* stream);
+/* gx[b][k] = sum_n gy W (written); gW[n][k] += sum_b gy x; gb[n] += sum_b gy.  Each of gx / gW / gb may be NULL (not all);
+ * W is needed for gx, x for gW. */
+int loans_linear_wide_bwd_f32(const float* x, const float* W, const float* gy, float* gx, float* gW, float* gb,
+                              int32_t B, int32_t K, int32_t N, void* stream);
+/* F.softmax_cross_entropy(z, t, normalize=True, ignore_label=-1) and F.accuracy(z, t) in one pass over z [B][N] (N <= 8192,
+ * B <= 65536).  t: int32 labels; a label outside [0, N) -- -1 or anything else -- marks an ignored row (loss 0, gz row 0).
+ * count = max(#rows not ignored, 1).  gz[B][N] = (softmax(z) - onehot(t)) / count;  row_loss[B], row_hit[B]: per-row loss and
+ * (argmax == t, first index wins a tie);  out[0] = sum(row_loss) / count, out[1] = sum(row_hit) / B, both summed in a fixed order. */
+int loans_softmax_xent_fwd_f32(const float* z, const int32_t* t, float* gz, float* row_loss, float* row_hit,
+                               float* out, int32_t B, int32_t N, void* stream);
+/* y[i] = x[i] * s[0], s on the device (the loss's upstream gradient times gz) */
+int loans_scale_by_scalar_f32(const float* x, const float* s, float* y, int64_t n, void* stream);
 /* y = x * mask (elementwise, n floats) -- RotationDropout forward/backward (functions/rotation_droput.py:26-48) */
 int loans_mul_f32(const float* x, const float* mask, float* y, int64_t n, void* stream);
 /* y = a*x + b*y */

@@ -2,7 +2,8 @@
 
 Public surface mirrors the reference's (Bartzi/loans) for this path:
 ``SheepLocalizer``, ``ResnetAssessor``, ``SheepAssessor`` (alias ``SheepUpdater``),
-``rotation_dropout``, ``DirectionLossCalculator``, ``OutOfImageLossCalculator``, ``Adam``.
+``rotation_dropout``, ``DirectionLossCalculator``, ``OutOfImageLossCalculator``, ``Adam``; ``Classifier`` for the
+ImageNet pre-training arm (``SheepLocalizer(train_imagenet=True)``).
 """
 from .runtime.core import (Variable, Function, Link, Chain, ChainList, Parameter, config, using_config,  # noqa: F401
                            report, reporter, save_npz, load_npz)
@@ -12,6 +13,7 @@ from .iou.iou_regressor import MyResNet50Layers  # noqa: F401
 from .sheep.sheep_updater import SheepAssessor, SheepUpdater  # noqa: F401
 from .sheep.sheep_evaluator import SheepMAPEvaluator  # noqa: F401
 from .common.net import ResnetAssessor  # noqa: F401
+from .classifier import Classifier  # noqa: F401
 from .common.utils import Size, DirectionLossCalculator, OutOfImageLossCalculator  # noqa: F401
 from .functions.rotation_dropout import rotation_dropout, RotationDropout  # noqa: F401
 

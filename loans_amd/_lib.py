@@ -147,6 +147,10 @@ SIGNATURES = {
     'loans_gap_bwd_f32': [_p, _p, _i32, _i32, _i32, _p],
     'loans_linear_fwd_f32': [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p],
     'loans_linear_bwd_f32': [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p],
+    'loans_linear_wide_fwd_f32': [_p, _p, _p, _p, _i32, _i32, _i32, _p],
+    'loans_linear_wide_bwd_f32': [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p],
+    'loans_softmax_xent_fwd_f32': [_p, _p, _p, _p, _p, _p, _i32, _i32, _p],
+    'loans_scale_by_scalar_f32': [_p, _p, _p, _i64, _p],
     'loans_mul_f32': [_p, _p, _p, _i64, _p],
     'loans_axpby_f32': [_f32, _p, _f32, _p, _i64, _p],
     'loans_st_grid_fwd_f32': [_p, _p, _i32, _i32, _i32, _p],

@@ -1,0 +1,254 @@
+// The ImageNet classification head: a wide Linear layer (9 .. 2^16 outputs) in three directions on the fp32 matrix cores
+// (v_mfma_f32_32x32x2_f32), and softmax cross-entropy with top-1 accuracy in one pass over the logits.
+// No atomics anywhere in this file: every output element is owned by one lane (GEMM) or one block (loss rows) and is summed
+// in an order that depends on the shape alone, so two launches on the same inputs give the same bits.
+#include "common.h"
+
+namespace {
+
+// ---- small GEMM ------------------------------------------------------------------------------------------------------------
+// out[m][c] (+)= sum_r A(m, r) * Bm(r, c) (+ bias[c]),   m < M, c < C, r < R
+//   A(m, r)  = A[m * lda + r]  (A_RC: r contiguous)   or  A[r * lda + m]   (m contiguous)
+//   Bm(r, c) = Bm[c * ldb + r] (B_RC: r contiguous)   or  Bm[r * ldb + c]  (c contiguous)
+// Block = 4 waves = a 64 x 64 tile of `out`, one 32 x 32 accumulator per wave; the reduction runs in chunks of GK through LDS
+// images [r][m] and [r][c] (what one MFMA reads -- 32 consecutive floats per half wave -- is conflict free).  Rows, columns
+// and reduction indices past the edge are staged as zeros: fma(0, 0, acc) leaves acc bit for bit, so a ragged tile sums
+// exactly its own terms, in increasing r.  The MFMA is a k-ordered chain of fp32 fmaf: acc = fma(a_r, b_r, acc), r = 0 .. R-1.
+constexpr int GT = 64;          // tile edge
+constexpr int GK = 16;          // reduction chunk
+constexpr int GLD = GT + 4;     // LDS row pitch (floats)
+
+template <bool RC>
+__device__ __forceinline__ void stage_tile(const float* __restrict__ src, int ld, int e0, int E, int r0, int R,
+                                           float (*dst)[GLD], int tid) {
+    if (RC) {           // src[e * ld + r]: 16 consecutive threads walk r
+        const int r = tid & (GK - 1), gr = r0 + r;
+#pragma unroll
+        for (int i = 0; i < GT / 16; ++i) {
+            const int e = (tid >> 4) + 16 * i, ge = e0 + e;
+            dst[r][e] = (ge < E && gr < R) ? src[(int64_t)ge * ld + gr] : 0.f;
+        }
+    } else {            // src[r * ld + e]: 64 consecutive threads walk e
+        const int e = tid & (GT - 1), ge = e0 + e;
+#pragma unroll
+        for (int i = 0; i < GK / 4; ++i) {
+            const int r = (tid >> 6) + 4 * i, gr = r0 + r;
+            dst[r][e] = (ge < E && gr < R) ? src[(int64_t)gr * ld + ge] : 0.f;
+        }
+    }
+}
+
+template <bool A_RC, bool B_RC>
+__global__ __launch_bounds__(256) void gemm_tile_kernel(const float* __restrict__ A, int lda, const float* __restrict__ Bm, int ldb,
+                                                        const float* __restrict__ bias, float* __restrict__ out, int ldo,
+                                                        int M, int C, int R, int accumulate) {
+    __shared__ float As[GK][GLD];
+    __shared__ float Bs[GK][GLD];
+    const int tid = threadIdx.x;
+    const int wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int m0 = blockIdx.y * GT, c0 = blockIdx.x * GT;
+    f32x16 acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+    for (int r0 = 0; r0 < R; r0 += GK) {
+        stage_tile<A_RC>(A, lda, m0, M, r0, R, As, tid);
+        stage_tile<B_RC>(Bm, ldb, c0, C, r0, R, Bs, tid);
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < GK; kk += 2)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + h][wm * 32 + r], Bs[kk + h][wn * 32 + r], acc, 0, 0, 0);
+        __syncthreads();
+    }
+    const int c = c0 + wn * 32 + r;
+    if (c >= C) return;
+    const float bv = bias ? bias[c] : 0.f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int m = m0 + wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        if (m < M) {
+            float* o = out + (int64_t)m * ldo + c;
+            float v = acc[e] + bv;
+            if (accumulate) v += *o;
+            *o = v;
+        }
+    }
+}
+
+// gb[n] += sum_b gy[b][n], b increasing: one thread per column
+__global__ __launch_bounds__(256) void colsum_ordered_kernel(const float* __restrict__ gy, float* __restrict__ gb, int B, int N) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    float s = 0.f;
+    for (int b = 0; b < B; ++b) s += gy[(int64_t)b * N + n];
+    gb[n] += s;
+}
+
+// ---- softmax cross-entropy -------------------------------------------------------------------------------------------------
+// 256-thread block sum in a fixed tree: 6 butterfly levels inside each wave, then (w0 + w1) + (w2 + w3); valid in every thread
+__device__ __forceinline__ float block_sum_256(float v, float* sh) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+__device__ __forceinline__ int block_count_256(int v, int* sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+// one block per row; the row is read from memory once and kept in LDS (dynamic, N floats)
+//   m = max z, first index wins a tie;  S = sum exp(z - m);  lse = m + log S;  loss = lse - z[t]
+//   gz = (exp(z - m) / S - onehot) / count        count = max(#rows with a label in [0, N), 1)
+// rows whose label is outside [0, N) (-1 = ignore_label; anything else out of range is treated the same way): loss 0, gz 0.
+__global__ __launch_bounds__(256) void softmax_xent_rows_kernel(const float* __restrict__ z, const int* __restrict__ t,
+                                                                float* __restrict__ gz, float* __restrict__ row_loss,
+                                                                float* __restrict__ row_hit, int B, int N) {
+    extern __shared__ __attribute__((aligned(16))) float row[];
+    __shared__ float shf[4];
+    __shared__ int shi[4];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const float* zr = z + (int64_t)b * N;
+    float* gr = gz + (int64_t)b * N;
+
+    int valid = 0;
+    for (int i = tid; i < B; i += 256) valid += (unsigned)t[i] < (unsigned)N;
+    const int count = max(block_count_256(valid, shi), 1);
+
+    float m = -INFINITY;
+    int am = 0x7fffffff;
+    for (int i = tid; i < N; i += 256) {
+        const float v = zr[i];
+        row[i] = v;
+        if (v > m || am == 0x7fffffff) { m = v; am = i; }       // strictly greater: the earlier index stays on a tie
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float om = __shfl_xor(m, o, 64);
+        const int oa = __shfl_xor(am, o, 64);
+        if (oa != 0x7fffffff && (am == 0x7fffffff || om > m || (om == m && oa < am))) { m = om; am = oa; }
+    }
+    __syncthreads();
+    if ((tid & 63) == 0) { shf[tid >> 6] = m; shi[tid >> 6] = am; }
+    __syncthreads();
+    m = shf[0]; am = shi[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+        const float om = shf[w];
+        const int oa = shi[w];
+        if (oa != 0x7fffffff && (am == 0x7fffffff || om > m || (om == m && oa < am))) { m = om; am = oa; }
+    }
+
+    const int label = t[b];
+    if (tid == 0) row_hit[b] = (am == label) ? 1.f : 0.f;
+    if ((unsigned)label >= (unsigned)N) {       // ignored row (uniform per block)
+        for (int i = tid; i < N; i += 256) gr[i] = 0.f;
+        if (tid == 0) row_loss[b] = 0.f;
+        return;
+    }
+    float s = 0.f;
+    for (int i = tid; i < N; i += 256) s += expf(row[i] - m);
+    const float S = block_sum_256(s, shf);
+    if (tid == 0) row_loss[b] = (m + logf(S)) - row[label];
+    const float fc = (float)count;
+    for (int i = tid; i < N; i += 256) {
+        const float p = expf(row[i] - m) / S;
+        gr[i] = (p - (i == label ? 1.f : 0.f)) / fc;
+    }
+}
+
+// out[0] = (sum_b row_loss[b]) / count ; out[1] = (sum_b row_hit[b]) / B   -- one block, the same fixed tree
+__global__ __launch_bounds__(256) void softmax_xent_reduce_kernel(const float* __restrict__ row_loss, const float* __restrict__ row_hit,
+                                                                  const int* __restrict__ t, float* __restrict__ out, int B, int N) {
+    __shared__ float shf[4];
+    __shared__ int shi[4];
+    const int tid = threadIdx.x;
+    int valid = 0;
+    float l = 0.f, a = 0.f;
+    for (int i = tid; i < B; i += 256) {
+        valid += (unsigned)t[i] < (unsigned)N;
+        l += row_loss[i];
+        a += row_hit[i];
+    }
+    const int count = max(block_count_256(valid, shi), 1);
+    const float L = block_sum_256(l, shf);
+    const float A = block_sum_256(a, shf);
+    if (tid == 0) { out[0] = L / (float)count; out[1] = A / (float)B; }
+}
+
+__global__ __launch_bounds__(256) void scale_by_scalar_kernel(const float* __restrict__ x, const float* __restrict__ s,
+                                                              float* __restrict__ y, int64_t n) {
+    const float g = s[0];
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) y[i] = x[i] * g;
+}
+
+constexpr int WIDE_MAX = 1 << 16;           // B, K, N of the wide Linear
+constexpr int XENT_MAX_N = 1 << 13;         // one row of logits in LDS: 32 KB
+constexpr int XENT_MAX_B = 1 << 16;
+
+int wide_shape_ok(int32_t B, int32_t K, int32_t N) {
+    if (B <= 0 || K < 4 || (K & 3) || N < 9) return LOANS_EINVAL;
+    if (B > WIDE_MAX || K > WIDE_MAX || N > WIDE_MAX) return LOANS_ERANGE;
+    if ((int64_t)B * K >= (1ll << 31) || (int64_t)N * K >= (1ll << 31) || (int64_t)B * N >= (1ll << 31)) return LOANS_ERANGE;
+    return LOANS_OK;
+}
+
+dim3 tiles(int M, int C) { return dim3((C + GT - 1) / GT, (M + GT - 1) / GT); }
+
+}  // namespace
+
+extern "C" int loans_linear_wide_fwd_f32(const float* x, const float* W, const float* b, float* y, int32_t B, int32_t K,
+                                         int32_t N, void* stream) {
+    if (!x || !W || !y) return LOANS_EINVAL;
+    if (int rc = wide_shape_ok(B, K, N)) return rc;
+    hipLaunchKernelGGL((gemm_tile_kernel<true, true>), tiles(B, N), dim3(256), 0, as_stream(stream), x, K, W, K, b, y, N, B, N, K, 0);
+    LOANS_LAUNCH_CHECK();
+    return LOANS_OK;
+}
+
+extern "C" int loans_linear_wide_bwd_f32(const float* x, const float* W, const float* gy, float* gx, float* gW, float* gb,
+                                         int32_t B, int32_t K, int32_t N, void* stream) {
+    if (!gy) return LOANS_EINVAL;
+    if ((gx && !W) || (gW && !x)) return LOANS_EINVAL;
+    if (!gx && !gW && !gb) return LOANS_EINVAL;
+    if (int rc = wide_shape_ok(B, K, N)) return rc;
+    hipStream_t st = as_stream(stream);
+    if (gx) {       // gx[b][k] = sum_n gy[b][n] W[n][k]
+        hipLaunchKernelGGL((gemm_tile_kernel<true, false>), tiles(B, K), dim3(256), 0, st, gy, N, W, K, (const float*)nullptr, gx, K, B, K, N, 0);
+        LOANS_LAUNCH_CHECK();
+    }
+    if (gW) {       // gW[n][k] += sum_b gy[b][n] x[b][k]
+        hipLaunchKernelGGL((gemm_tile_kernel<false, false>), tiles(N, K), dim3(256), 0, st, gy, N, x, K, (const float*)nullptr, gW, K, N, K, B, 1);
+        LOANS_LAUNCH_CHECK();
+    }
+    if (gb) {
+        hipLaunchKernelGGL(colsum_ordered_kernel, dim3((N + 255) / 256), dim3(256), 0, st, gy, gb, B, N);
+        LOANS_LAUNCH_CHECK();
+    }
+    return LOANS_OK;
+}
+
+extern "C" int loans_softmax_xent_fwd_f32(const float* z, const int32_t* t, float* gz, float* row_loss, float* row_hit,
+                                          float* out, int32_t B, int32_t N, void* stream) {
+    if (!z || !t || !gz || !row_loss || !row_hit || !out || B <= 0 || N <= 0) return LOANS_EINVAL;
+    if (N > XENT_MAX_N || B > XENT_MAX_B) return LOANS_ERANGE;
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(softmax_xent_rows_kernel, dim3(B), dim3(256), (size_t)N * sizeof(float), st, z, t, gz, row_loss, row_hit, B, N);
+    LOANS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(softmax_xent_reduce_kernel, dim3(1), dim3(256), 0, st, row_loss, row_hit, t, out, B, N);
+    LOANS_LAUNCH_CHECK();
+    return LOANS_OK;
+}
+
+extern "C" int loans_scale_by_scalar_f32(const float* x, const float* s, float* y, int64_t n, void* stream) {
+    if (!x || !s || !y || n <= 0) return LOANS_EINVAL;
+    hipLaunchKernelGGL(scale_by_scalar_kernel, dim3(grid_for(n, 256)), dim3(256), 0, as_stream(stream), x, s, y, n);
+    LOANS_LAUNCH_CHECK();
+    return LOANS_OK;
+}

@@ -121,3 +121,19 @@ def make_assessor_batch(seed, batch, th, tw, src=224):
         images.append(to_chw_float(_resize_bilinear(crop_img, th, tw)))
         labels.append(round(float(best_iou), 4))
     return np.stack(images, axis=0), np.asarray(labels, np.float32).reshape(-1, 1)
+
+
+def make_classification_set(seed, n, classes, h, w, noise=20.0, split=0):
+    """Seeded classification examples for the ImageNet pre-training arm: class c owns ONE low-frequency RGB texture (drawn
+    from ``seed`` alone, so a training (``split=0``) and a validation set (``split=1``) of one seed share their classes);
+    example i shows the texture of class ``i % classes`` under Gaussian pixel noise drawn from (seed, split).  Returns ((n,3,h,w) float32 RGB in [0,1], exactly
+    k/255 like every frame here, and (n,) int32 labels)."""
+    proto_rng = np.random.Generator(np.random.PCG64(seed))
+    protos = [_low_freq_noise(proto_rng, h, w, cells=4).astype(np.float32) for _ in range(classes)]
+    rng = np.random.Generator(np.random.PCG64([seed, split + 1]))
+    labels = (np.arange(n) % classes).astype(np.int32)
+    images = []
+    for c in labels:
+        img = protos[int(c)] + rng.normal(0, noise, size=(h, w, 3)).astype(np.float32)
+        images.append(to_chw_float(np.clip(img + 0.5, 0, 255).astype(np.uint8)))
+    return np.stack(images, axis=0), labels

@@ -6,7 +6,7 @@ the reference calls: ``_global_average_pooling_2d`` (sheep_localizer.py:58),
 import torch
 
 from .. import ops
-from ..runtime.core import Function, Parameter, Variable
+from ..runtime.core import Function, Parameter, Variable, using_config
 
 
 class GlobalAveragePooling2D(Function):
@@ -25,7 +25,8 @@ def global_average_pooling_2d(x):
 
 
 class LinearFunction(Function):
-    """y = act_out(act_in(x) W^T + b); accumulates gW / gb into the arena itself."""
+    """y = act_out(act_in(x) W^T + b); accumulates gW / gb into the arena itself.  More than ``ops.LINEAR_SMALL_N`` outputs
+    (the ImageNet heads) run on the GEMM kernels of classify.hip, which have no fused activations."""
 
     def __init__(self, act_in=False, act_out=False):
         self.act_in, self.act_out = act_in, act_out
@@ -33,6 +34,11 @@ class LinearFunction(Function):
     def forward(self, inputs):
         x, W = inputs[0], inputs[1]
         b = inputs[2] if len(inputs) > 2 else None
+        self.wide = W.shape[0] > ops.LINEAR_SMALL_N
+        if self.wide:
+            if self.act_in or self.act_out:
+                raise ValueError('a Linear layer with more than %d outputs has no fused activation' % ops.LINEAR_SMALL_N)
+            return ops.linear_wide_fwd(x.contiguous(), W, b)
         self.y = ops.linear_fwd(x, W, b, self.act_in, self.act_out)
         return self.y
 
@@ -41,6 +47,11 @@ class LinearFunction(Function):
         Wp = self.inputs[1]
         bp = self.inputs[2] if len(inputs) > 2 else None
         wgrad = Wp.update_rule.enabled or not getattr(Wp, 'skip_grad_when_disabled', False)
+        if self.wide:
+            gx = ops.linear_wide_bwd(x.contiguous(), W, gys[0].contiguous(), gW=Wp.grad_view if wgrad else None,
+                                     gb=bp.grad_view if (bp is not None and wgrad) else None,
+                                     need_gx=self.inputs[0].requires_grad)
+            return (gx,) + (None,) * (len(inputs) - 1)
         gx = ops.linear_bwd(x, W, self.y, gys[0].contiguous(),
                             gW=Wp.grad_view if wgrad else None,
                             gb=bp.grad_view if (bp is not None and wgrad) else None,
@@ -117,6 +128,52 @@ def mean_squared_error(x0, x1):
     """``F.mean_squared_error(y, t)``.  ``t`` may be a constant-filled array created with
     ``xp.full`` (sheep_updater.py:42); any array works."""
     return MeanSquaredError()(x0, x1)
+
+
+class SoftmaxCrossEntropy(Function):
+    """``F.softmax_cross_entropy(x, t, normalize=True, ignore_label=-1)`` and ``F.accuracy(x, t)`` from ONE pass over the
+    logits: outputs (loss, accuracy), both 0-d device arrays.  t: int32 labels; a label outside [-1, N) is treated as ignored.
+    The forward leaves ``(softmax - onehot) / count`` behind; the backward multiplies it by the upstream gradient."""
+
+    def forward(self, inputs):
+        x, t = inputs[0].contiguous(), inputs[1].contiguous()
+        out, self.gz, _, _ = ops.softmax_xent_fwd(x, t)
+        return out[0], out[1]
+
+    def backward(self, inputs, gys):
+        if gys[0] is None:          # only the accuracy was used: it has no gradient
+            return None, None
+        return ops.scale_by_scalar(self.gz, gys[0].reshape(1).contiguous()), None
+
+    def release(self):
+        self.gz = None
+
+
+def _as_labels(x, t):
+    import numpy as np
+    if isinstance(t, Variable):
+        t = t.data
+    if isinstance(t, np.ndarray):
+        t = torch.from_numpy(np.ascontiguousarray(t))
+    device = x.data.device if isinstance(x, Variable) else x.device
+    return Variable(t.to(device=device, dtype=torch.int32), requires_grad=False)
+
+
+def softmax_cross_entropy_with_accuracy(x, t, ignore_label=-1):
+    if ignore_label != -1:
+        raise ValueError('only ignore_label=-1 (Chainer\'s default) is built')
+    return SoftmaxCrossEntropy()(x, _as_labels(x, t))
+
+
+def softmax_cross_entropy(x, t, ignore_label=-1):
+    """``F.softmax_cross_entropy(x, t)``: the mean loss over the rows whose label is not ``ignore_label``"""
+    return softmax_cross_entropy_with_accuracy(x, t, ignore_label)[0]
+
+
+def accuracy(y, t):
+    """``F.accuracy(y, t)``: the share of ALL rows whose argmax (first index on a tie) equals the label; not differentiable"""
+    with using_config('enable_backprop', False):
+        return softmax_cross_entropy_with_accuracy(y, t)[1]
 
 
 class GridLoss(Function):

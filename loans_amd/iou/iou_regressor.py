@@ -12,7 +12,7 @@ import collections
 
 from .. import links as L
 from ..functions import blocks
-from ..functions import global_average_pooling_2d
+from ..functions import global_average_pooling_2d, linear
 from ..runtime.core import Chain
 
 
@@ -100,9 +100,10 @@ class ResNet50Layers(Chain):
         ])
 
     def _fc6(self, x):
-        raise NotImplementedError("the ImageNet classifier head is outside the LoANs training path")
+        return linear(x, self.fc6.W, self.fc6.b)
 
-    _prob = _fc6
+    def _prob(self, x):
+        raise NotImplementedError("the 'prob' tap (a softmax over fc6) is not built: the classification loss takes the logits")
 
     @property
     def available_layers(self):

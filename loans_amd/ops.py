@@ -2352,6 +2352,61 @@ def linear_bwd(x, W, y, gy, gW=None, gb=None, need_gx=True, act_in=False, act_ou
     return gx
 
 
+LINEAR_SMALL_N = 8       # loans_linear_*: one block per sample walks N <= 8 outputs; wider layers are the GEMM of classify.hip
+
+
+def linear_wide_fwd(x, W, b=None):
+    """y = x W^T + b for 9 <= N <= 65536 outputs, fp32 (the pooled features are fp32 in both storage arms)"""
+    assert x.dtype == torch.float32 and W.dtype == torch.float32, 'the wide Linear is fp32 only'
+    B = x.shape[0]
+    K = x.numel() // B
+    N = W.numel() // K
+    y = _empty((B, N), device=x.device, dtype=torch.float32)
+    if CLASS_COUNT is not None: _acct('heads', 2 * B * K * N, _nbytes(x, W), _nbytes(y))
+    check(_lib.load().loans_linear_wide_fwd_f32(_ptr(x), _ptr(W), _ptr(b), _ptr(y), B, K, N, _stream()), 'loans_linear_wide_fwd_f32')
+    return y
+
+
+def linear_wide_bwd(x, W, gy, gW=None, gb=None, need_gx=True):
+    """gx = gy W (returned, or None); gW += gy^T x and gb += colsum(gy) in place"""
+    assert x.dtype == torch.float32 and gy.dtype == torch.float32, 'the wide Linear is fp32 only'
+    B = x.shape[0]
+    K = x.numel() // B
+    N = W.numel() // K
+    gx = _empty_like(x) if need_gx else None
+    if gx is None and gW is None and gb is None:
+        return None
+    if CLASS_COUNT is not None: _acct('heads', (4 if need_gx else 2) * B * K * N, _nbytes(x, W, gy), _nbytes(gx, gW))
+    check(_lib.load().loans_linear_wide_bwd_f32(_ptr(x), _ptr(W), _ptr(gy), _ptr(gx), _ptr(gW), _ptr(gb), B, K, N, _stream()),
+          'loans_linear_wide_bwd_f32')
+    return gx
+
+
+def softmax_xent_fwd(z, t):
+    """z (B, N) fp32 logits, t (B,) int32 labels on the device -> (out, gz, row_loss, row_hit): out[0] the batch loss, out[1] the
+    top-1 accuracy, gz = (softmax - onehot) / count.  No host synchronisation."""
+    assert z.dtype == torch.float32 and z.dim() == 2 and z.is_contiguous(), 'logits must be a contiguous (B, N) fp32 array'
+    assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == z.shape[0] and t.device == z.device, \
+        'labels must be int32, one per row, on the logits\' device'
+    B, N = z.shape
+    gz = _empty_like(z)
+    row_loss = _empty((B,), device=z.device, dtype=torch.float32)
+    row_hit = _empty((B,), device=z.device, dtype=torch.float32)
+    out = _empty((2,), device=z.device, dtype=torch.float32)
+    if CLASS_COUNT is not None: _acct('heads', 0, _nbytes(z), _nbytes(gz))
+    check(_lib.load().loans_softmax_xent_fwd_f32(_ptr(z), _ptr(t), _ptr(gz), _ptr(row_loss), _ptr(row_hit), _ptr(out), B, N,
+                                                 _stream()), 'loans_softmax_xent_fwd_f32')
+    return out, gz, row_loss, row_hit
+
+
+def scale_by_scalar(x, s):
+    """x * s[0] with s a one-element device tensor"""
+    assert s.dtype == torch.float32 and s.numel() == 1 and s.device == x.device
+    y = _empty_like(x)
+    check(_lib.load().loans_scale_by_scalar_f32(_ptr(x), _ptr(s), _ptr(y), x.numel(), _stream()), 'loans_scale_by_scalar_f32')
+    return y
+
+
 def mul(x, m, keep=False):
     """keep: the result outlives the step (a tensor callers hold across update() calls): never a slice of the step arena"""
     y = torch.empty_like(x) if keep else _empty_like(x)

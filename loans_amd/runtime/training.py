@@ -376,4 +376,22 @@ class StandardUpdater:
         self.iteration += 1
 
     def update_core(self):
-        raise NotImplementedError
+        """chainer.training.StandardUpdater: one batch of the ``main`` iterator through ``optimizer.update(target, *arrays)``
+        -- forward, cleargrads, backward, step -- inside one step workspace.  Runs in the target's own precision."""
+        from .. import ops
+        optimizer = self._optimizers['main']
+        loss_func = getattr(self, 'loss_func', None) or optimizer.target
+        with torch.cuda.device(self.device):
+            in_arrays = self.converter(next(self._iterators['main']), self.device)
+            want = optimizer.target.__dict__.get('precision') or ops.current_precision()
+            with ops.precision(*want):
+                ops.begin_step(torch.device('cuda', torch.cuda.current_device()))
+                try:
+                    if isinstance(in_arrays, tuple):
+                        optimizer.update(loss_func, *in_arrays)
+                    elif isinstance(in_arrays, dict):
+                        optimizer.update(loss_func, **in_arrays)
+                    else:
+                        optimizer.update(loss_func, in_arrays)
+                finally:
+                    ops.end_step()

@@ -7,9 +7,10 @@ interchange.  Each block's ``__call__`` is one fused function node
 (functions/blocks.py).  Only the basic-block depths the LoANs trainer can
 instantiate (18 / 20 / 34) are built; the bottleneck variants
 (sheep/resnet.py:163-216) belong to the ResNet-50 localizer.
+``class_labels=K`` adds the ImageNet head of sheep/resnet.py:65-87: global average pooling and ``fc = L.Linear(None, K)``.
 """
 from .. import links as L
-from ..functions import blocks
+from ..functions import blocks, global_average_pooling_2d, linear
 from ..runtime.core import Chain, ChainList
 
 
@@ -26,9 +27,6 @@ class ResNet(Chain):
             block = [3, 4, 6, 3]
         else:
             raise ValueError("You tried to create a ResNet variant that does not exist")
-        if class_labels is not None:
-            raise NotImplementedError("the ImageNet classification head is outside the LoANs training path")
-
         with self.init_scope():
             self.conv1 = L.Convolution2D(3, 64, 7, 2, 3, initialW=w, dense_rows=True)
             self.bn1 = L.BatchNormalization(64)
@@ -39,6 +37,8 @@ class ResNet(Chain):
             if n_layers == 20:
                 self.res6 = BasicBlock(block[4], 512, in_ch=512)
                 self.res7 = BasicBlock(block[5], 512, in_ch=512)
+            if class_labels is not None:
+                self.fc = L.Linear(None, class_labels)      # Chainer's default initialiser: LeCunNormal, zero bias
 
         self.n_layers = n_layers
         self.class_labels = class_labels
@@ -48,8 +48,16 @@ class ResNet(Chain):
     # the rest when the backward ends (loans_amd/parallel.py)
     exchange_stages = ('res4', 'res5')
 
+    def materialize_head(self):
+        """Size the lazily sized ``fc`` (the last stage has 512 channels at every depth).  A parameter can only join the
+        model's arena before ``finalize``, so whoever finalises the tree (the localizer, ``Classifier``) calls this first."""
+        if self.class_labels is not None:
+            self.fc.ensure_initialized(512)
+
     def __call__(self, x):
-        """x: preprocessed frames (``prepare_images``: the padded packed-RGB buffer conv1 reads).  Returns the NHWC feature map."""
+        """x: preprocessed frames (``prepare_images``: the padded packed-RGB buffer conv1 reads).  Returns the NHWC feature map,
+        or the (B, class_labels) logits when the model has the classification head."""
+        self.materialize_head()
         h = blocks.StemFunction(self.conv1, self.bn1)(x, self.conv1.W, self.conv1.b, self.bn1.gamma, self.bn1.beta)
         h = self.res2(h)
         h = self.res3(h)
@@ -60,6 +68,9 @@ class ResNet(Chain):
             h = self.res6(h)
         if hasattr(self, 'res7'):
             h = self.res7(h)
+        if self.class_labels is not None:
+            h = global_average_pooling_2d(h)        # average_pooling_2d(h, (H, W), stride=1)
+            h = linear(h, self.fc.W, self.fc.b)
         return h
 
 

@@ -35,20 +35,20 @@ class SheepLocalizer(Chain):
 
     def __init__(self, out_size, transform_rois_to_grayscale=False, train_imagenet=False):
         super().__init__()
-        if train_imagenet:
-            raise NotImplementedError("ImageNet pre-training head is outside the LoANs training path")
         with self.init_scope():
-            self.feature_extractor = ResNet(18, class_labels=None)
-            self.res6 = BasicBlock(2, 512, in_ch=512)
-            self.res7 = BasicBlock(2, 512, in_ch=512)
-            self.param_predictor = L.Linear(512, 6)
+            self.feature_extractor = ResNet(18, class_labels=1000 if train_imagenet else None)
+            if not train_imagenet:
+                self.res6 = BasicBlock(2, 512, in_ch=512)
+                self.res7 = BasicBlock(2, 512, in_ch=512)
+                self.param_predictor = L.Linear(512, 6)
 
-            transform_bias = self.param_predictor.b.host
-            transform_bias[[0, 4]] = 0.8
-            transform_bias[[2, 5]] = 0
-            self.param_predictor.W.host[...] = 0
+                transform_bias = self.param_predictor.b.host
+                transform_bias[[0, 4]] = 0.8
+                transform_bias[[2, 5]] = 0
+                self.param_predictor.W.host[...] = 0
 
-        self.cold_links = ('res6', 'res7')          # arena tail: only used on frames taller than 224 / 300 px
+        # arena tail: only used on frames taller than 224 / 300 px
+        self.cold_links = () if train_imagenet else ('res6', 'res7')
         self.visual_backprop_anchors = []
         self.out_size = tuple(out_size)
         self.transform_rois_to_grayscale = transform_rois_to_grayscale
@@ -58,6 +58,10 @@ class SheepLocalizer(Chain):
         self.visual_backprop_anchors.clear()
         device = images.data.device if isinstance(images, Variable) else (
             images.device if torch.is_tensor(images) and images.is_cuda else torch.device('cuda', torch.cuda.current_device()))
+        if self.train_imagenet:             # ImageNet pre-training: the logits of the backbone's own head
+            self.feature_extractor.materialize_head()
+            self.finalize(device)
+            return self.feature_extractor(self.prepare_images(_as_device_batch(images, device)))
         self.finalize(device)
         images = _as_device_batch(images, device)
         height = images.shape[-2]
@@ -149,23 +153,22 @@ class Resnet50SheepLocalizer(SheepLocalizer):
 
     def __init__(self, out_size, transform_rois_to_grayscale=False, train_imagenet=False):
         super(SheepLocalizer, self).__init__()
-        if train_imagenet:
-            raise NotImplementedError("ImageNet pre-training head is outside the LoANs training path")
         initialW = L.HeNormal(scale=1., fan_option='fan_out')
-        keys_to_remove = ['fc6', 'prob']
+        keys_to_remove = ['fc6', 'prob'] if not train_imagenet else ['prob']
         with self.init_scope():
             self.feature_extractor = MyResNet50Layers(keys_to_remove=keys_to_remove, pretrained_model='auto')
-            self.param_predictor = L.Linear(2048, 6)
+            if not train_imagenet:
+                self.param_predictor = L.Linear(2048, 6)
 
-            self.res6 = ResBlock(2, 2048, 1024, 2048, 2, initialW=initialW)
-            self.res7 = ResBlock(2, 2048, 1024, 2048, 2, initialW=initialW)
+                self.res6 = ResBlock(2, 2048, 1024, 2048, 2, initialW=initialW)
+                self.res7 = ResBlock(2, 2048, 1024, 2048, 2, initialW=initialW)
 
-            transform_bias = self.param_predictor.b.host
-            transform_bias[[0, 4]] = 0.8
-            transform_bias[[2, 5]] = 0
-            self.param_predictor.W.host[...] = 0
+                transform_bias = self.param_predictor.b.host
+                transform_bias[[0, 4]] = 0.8
+                transform_bias[[2, 5]] = 0
+                self.param_predictor.W.host[...] = 0
 
-        self.cold_links = ('res6', 'res7', 'feature_extractor/fc6')
+        self.cold_links = () if train_imagenet else ('res6', 'res7', 'feature_extractor/fc6')
         self.visual_backprop_anchors = []
         self.out_size = tuple(out_size)
         self.transform_rois_to_grayscale = transform_rois_to_grayscale
@@ -177,6 +180,8 @@ class Resnet50SheepLocalizer(SheepLocalizer):
             images.device if torch.is_tensor(images) and images.is_cuda else torch.device('cuda', torch.cuda.current_device()))
         self.finalize(device)
         images = _as_device_batch(images, device)
+        if self.train_imagenet:
+            return self.feature_extractor(self.prepare_images(images), layers=['fc6'])['fc6']
         height = images.shape[-2]
         self.arena.set_active('res6' if height <= 224 else ('res7' if height <= 300 else 'feature_extractor/fc6'))
 

@@ -1,0 +1,71 @@
+#!/usr/bin/env python
+"""Time one ImageNet pre-training step -- ``Classifier(SheepLocalizer(train_imagenet=True))``, Adam -- with device events, and
+say what the head costs: the flop counts of the three head GEMMs against the backbone's (``ops`` class accounting).
+
+    python tools/imagenet_step.py -b 256 --steps 20 --warmup 5             (step time, ms: median / min / max)
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/imagenet_step.py -b 256 --steps 3 --warmup 2
+        (per-kernel times: gemm_tile_kernel / colsum_ordered_kernel / softmax_xent_* are the head and the loss)
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np      # noqa: E402
+import torch            # noqa: E402
+
+import loans_amd        # noqa: E402
+from loans_amd.datasets import synthetic        # noqa: E402
+from loans_amd.runtime import training          # noqa: E402
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument('-b', '--batch-size', type=int, default=256)
+    ap.add_argument('--image-size', type=int, nargs=2, default=(224, 224))
+    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--dtype', default='f32', choices=['f32', 'bf16'])
+    ap.add_argument('--out', default=None, help='also write the JSON result here')
+    a = ap.parse_args(argv)
+    assert torch.cuda.is_available(), 'this measurement needs a GPU'
+    B, (H, W) = a.batch_size, a.image_size
+
+    np.random.seed(0)
+    model = loans_amd.Classifier(loans_amd.SheepLocalizer((75, 75), train_imagenet=True))
+    if a.dtype == 'bf16':
+        model.set_precision('bf16', 'bf16')
+    x, t = synthetic.make_classification_set(0, min(B, 64), 1000, H, W)
+    reps = -(-B // len(x))
+    x = torch.from_numpy(np.concatenate([x] * reps)[:B]).cuda()
+    t = torch.from_numpy(np.concatenate([t] * reps)[:B]).cuda()
+    opt = loans_amd.Adam(alpha=1e-3)
+    opt.setup(model)
+    upd = training.StandardUpdater(training.DeviceBatchIterator([(x, t)]), opt, converter=training.identity_converter, device=0)
+    for _ in range(a.warmup):
+        upd.update()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(a.steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        upd.update()
+        e1.record()
+        e1.synchronize()
+        times.append(e0.elapsed_time(e1))
+    head_flop = 3 * 2 * B * 512 * 1000
+    res = {'what': 'imagenet_step', 'dtype': a.dtype, 'batch': B, 'image_size': [H, W], 'steps': a.steps,
+           'step_ms_median': float(np.median(times)), 'step_ms_min': float(min(times)), 'step_ms_max': float(max(times)),
+           'images_per_s': B / (float(np.median(times)) * 1e-3), 'head_gflop': head_flop / 1e9,
+           'loss': float(loans_amd.reporter.observation['loss']), 'accuracy': float(loans_amd.reporter.observation['accuracy'])}
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, 'w') as f:
+            f.write(line + '\n')
+
+
+if __name__ == '__main__':
+    main()

@@ -1,0 +1,198 @@
+#!/usr/bin/env python
+"""ImageNet pre-training of the localizer backbones (the ``train_imagenet=True`` arm of the reference's localizers,
+sheep/sheep_localizer.py:20-49,122-152): ``Classifier(SheepLocalizer(train_imagenet=True))`` -- softmax cross-entropy over
+the 1000-way head -- trained with Adam.  The snapshot it writes is what ``train_sheep_localizer.py --rl`` starts a LoANs
+run from: ``load_pretrained_model`` is not strict, so the backbone is taken and ``fc`` / ``fc6`` are ignored.
+
+    python train_imagenet.py train.tsv val.tsv --use-resnet-18 -b 64
+    python train_imagenet.py --use-resnet-18 -b 32 --iterations 20            (seeded synthetic classes)
+    python train_sheep_localizer.py --use-resnet-18 --rl <log dir>/SheepLocalizer_20.npz
+
+``train_file`` / ``val_file`` hold one tab-separated ``path<TAB>class`` line per image, paths relative to the file; the
+literal ``synthetic`` (the default) is a seeded set of low-frequency textures, one per class.
+
+Not built (follow-ups): ``--gpus N``, ``--use-graph``, a momentum-SGD optimiser, top-5 accuracy, label smoothing and
+random-resized-crop augmentation.
+"""
+import argparse
+import datetime
+import json
+import os
+import time
+
+import numpy as np
+import torch
+
+import loans_amd
+from loans_amd.datasets import synthetic
+from loans_amd.runtime import training
+
+SYNTHETIC = 'synthetic'
+
+
+class SyntheticClasses:
+    """``LabeledImageDataset`` stand-in: (float32 CHW RGB frame in [0,1], int32 class) pairs"""
+
+    def __init__(self, n, classes, image_size, seed=0, split=0):
+        self.x, self.t = synthetic.make_classification_set(seed, n, classes, image_size[0], image_size[1], split=split)
+
+    def __len__(self):
+        return len(self.x)
+
+    def __getitem__(self, i):
+        return self.x[i], self.t[i]
+
+    get_example = __getitem__
+
+
+def parse_args(argv=None):
+    parser = argparse.ArgumentParser(description="ImageNet pre-training of a localizer backbone (MI355X-native)")
+    parser.add_argument("train_file", nargs='?', default=SYNTHETIC, help="tab-separated `path<TAB>class` lines ('synthetic': seeded textures)")
+    parser.add_argument("val_file", nargs='?', default=SYNTHETIC, help="validation file in the same format")
+    parser.add_argument("--use-resnet-18", action='store_true', default=False, help="SheepLocalizer (ResNet-18 variant) instead of the ResNet-50 one")
+    parser.add_argument("-b", "--batch-size", type=int, default=32, help="batch size")
+    parser.add_argument("-g", "--gpu", type=int, default=-1, help="gpu id to use (-1: the current device)")
+    parser.add_argument("--lr", "--learning-rate", dest="learning_rate", type=float, default=0.001, help="Adam's alpha")
+    parser.add_argument("--weight-decay", type=float, default=0.0, help="Adam's weight_decay_rate")
+    parser.add_argument("--num-epoch", type=int, default=100, help="number of epochs to train")
+    parser.add_argument("--iterations", type=int, default=None, help="stop after this many iterations (before --num-epoch epochs)")
+    parser.add_argument("--image-size", type=int, nargs=2, default=(224, 224), help="input size")
+    parser.add_argument("-l", "--log-dir", default='imagenet_logs', help="path to log dir")
+    parser.add_argument("--ln", "--log-name", dest="ln", default="test", help="name of log")
+    parser.add_argument("--log-interval", type=int, default=100, help="log interval")
+    parser.add_argument("--snapshot-interval", type=int, default=1000, help="number of iterations after which a snapshot will be taken")
+    parser.add_argument("--dtype", default='f32', choices=['f32', 'bf16'], help="f32, or bf16 activations and bf16 MFMA in the backbone (the head and the loss stay fp32)")
+    parser.add_argument("--seed", type=int, default=None, help="seed NumPy's global RNG before the model is built (the initialisers draw from it)")
+    parser.add_argument("--no-shuffle", action='store_true', help="iterate the training set in order")
+    parser.add_argument("--no-validation", dest='validation', action='store_false', default=True, help="don't do validation")
+    # the synthetic set
+    parser.add_argument("--dataset-size", type=int, default=256, help="synthetic training examples")
+    parser.add_argument("--validation-size", type=int, default=64, help="synthetic validation examples")
+    parser.add_argument("--synthetic-classes", type=int, default=10, help="classes of the synthetic set (labels 0 .. n-1 of the 1000-way head)")
+    parser.add_argument("--data-seed", type=int, default=10, help="seed of the synthetic set")
+    parser.add_argument("--flat-log-dir", action='store_true', help="write into --log-dir itself (no <time>_<name> sub-directory)")
+    parser.add_argument("--loader-threads", type=int, default=4, help="decode threads per iterator")
+    return parser.parse_args(argv)
+
+
+def build_model(args):
+    """the localizer in its ``train_imagenet`` form under a ``Classifier``; host side only"""
+    if args.seed is not None:
+        np.random.seed(args.seed)
+    localizer_class = loans_amd.SheepLocalizer if args.use_resnet_18 else loans_amd.Resnet50SheepLocalizer
+    model = loans_amd.Classifier(localizer_class((75, 75), train_imagenet=True))
+    model.materialize()         # the ResNet-18 variant's lazily sized fc
+    return model
+
+
+def build_datasets(args):
+    """(train, validation or None)"""
+    from loans_amd.common.datasets.image_dataset import LabeledImageDataset
+
+    def labelled(path):
+        return LabeledImageDataset(path, os.path.dirname(path), dtype=np.float32, label_dtype=np.int32,
+                                   image_size=tuple(args.image_size), return_dummy_scores=False)
+
+    if args.train_file == SYNTHETIC:
+        train = SyntheticClasses(args.dataset_size, args.synthetic_classes, args.image_size, seed=args.data_seed, split=0)
+    else:
+        train = labelled(args.train_file)
+    validation = None
+    if args.validation:
+        if args.val_file == SYNTHETIC:
+            validation = SyntheticClasses(args.validation_size, args.synthetic_classes, args.image_size, seed=args.data_seed, split=1)
+        else:
+            validation = labelled(args.val_file)
+    return train, validation
+
+
+def converter(batch, device=None):
+    """(frames (B,3,H,W) float32, labels (B,) int32) on the device; a label read from a file is a one-element row"""
+    images, labels = training.concat_examples(batch, device)[:2]
+    return images, labels.reshape(-1).to(torch.int32)
+
+
+def run(args, log=print):
+    """The training loop.  Returns (log entries, model)."""
+    if args.gpu < 0:
+        args.gpu = torch.cuda.current_device()
+    torch.cuda.set_device(args.gpu)
+
+    train_dataset, validation_dataset = build_datasets(args)
+    train_iter = training.MultithreadIterator(train_dataset, args.batch_size, shuffle=not args.no_shuffle, n_threads=args.loader_threads)
+
+    model = build_model(args)
+    localizer = model.predictor
+    if args.dtype == 'bf16':
+        model.set_precision('bf16', 'bf16')
+    model.to_gpu(args.gpu)
+
+    optimizer = loans_amd.Adam(alpha=args.learning_rate, weight_decay_rate=args.weight_decay)
+    optimizer.setup(model)
+    updater = training.StandardUpdater(train_iter, optimizer, converter=converter, device=args.gpu)
+
+    evaluator = None
+    if validation_dataset is not None:
+        validation_iter = training.MultithreadIterator(validation_dataset, args.batch_size, repeat=False, shuffle=False,
+                                                       n_threads=args.loader_threads)
+
+        def eval_func(x, t):
+            with loans_amd.using_config('train', False), loans_amd.using_config('enable_backprop', False):
+                model(x, t)
+            return {'validation/loss': float(model.loss.data), 'validation/accuracy': float(model.accuracy.data)}
+
+        evaluator = training.Evaluator(validation_iter, model, converter=converter, device=args.gpu, eval_func=eval_func)
+
+    if not args.flat_log_dir:
+        args.log_dir = os.path.join(args.log_dir, "{}_{}".format(datetime.datetime.now().isoformat(), args.ln))
+    os.makedirs(args.log_dir, exist_ok=True)
+    data_to_log = {'log_dir': args.log_dir, 'image_size': list(args.image_size), 'localizer': [localizer.__class__.__name__, 'localizer.py']}
+    for argument in filter(lambda x: not x.startswith('_'), dir(args)):
+        data_to_log[argument] = getattr(args, argument)
+    log_entries = []
+
+    def snapshot_path(it):
+        return os.path.join(args.log_dir, '%s_%d.npz' % (localizer.__class__.__name__, it))
+
+    t0 = time.time()
+    it = 0
+    while updater.epoch < args.num_epoch and (args.iterations is None or it < args.iterations):
+        updater.update()
+        it = updater.iteration
+        last = (args.iterations is not None and it == args.iterations) or updater.epoch >= args.num_epoch
+        if updater.is_new_epoch or it % args.log_interval == 0 or last:
+            # the only host synchronisation of an iteration
+            obs = loans_amd.reporter.observation
+            entry = {'iteration': it, 'epoch': updater.epoch, 'loss': float(obs['loss']), 'accuracy': float(obs['accuracy'])}
+            if evaluator is not None:
+                keep = (obs['loss'], obs['accuracy'])
+                entry.update({k: v for k, v in evaluator.evaluate().items() if k.startswith('validation/')})
+                loans_amd.report({'loss': keep[0], 'accuracy': keep[1]})
+            entry['elapsed_time'] = time.time() - t0
+            val = ''
+            if 'validation/loss' in entry:
+                val = '  validation loss %.5f accuracy %.4f' % (entry['validation/loss'], entry['validation/accuracy'])
+            log('iteration %4d  epoch %d  loss %.5f  accuracy %.4f%s  (%.1f s)' % (
+                it, updater.epoch, entry['loss'], entry['accuracy'], val, entry['elapsed_time']))
+            if not log_entries:
+                entry.update(data_to_log)
+            log_entries.append(entry)
+            with open(os.path.join(args.log_dir, 'log'), 'w') as f:
+                json.dump(log_entries, f, indent=4, default=str)
+        if it % args.snapshot_interval == 0:
+            loans_amd.save_npz(snapshot_path(it), localizer)
+    train_iter.finalize()
+    if evaluator is not None:
+        validation_iter.finalize()
+    if not os.path.exists(snapshot_path(updater.iteration)):
+        loans_amd.save_npz(snapshot_path(updater.iteration), localizer)
+    log('snapshot: %s' % snapshot_path(updater.iteration))
+    return log_entries, model
+
+
+def main(argv=None):
+    run(parse_args(argv))
+
+
+if __name__ == "__main__":
+    main()
