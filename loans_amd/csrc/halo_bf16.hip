@@ -17,6 +17,7 @@
 //   tile 8 x 16 x BN 64, one chunk (LOANS_TILE_HALO_128x64S, Cin = 64): 39 KiB, FOUR blocks per CU -- a Cin = 64 tile lives for
 //     nine steps only, so what hides its image load and its epilogue is other blocks, not its own pipeline
 #include "common.h"
+#include "conv_rows.h"
 #include <stdlib.h>
 
 namespace {
@@ -50,10 +51,6 @@ struct Halo16Args {
 #define HDBG(bit) false
 #endif
 
-__device__ __forceinline__ int xcd_remap_h(int id, int nblk) {
-    const int q = nblk >> 3, r = nblk & 7, xcd = id & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
-}
 __device__ __forceinline__ bf16x8_t relu8(bf16x8_t v) {
     const s16x8_t z = {0, 0, 0, 0, 0, 0, 0, 0};
     return __builtin_bit_cast(bf16x8_t, __builtin_elementwise_max(__builtin_bit_cast(s16x8_t, v), z));
@@ -97,7 +94,7 @@ __global__ __launch_bounds__(64 * WM * WN) void halo16_kernel(const Halo16Args a
 
     const loans_igemm_desc& d = a.d;
     const int tid = threadIdx.x;
-    int logical = xcd_remap_h(blockIdx.x, gridDim.x);
+    int logical = xcd_remap(blockIdx.x, gridDim.x);
     const int tn = logical % a.tiles_n; logical /= a.tiles_n;
     const int tx = logical % a.tiles_x; logical /= a.tiles_x;
     const int ty = logical % a.tiles_y;
@@ -801,10 +798,10 @@ __global__ __launch_bounds__(512, 1) void wsw_kernel(const Halo16Args a, int nun
 
     // units in row-pair strips: the eight waves of a block take eight neighbouring units, the blocks of an XCD the strips next
     // to each other (their halo rows overlap: L2 hits)
-    int gw = xcd_remap_h(blockIdx.x, gridDim.x) * 8 + wave_u, nw = gridDim.x * 8;
+    int gw = xcd_remap(blockIdx.x, gridDim.x) * 8 + wave_u, nw = gridDim.x * 8;
     if (HDBG(16)) {         // experiment: four working waves per CU (one per SIMD)
         if (wave_u >= 4) return;
-        gw = xcd_remap_h(blockIdx.x, gridDim.x) * 4 + wave_u;
+        gw = xcd_remap(blockIdx.x, gridDim.x) * 4 + wave_u;
         nw = gridDim.x * 4;
     }
     const int per_img = units_y * units_x;

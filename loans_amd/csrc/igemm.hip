@@ -17,6 +17,7 @@
 //   register-staged double buffering: global loads of chunk c+1 are issued before the 64
 //   MFMAs of chunk c and written to the other LDS buffer after them (one barrier per chunk).
 #include "common.h"
+#include "conv_rows.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -75,32 +76,21 @@ struct IgemmArgs {
     int nt_out;         // output stores non-temporal (loans_conv_nt)
     int dbg;            // experiment bits (LOANS_EXPERIMENT builds only; 0 in the product library)
     unsigned in_bytes, w_bytes, out_bytes;
-    struct {            // nx > 0: taps are an ny x nx grid, dy = dy0 + row*sdy, dx = dx0 + col*sdx, sd* = +-1
-        int nx, ny, dy0, sdy, dx0, sdx;
-        unsigned long long rowpat;      // bit (row * nx) set for every row
-    } ap;
     // class launch (loans_igemm_classes_f32): the stride-parity classes of ONE strided data gradient share a grid and a tail.
     // Everything that differs between classes lives here and the kernel reads it through `k` -- an ordinary launch is a class
-    // launch with ncls = 1 (cls[0] mirrors d / ap / M / Ktot).
+    // launch with ncls = 1 (cls[0] mirrors d / M / Ktot).
     int ncls;
     struct Cls {
         const float* w;
         unsigned w_bytes;
         int gridH, gridW, oy0, ox0, ntaps;
         int M, Ktot, nchunks, tail_groups, tiles_m, blk0, per_xcd;
-        int nx, ny, dy0, sdy, dx0, sdx;
-        unsigned long long rowpat;
+        TapGrid g;
         signed char dy[LOANS_MAX_CLS_TAPS], dx[LOANS_MAX_CLS_TAPS];
     } cls[LOANS_MAX_CLASSES];
 };
 
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-
-// XCD-aware, bijective block remap: blocks that share an XCD (id % 8) get a contiguous range of tiles
-__device__ __forceinline__ int xcd_remap(int id, int nblk) {
-    const int q = nblk >> 3, r = nblk & 7, xcd = id & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
-}
 
 // sched_group_barrier masks (LLVM SchedGroupMask)
 #define SG_VALU 0x2
@@ -206,71 +196,18 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
         taps[tid] = (int(tap_dy[t]) * d.inW + int(tap_dx[t])) * ubytes;
     }
 
-    // per row (fixed for the whole K loop): byte offset of its base pixel and a bitmask with bit t SET
-    // when tap t must read zero (outside the image, beyond ntaps, or the row does not exist).
-    // Every conv on this path has taps on an ny x nx grid whose dy / dx run in unit steps, so the in-bounds
-    // taps of a row are an index RANGE per axis and the mask is two shifts and a multiply -- no loops, no
-    // table reads.  (b, y, x) of the first row comes from two divisions, the others advance by 32 pixels.
+    // per row (fixed for the whole K loop): byte offset of its base pixel and a bitmask with bit t SET when tap t must read
+    // zero (outside the image, beyond ntaps, or the row does not exist); the output pixel's offset into opix (conv_rows.h)
     unsigned rowoff[RA];
     unsigned long long badmask[RA];
     {
-        const int gridH = k.gridH, gridW = k.gridW;
-        const int gHW = gridH * gridW;
-        const float inv_gw = 1.f / (float)gridW, inv_gh = 1.f / (float)gridH;
-        const int m0 = a.m_begin + tm * BM + lrow;
-        int b = m0 / gHW;
-        int rem = m0 - b * gHW;
-        int y = rem / gridW;
-        int x = rem - y * gridW;
-#pragma unroll
-        for (int i = 0; i < RA; ++i) {
-            const int m = m0 + 32 * i;
-            unsigned pixoff = 0xFFFFFFFFu;
-            unsigned long long mask = 0;
-            rowoff[i] = 0;
-            if (m < k.M) {
-                const int iy0 = y * d.isy, ix0 = x * d.isx;
-                rowoff[i] = (unsigned)((b * d.inH + iy0) * d.inW + ix0) * (unsigned)ubytes;
-                pixoff = (unsigned)((b * d.outH + y * d.osy + k.oy0) * d.outW + x * d.osx + k.ox0) * (unsigned)Cout *
-                         ((d.flags & LOANS_F_OUT_BF16) ? 2u : 4u);
-                if (dense) {
-                    mask = ~0ull;
-                } else if (k.nx > 0) {
-                    // column j valid <=> 0 <= ix0 + dx0 + j*sdx < inW  (sdx = +-1): a contiguous j range
-                    const int cx = ix0 + k.dx0, cy = iy0 + k.dy0;
-                    int jlo, jhi, rlo, rhi;
-                    if (k.sdx > 0) { jlo = max(0, -cx); jhi = min(k.nx, d.inW - cx); }
-                    else { jlo = max(0, cx - d.inW + 1); jhi = min(k.nx, cx + 1); }
-                    if (k.sdy > 0) { rlo = max(0, -cy); rhi = min(k.ny, d.inH - cy); }
-                    else { rlo = max(0, cy - d.inH + 1); rhi = min(k.ny, cy + 1); }
-                    if (jhi > jlo && rhi > rlo) {
-                        const unsigned long long colbits = ((1ull << jhi) - 1ull) & ~((1ull << jlo) - 1ull);
-                        const int blo = rlo * k.nx, bhi = rhi * k.nx;     // bhi <= 64
-                        const unsigned long long below_hi = bhi >= 64 ? ~0ull : ((1ull << bhi) - 1ull);
-                        const unsigned long long rowsel = k.rowpat & below_hi & ~((1ull << blo) - 1ull);
-                        mask = colbits * rowsel;       // colbits < 2^nx, rowsel bits nx apart: no carries
-                    }
-                } else {
-                    for (int t = 0; t < k.ntaps; ++t) {
-                        const int iy = iy0 + tap_dy[t], ix = ix0 + tap_dx[t];
-                        if ((unsigned)iy < (unsigned)d.inH && (unsigned)ix < (unsigned)d.inW) mask |= 1ull << t;
-                    }
-                }
-            }
-            badmask[i] = ~mask;
+        const RowLaunch rl = {a.m_begin + tm * BM + lrow, k.M, k.gridH, k.gridW, k.oy0, k.ox0, k.ntaps, tap_dy, tap_dx,
+                              (unsigned)Cout * ((d.flags & LOANS_F_OUT_BF16) ? 2u : 4u), (unsigned)ubytes, dense};
+        row_prologue<RA, 32>(d, k.g, rl, rowoff, badmask, opix + lrow, lu == 0);
 #ifdef LOANS_EXPERIMENT
-            if (a.dbg & 4) { rowoff[i] = (unsigned)((d.inW + 1) * ubytes) + (rowoff[i] & 0xFFFu); badmask[i] = 0; }   // cache-hot gathers
+        if (a.dbg & 4)      // cache-hot gathers
+            for (int i = 0; i < RA; ++i) { rowoff[i] = (unsigned)((d.inW + 1) * ubytes) + (rowoff[i] & 0xFFFu); badmask[i] = 0; }
 #endif
-            if (lu == 0) opix[lrow + 32 * i] = pixoff;
-            // advance 32 pixels: exact floor((v + .5) / n) for the small integers involved
-            x += 32;
-            const int qx = (int)(((float)x + 0.5f) * inv_gw);
-            x -= qx * gridW;
-            y += qx;
-            const int qy = (int)(((float)y + 0.5f) * inv_gh);
-            y -= qy * gridH;
-            b += qy;
-        }
     }
     __syncthreads();
 
@@ -327,30 +264,32 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
     f32x4 ra[RA], rb[RB];
     // The loader is cut into RA + RB + 1 independent pieces (one buffer load each, then the advance) so
     // that the K loop can drop one piece behind each MFMA of group 0: no waits, no branches.
-    auto load_a = [&](int i) {
+    auto a_off = [&](int i) {       // all ones where the tap is masked for this row or the K unit lies beyond Ktot
         const int tc = min(tap, LOANS_MAX_TAPS - 1);
         const unsigned kbad = (unsigned)(u * 4 < Ktot) - 1u;
         const unsigned bad = 0u - ((unsigned)(badmask[i] >> tc) & 1u);
-        const unsigned off = (rowoff[i] + toff) | bad | kbad;
+        return (rowoff[i] + toff) | bad | kbad;
+    };
+    auto b_off = [&](int i) {
+        const unsigned kbad = (unsigned)(u * 4 < Ktot) - 1u;
+        return (woff[i] + (unsigned)u * 16u) | wbad[i] | kbad;
+    };
+    auto load_a = [&](int i) {
+        const unsigned off = a_off(i);      // (made in front of the call: as an argument it moved instructions)
         ra[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)off, 0, 0));
     };
     auto load_b = [&](int i) {
-        const unsigned kbad = (unsigned)(u * 4 < Ktot) - 1u;
-        const unsigned off = (woff[i] + (unsigned)u * 16u) | wbad[i] | kbad;
+        const unsigned off = b_off(i);
         rb[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_w, (int)off, 0, 0));
     };
     const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
     typedef __attribute__((address_space(3))) void* lds_ptr_t;
     auto dma_a = [&](int buf, int i) {      // one 1 KiB LDS-DMA piece: 8 rows x 128 B of the A tile
-        const int tc = min(tap, LOANS_MAX_TAPS - 1);
-        const unsigned kbad = (unsigned)(u * 4 < Ktot) - 1u;
-        const unsigned bad = 0u - ((unsigned)(badmask[i] >> tc) & 1u);
-        const unsigned off = (rowoff[i] + toff) | bad | kbad;
+        const unsigned off = a_off(i);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_ptr_t)(As + (buf * BM + 32 * i + 8 * wave_u) * BK), 16, (int)off, 0, 0, 0);
     };
     auto dma_b = [&](int buf, int i) {
-        const unsigned kbad = (unsigned)(u * 4 < Ktot) - 1u;
-        const unsigned off = (woff[i] + (unsigned)u * 16u) | wbad[i] | kbad;
+        const unsigned off = b_off(i);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_ptr_t)(Bs + (buf * BN + 32 * i + 8 * wave_u) * BK), 16, (int)off, 0, 0, 0);
     };
     auto advance = [&]() {      // to the following chunk (8 units further along K); prefetch its tap offset
@@ -459,6 +398,15 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
 #ifdef LOANS_STAMPS
     unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, s_load = 0, s_mfma = 0, s_store = 0, s_bar = 0, t_begin = 0;
 #endif
+    // fp32 arms: MFMA number s (0 .. NMMA-1) of a k group
+    auto mma_one = [&](int s, const f32x4 (&af)[TM], const f32x4 (&bf)[TN]) {
+        const int kk = s / (TM * TN), i = (s / TN) % TM, j = s % TN;
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][kk], bf[j][kk], acc[i][j], 0, 0, 0);
+    };
+    auto mma = [&](const f32x4 (&af)[TM], const f32x4 (&bf)[TN]) {
+#pragma unroll
+        for (int s = 0; s < NMMA; ++s) mma_one(s, af, bf);
+    };
     if constexpr (BF16) {
         // ---- bf16 MFMA K loop: a chunk (32 of K) is two 32x32x16 steps per tile; the loop is bound by the
         // operand traffic, not the matrix pipe, so it stays simple: next chunk's loads in flight across the
@@ -498,14 +446,6 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
     // straight into the other LDS stage (free since the barrier that ended chunk c-1); they land while groups
     // 0..2 compute, __syncthreads() drains them (hipcc puts vmcnt(0) in front of the barrier while an LDS-DMA is
     // outstanding) and group 3's MFMAs run behind the barrier as in the register-staged loop.
-    auto mma_one = [&](int s, const f32x4 (&af)[TM], const f32x4 (&bf)[TN]) {
-        const int kk = s / (TM * TN), i = (s / TN) % TM, j = s % TN;
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][kk], bf[j][kk], acc[i][j], 0, 0, 0);
-    };
-    auto mma = [&](const f32x4 (&af)[TM], const f32x4 (&bf)[TN]) {
-#pragma unroll
-        for (int s = 0; s < NMMA; ++s) mma_one(s, af, bf);
-    };
     constexpr int NPIECE = RA + RB + 1;
     static_assert(NPIECE <= 2 * NMMA, "one piece per MFMA gap of groups 0 and 1");
     auto dma_piece = [&](int buf, int p) {
@@ -582,16 +522,6 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
     if (per_tap) k_loop(std::true_type{});
     else k_loop(std::false_type{});
     } else {
-    // MFMA number s (0 .. NMMA-1) of a k group
-    auto mma_one = [&](int s, const f32x4 (&af)[TM], const f32x4 (&bf)[TN]) {
-        const int kk = s / (TM * TN), i = (s / TN) % TM, j = s % TN;
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][kk], bf[j][kk], acc[i][j], 0, 0, 0);
-    };
-    auto mma = [&](const f32x4 (&af)[TM], const f32x4 (&bf)[TN]) {
-#pragma unroll
-        for (int s = 0; s < NMMA; ++s) mma_one(s, af, bf);
-    };
-
     // ---- software-pipelined K loop ---------------------------------------------------------------
     // A chunk (32 of K) = 4 groups of 8; fragments of group g+1 are read from LDS while the MFMAs of
     // group g run; the loader pieces of chunk c+1 ride one behind each MFMA of group 0, their LDS
@@ -877,15 +807,13 @@ constexpr size_t igemm_lds_bytes() {
     return igemm_aux_floats<BM, BN, DMA>() * 4 + LOANS_MAX_TAPS * 4 + BM * 4;
 }
 
-// an ordinary launch is a class launch with one class: the kernel reads the per-class view only
+// an ordinary launch is a class launch with one class: the kernel reads the per-class view only (cls[0].g: igemm_impl)
 void fill_class0(IgemmArgs& a) {
     IgemmArgs::Cls& k = a.cls[0];
     a.ncls = 1;
     k.w = a.w; k.w_bytes = a.w_bytes;
     k.gridH = a.d.gridH; k.gridW = a.d.gridW; k.oy0 = a.d.oy0; k.ox0 = a.d.ox0; k.ntaps = a.d.ntaps;
     k.M = a.M; k.Ktot = a.Ktot; k.nchunks = a.nchunks; k.tail_groups = a.tail_groups; k.tiles_m = a.tiles_m; k.blk0 = 0; k.per_xcd = 0;
-    k.nx = a.ap.nx; k.ny = a.ap.ny; k.dy0 = a.ap.dy0; k.sdy = a.ap.sdy; k.dx0 = a.ap.dx0; k.sdx = a.ap.sdx;
-    k.rowpat = a.ap.rowpat;
 }
 
 template <int BM, int BN, int WM, int WN, bool RELU, bool BF16, bool DMA>
@@ -931,22 +859,6 @@ int launch_igemm_r(IgemmArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, a);
     LOANS_LAUNCH_CHECK();
     return LOANS_OK;
-}
-
-// recognise a row-major ny x nx tap grid with unit-step dy / dx (every conv of this path); nx = 0 otherwise
-void detect_tap_grid(const loans_igemm_desc* d, IgemmArgs& a) {
-    a.ap.nx = 0; a.ap.ny = 0; a.ap.dy0 = a.ap.dx0 = 0; a.ap.sdy = a.ap.sdx = 1; a.ap.rowpat = 0;
-    int nx = 1;
-    while (nx < d->ntaps && d->dy[nx] == d->dy[0]) ++nx;
-    if (d->ntaps % nx) return;
-    const int ny = d->ntaps / nx;
-    const int sdx = nx > 1 ? d->dx[1] - d->dx[0] : 1;
-    const int sdy = ny > 1 ? d->dy[nx] - d->dy[0] : 1;
-    if ((sdx != 1 && sdx != -1) || (sdy != 1 && sdy != -1)) return;
-    for (int t = 0; t < d->ntaps; ++t)
-        if (d->dy[t] != d->dy[0] + (t / nx) * sdy || d->dx[t] != d->dx[0] + (t % nx) * sdx) return;
-    a.ap.nx = nx; a.ap.ny = ny; a.ap.dy0 = d->dy[0]; a.ap.sdy = sdy; a.ap.dx0 = d->dx[0]; a.ap.sdx = sdx;
-    for (int r = 0; r < ny; ++r) a.ap.rowpat |= 1ull << (r * nx);
 }
 
 template <int BM, int BN, int WM, int WN>
@@ -1040,7 +952,7 @@ static int igemm_impl(const float* in, const float* w, float* out, const float* 
         a.out_bytes = (unsigned)ob;
         a.nt_out = loans_conv_nt((size_t)ob);
     }
-    detect_tap_grid(d, a);
+    a.cls[0].g = detect_tap_grid(d);
     if (pair) {
         const int64_t wb2 = (int64_t)pair->Cout * a.Ktot * 4;
         const int64_t ob2 = (int64_t)d->B * d->outH * d->outW * pair->Cout * 4;
@@ -1062,9 +974,8 @@ static int igemm_impl(const float* in, const float* w, float* out, const float* 
                 e->outW != d->outW || e->Cout != d->Cout || e->osy != d->osy || e->osx != d->osx || e->isy != d->isy ||
                 e->isx != d->isx || e->flags != d->flags)
                 return LOANS_EINVAL;
-            IgemmArgs t;                    // tap grid of this class
-            detect_tap_grid(e, t);
             IgemmArgs::Cls& k = a.cls[c];
+            k.g = detect_tap_grid(e);
             k.w = mc->w[c];
             k.gridH = e->gridH; k.gridW = e->gridW; k.oy0 = e->oy0; k.ox0 = e->ox0; k.ntaps = e->ntaps;
             k.M = e->B * e->gridH * e->gridW;
@@ -1073,8 +984,6 @@ static int igemm_impl(const float* in, const float* w, float* out, const float* 
             k.nchunks = (k.Ktot + BK - 1) / BK;
             k.tail_groups = (k.Ktot - (k.nchunks - 1) * BK + 7) / 8;
             k.tiles_m = 0; k.blk0 = 0; k.per_xcd = 0;      // per tile shape: launch_igemm_r
-            k.nx = t.ap.nx; k.ny = t.ap.ny; k.dy0 = t.ap.dy0; k.sdy = t.ap.sdy; k.dx0 = t.ap.dx0; k.sdx = t.ap.sdx;
-            k.rowpat = t.ap.rowpat;
             for (int i = 0; i < LOANS_MAX_CLS_TAPS; ++i) { k.dy[i] = e->dy[i < e->ntaps ? i : 0]; k.dx[i] = e->dx[i < e->ntaps ? i : 0]; }
         }
     }

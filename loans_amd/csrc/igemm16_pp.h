@@ -47,7 +47,7 @@ __global__ __launch_bounds__(512) void igemm16pp_kernel(const Igemm16Args a) {
 
     const loans_igemm_desc& d = a.d;
     const int tid = threadIdx.x;
-    const int logical = xcd_remap16(blockIdx.x, gridDim.x);
+    const int logical = xcd_remap(blockIdx.x, gridDim.x);
     const int tn = logical % a.tiles_n;
     const int tm = logical / a.tiles_n;
     const int nch = a.nchunks;
@@ -61,54 +61,9 @@ __global__ __launch_bounds__(512) void igemm16pp_kernel(const Igemm16Args a) {
     // per staged row (tile row lrow + 64 q, q = 0..3: rows 64 q' of half q >> 1): base pixel offset, bitmask of taps that read zero
     unsigned rowoff[4], badmask[4];
     {
-        const int gHW = d.gridH * d.gridW;
-        const float inv_gw = 1.f / (float)d.gridW, inv_gh = 1.f / (float)d.gridH;
-        const int m0 = tm * BM + lrow;
-        int b = m0 / gHW;
-        int rem = m0 - b * gHW;
-        int y = rem / d.gridW;
-        int x = rem - y * d.gridW;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int m = m0 + RPP * i;
-            unsigned pixoff = 0xFFFFFFFFu;
-            unsigned long long mask = 0;
-            rowoff[i] = 0;
-            if (m < a.M) {
-                const int iy0 = y * d.isy, ix0 = x * d.isx;
-                rowoff[i] = (unsigned)((b * d.inH + iy0) * d.inW + ix0) * (unsigned)pbytes;
-                pixoff = (unsigned)((b * d.outH + y * d.osy + d.oy0) * d.outW + x * d.osx + d.ox0) * (unsigned)a.out_c * 2u;
-                if (a.ap.nx > 0) {
-                    const int cx = ix0 + a.ap.dx0, cy = iy0 + a.ap.dy0;
-                    int jlo, jhi, rlo, rhi;
-                    if (a.ap.sdx > 0) { jlo = max(0, -cx); jhi = min(a.ap.nx, d.inW - cx); }
-                    else { jlo = max(0, cx - d.inW + 1); jhi = min(a.ap.nx, cx + 1); }
-                    if (a.ap.sdy > 0) { rlo = max(0, -cy); rhi = min(a.ap.ny, d.inH - cy); }
-                    else { rlo = max(0, cy - d.inH + 1); rhi = min(a.ap.ny, cy + 1); }
-                    if (jhi > jlo && rhi > rlo) {
-                        const unsigned long long colbits = ((1ull << jhi) - 1ull) & ~((1ull << jlo) - 1ull);
-                        const int blo = rlo * a.ap.nx, bhi = rhi * a.ap.nx;
-                        const unsigned long long below_hi = bhi >= 64 ? ~0ull : ((1ull << bhi) - 1ull);
-                        const unsigned long long rowsel = a.ap.rowpat & below_hi & ~((1ull << blo) - 1ull);
-                        mask = colbits * rowsel;
-                    }
-                } else {
-                    for (int t = 0; t < d.ntaps; ++t) {
-                        const int iy = iy0 + d.dy[t], ix = ix0 + d.dx[t];
-                        if ((unsigned)iy < (unsigned)d.inH && (unsigned)ix < (unsigned)d.inW) mask |= 1ull << t;
-                    }
-                }
-            }
-            badmask[i] = ~(unsigned)mask;
-            if (lu == 0) opix[lrow + RPP * i] = pixoff;
-            x += RPP;
-            const int qx = (int)(((float)x + 0.5f) * inv_gw);
-            x -= qx * d.gridW;
-            y += qx;
-            const int qy = (int)(((float)y + 0.5f) * inv_gh);
-            y -= qy * d.gridH;
-            b += qy;
-        }
+        const RowLaunch rl = {tm * BM + lrow, a.M, d.gridH, d.gridW, d.oy0, d.ox0, d.ntaps, d.dy, d.dx, (unsigned)a.out_c * 2u,
+                              (unsigned)pbytes, false};
+        row_prologue<4, RPP>(d, a.g, rl, rowoff, badmask, opix + lrow, lu == 0);
     }
     __syncthreads();
 

@@ -12,6 +12,7 @@
 // Same problem descriptor, tap masks, XCD-aware tile order and epilogue flags as igemm.hip; forward convolution and
 // data gradient are the same kernel (dgrad: one launch per stride-parity class on re-packed weights).
 #include "common.h"
+#include "conv_rows.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -51,10 +52,7 @@ struct Igemm16Args {
     int nt_out;         // output stores non-temporal (loans_conv_nt)
     int dbg;            // experiment bits (LOANS_EXPERIMENT builds only)
     unsigned in_bytes, w_bytes, out_bytes;
-    struct {            // nx > 0: taps are an ny x nx grid, dy = dy0 + row*sdy, dx = dx0 + col*sdx, sd* = +-1
-        int nx, ny, dy0, sdy, dx0, sdx;
-        unsigned long long rowpat;
-    } ap;
+    TapGrid g;
     // split-K (loans_igemm_bf16s_splitk): block (tile, s) contracts chunks [s * cps, (s + 1) * cps) and ADDS its raw fp32 tile
     // to `partial` [pixels][Cout] (zeroed by the caller); loans_igemm_finalize_bf16 makes the bf16 tensor of the finished sums
     int splits, chunks_per_split;
@@ -66,11 +64,6 @@ struct Igemm16Args {
     unsigned tensor_bytes;
     double* stats2;
 };
-
-__device__ __forceinline__ int xcd_remap16(int id, int nblk) {
-    const int q = nblk >> 3, r = nblk & 7, xcd = id & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
-}
 
 // relu on packed bf16: as signed 16-bit integers the negative floats (and -0) are negative, so max(v, 0) is relu
 typedef short s16x8_t __attribute__((ext_vector_type(8)));
@@ -128,7 +121,7 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm16_kernel(const Igemm16Args
     unsigned long long t_entry = 0;
     STAMP16(t_entry);
 #endif
-    const int logical = xcd_remap16(blockIdx.x, gridDim.x);
+    const int logical = xcd_remap(blockIdx.x, gridDim.x);
     const int ntile = a.tiles_m * a.tiles_n;
     const int split = logical / ntile;                  // 0 unless split-K
     const int ltile = logical - split * ntile;
@@ -148,65 +141,19 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm16_kernel(const Igemm16Args
         taps[tid] = (int(d.dy[t]) * d.inW + int(d.dx[t])) * pbytes;
     }
 
-    // per row: byte offset of its base pixel and the bitmask of taps that must read zero (see igemm.hip)
+    // per row: byte offset of its base pixel and the bitmask of taps that must read zero (conv_rows.h, see igemm.hip)
     // (32 bits here: the launcher admits at most 32 taps without LOANS_F_DENSE, and a dense launch has no bad tap --
     // one v_bfe_i32 per piece instead of a 64-bit shift + extract)
     unsigned rowoff[RA];
     unsigned badmask[RA];
     {
-        const int gHW = d.gridH * d.gridW;
-        const float inv_gw = 1.f / (float)d.gridW, inv_gh = 1.f / (float)d.gridH;
-        const int m0 = tm * BM + lrow;
-        int b = m0 / gHW;
-        int rem = m0 - b * gHW;
-        int y = rem / d.gridW;
-        int x = rem - y * d.gridW;
-#pragma unroll
-        for (int i = 0; i < RA; ++i) {
-            const int m = m0 + RPP * i;
-            unsigned pixoff = 0xFFFFFFFFu;
-            unsigned long long mask = 0;
-            rowoff[i] = 0;
-            if (m < a.M) {
-                const int iy0 = y * d.isy, ix0 = x * d.isx;
-                rowoff[i] = (unsigned)((b * d.inH + iy0) * d.inW + ix0) * (unsigned)pbytes;
-                pixoff = (unsigned)((b * d.outH + y * d.osy + d.oy0) * d.outW + x * d.osx + d.ox0) * (unsigned)a.out_c * 2u;
-                if (dense) {
-                    mask = ~0ull;
-                } else if (a.ap.nx > 0) {
-                    const int cx = ix0 + a.ap.dx0, cy = iy0 + a.ap.dy0;
-                    int jlo, jhi, rlo, rhi;
-                    if (a.ap.sdx > 0) { jlo = max(0, -cx); jhi = min(a.ap.nx, d.inW - cx); }
-                    else { jlo = max(0, cx - d.inW + 1); jhi = min(a.ap.nx, cx + 1); }
-                    if (a.ap.sdy > 0) { rlo = max(0, -cy); rhi = min(a.ap.ny, d.inH - cy); }
-                    else { rlo = max(0, cy - d.inH + 1); rhi = min(a.ap.ny, cy + 1); }
-                    if (jhi > jlo && rhi > rlo) {
-                        const unsigned long long colbits = ((1ull << jhi) - 1ull) & ~((1ull << jlo) - 1ull);
-                        const int blo = rlo * a.ap.nx, bhi = rhi * a.ap.nx;
-                        const unsigned long long below_hi = bhi >= 64 ? ~0ull : ((1ull << bhi) - 1ull);
-                        const unsigned long long rowsel = a.ap.rowpat & below_hi & ~((1ull << blo) - 1ull);
-                        mask = colbits * rowsel;
-                    }
-                } else {
-                    for (int t = 0; t < d.ntaps; ++t) {
-                        const int iy = iy0 + d.dy[t], ix = ix0 + d.dx[t];
-                        if ((unsigned)iy < (unsigned)d.inH && (unsigned)ix < (unsigned)d.inW) mask |= 1ull << t;
-                    }
-                }
-            }
-            badmask[i] = ~(unsigned)mask;
+        const RowLaunch rl = {tm * BM + lrow, a.M, d.gridH, d.gridW, d.oy0, d.ox0, d.ntaps, d.dy, d.dx, (unsigned)a.out_c * 2u,
+                              (unsigned)pbytes, dense};
+        row_prologue<RA, RPP>(d, a.g, rl, rowoff, badmask, opix + lrow, lu == 0);
 #ifdef LOANS_EXPERIMENT
-            if (a.dbg & 4) { rowoff[i] = (unsigned)((d.inW + 1) * pbytes) + (rowoff[i] & 0x3FFu); badmask[i] = 0; }   // cache-hot gathers
+        if (a.dbg & 4)      // cache-hot gathers
+            for (int i = 0; i < RA; ++i) { rowoff[i] = (unsigned)((d.inW + 1) * pbytes) + (rowoff[i] & 0x3FFu); badmask[i] = 0; }
 #endif
-            if (lu == 0) opix[lrow + RPP * i] = pixoff;
-            x += RPP;
-            const int qx = (int)(((float)x + 0.5f) * inv_gw);
-            x -= qx * d.gridW;
-            y += qx;
-            const int qy = (int)(((float)y + 0.5f) * inv_gh);
-            y -= qy * d.gridH;
-            b += qy;
-        }
     }
     __syncthreads();
 
@@ -686,21 +633,6 @@ int launch_igemm16(Igemm16Args& a, hipStream_t st) {
 
 #include "igemm16_pp.h"      // LOANS_TILE_256x256PP: the same block tile with a ping-pong K loop
 
-void detect_tap_grid16(const loans_igemm_desc* d, Igemm16Args& a) {
-    a.ap.nx = 0; a.ap.ny = 0; a.ap.dy0 = a.ap.dx0 = 0; a.ap.sdy = a.ap.sdx = 1; a.ap.rowpat = 0;
-    int nx = 1;
-    while (nx < d->ntaps && d->dy[nx] == d->dy[0]) ++nx;
-    if (d->ntaps % nx) return;
-    const int ny = d->ntaps / nx;
-    const int sdx = nx > 1 ? d->dx[1] - d->dx[0] : 1;
-    const int sdy = ny > 1 ? d->dy[nx] - d->dy[0] : 1;
-    if ((sdx != 1 && sdx != -1) || (sdy != 1 && sdy != -1)) return;
-    for (int t = 0; t < d->ntaps; ++t)
-        if (d->dy[t] != d->dy[0] + (t / nx) * sdy || d->dx[t] != d->dx[0] + (t % nx) * sdx) return;
-    a.ap.nx = nx; a.ap.ny = ny; a.ap.dy0 = d->dy[0]; a.ap.sdy = sdy; a.ap.dx0 = d->dx[0]; a.ap.sdx = sdx;
-    for (int r = 0; r < ny; ++r) a.ap.rowpat |= 1ull << (r * nx);
-}
-
 // fp32 -> bf16 (RNE), n a multiple of 4; dst[co][tapsel..] re-pack variant below
 __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* src, __bf16* dst, int64_t n4) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x)
@@ -779,7 +711,7 @@ __global__ __launch_bounds__(64 * NWV) void wgrad16_kernel(const Wgrad16Args a) 
 
     const loans_igemm_desc& d = a.d;
     const int tid = threadIdx.x;
-    const int logical = xcd_remap16(blockIdx.x, gridDim.x);
+    const int logical = xcd_remap(blockIdx.x, gridDim.x);
     const int ntile = a.tiles_co * a.tiles_j;
     const int split = logical / ntile;
     const int tile = logical - split * ntile;
@@ -1079,7 +1011,7 @@ static int igemm_bf16s_impl(const void* in, const void* w, void* out, const floa
         a.nt_out = loans_conv_nt((size_t)ob);
         if (pair) a.tensor_bytes = (unsigned)(ob / 2);
     }
-    detect_tap_grid16(d, a);
+    a.g = detect_tap_grid(d);
     hipStream_t st = as_stream(stream);
     int tile = d->tile;
     if (tile == 0) {

@@ -20,6 +20,7 @@
 // Global loads of tile n + 1 are issued before the MFMAs of tile n and land in registers (the LDS image is single: a
 // block's ~2300-4600 MFMA cycles per tile hide the two short LDS-write phases around its barriers).
 #include "common.h"
+#include "conv_rows.h"
 
 namespace {
 
@@ -56,14 +57,6 @@ struct WgHaloArgs {
     int64_t slab;
 };
 
-__device__ __forceinline__ int xcd_remap(int id, int nblk) {
-    // consecutive logical ids on one XCD (hardware deals blocks round-robin over the 8 XCDs): the channel-tile pairs that
-    // share a pixel range then share an L2
-    const int per = nblk >> 3;
-    if (per == 0 || (nblk & 7)) return id;
-    return (id & 7) * per + (id >> 3);
-}
-
 __device__ __forceinline__ u32x4 relu8(u32x4 v) {
     const i16x8 s = __builtin_bit_cast(i16x8, v);
     const i16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -84,7 +77,7 @@ __global__ __launch_bounds__(64 * NWV, NWV == 4 ? 2 : 1) void wgrad_halo16_kerne
     __bf16* Xs = Ys + TH * TW * SY;                          // [HH * HW][SX]
 
     const int tid = threadIdx.x;
-    const int logical = xcd_remap(blockIdx.x, gridDim.x);
+    const int logical = xcd_remap_whole(blockIdx.x, gridDim.x);
     const int npairs = a.pairs_co * a.pairs_c;
     const int split = logical / npairs;
     const int pair = logical - split * npairs;

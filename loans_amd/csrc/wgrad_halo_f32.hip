@@ -21,6 +21,7 @@
 // Pixel-tile forms (compile-time, picked by the launcher from the frame): 7 x 14; 7 x 8 where that pads the frame less; and,
 // for frames up to 7 x 7, image pairs (wgrad_halo32_pair_kernel below), where a k-step is the same pixel of two images.
 #include "common.h"
+#include "conv_rows.h"
 
 namespace {
 
@@ -48,14 +49,6 @@ struct WgHalo32Args {
     unsigned x_bytes, gy_bytes;
 };
 
-__device__ __forceinline__ int xcd_remap(int id, int nblk) {
-    // consecutive logical ids on one XCD (hardware deals blocks round-robin over the 8 XCDs): the channel-tile pairs that
-    // share a pixel range then share an L2
-    const int per = nblk >> 3;
-    if (per == 0 || (nblk & 7)) return id;
-    return (id & 7) * per + (id >> 3);
-}
-
 __device__ __forceinline__ u32x4 relu4(u32x4 v) {
     f32x4 f = __builtin_bit_cast(f32x4, v);
     f.x = fmaxf(f.x, 0.f); f.y = fmaxf(f.y, 0.f); f.z = fmaxf(f.z, 0.f); f.w = fmaxf(f.w, 0.f);
@@ -76,7 +69,7 @@ __global__ __launch_bounds__(NT, 2) void wgrad_halo32_kernel(const WgHalo32Args 
     float* Xs = Ys + YPX * BC;                               // [XPX][64]
 
     const int tid = threadIdx.x;
-    const int logical = xcd_remap(blockIdx.x, gridDim.x);
+    const int logical = xcd_remap_whole(blockIdx.x, gridDim.x);
     const int npairs = a.pairs_co * a.pairs_c;
     const int split = logical / npairs;
     const int pair = logical - split * npairs;
@@ -216,7 +209,7 @@ __global__ __launch_bounds__(NT, 2) void wgrad_halo32_pair_kernel(const WgHalo32
     float* Xs = Ys + 2 * YPX * BC;                           // [2][XPX][64]
 
     const int tid = threadIdx.x;
-    const int logical = xcd_remap(blockIdx.x, gridDim.x);
+    const int logical = xcd_remap_whole(blockIdx.x, gridDim.x);
     const int npairs = a.pairs_co * a.pairs_c;
     const int split = logical / npairs;
     const int pair = logical - split * npairs;
