@@ -1022,13 +1022,6 @@ int reduce_geometry(int64_t rows, int C, int* rows_per_block, int* c4_block, int
     return (int)((rows + rpb - 1) / rpb);
 }
 
-// C/4 float4 groups must tile 256-thread blocks: a divisor of 256, or a multiple of 256 (slabs)
-bool reduce_channels_ok(int C) {
-    if (C < 4 || (C & 3)) return false;
-    const int c4 = C / 4;
-    return c4 <= 256 ? (256 % c4 == 0) : (c4 % 256 == 0);
-}
-
 // bn_bwd_reduce_kernel and colsum_kernel leave the threads beyond RL * C4 idle (`rl < RL`), so they take ANY C / 4 <= 256, not
 // only the divisors of 256: the channel counts the 16-byte-unit kernels do not tile (96, 192, ...) have to end here, the BN
 // backward has no other reduction.  (The other entry points keep reduce_channels_ok, which ops.py mirrors.)
@@ -1342,13 +1335,9 @@ extern "C" int loans_bn_bwd_reduce_bf16(const void* gy, const void* mask, const 
 
 extern "C" int loans_igemm_finalize_f32(float* out, const float* bias, double* stats, const float* ref, const float* addend,
                                         int32_t flags, int64_t rows, int32_t C, void* stream) {
-    if (!out || rows <= 0 || !reduce_channels_ok(C)) return LOANS_EINVAL;
-    if ((flags & LOANS_F_BIAS) && !bias) return LOANS_EINVAL;
-    if ((flags & LOANS_F_STATS) && !stats) return LOANS_EINVAL;
-    if ((flags & (LOANS_F_MASK | LOANS_F_ADDEND_MASK)) && !ref) return LOANS_EINVAL;
-    if ((flags & LOANS_F_ADDEND_MASK) && !(flags & LOANS_F_ADDEND)) return LOANS_EINVAL;
-    if ((flags & LOANS_F_ADDEND) && !addend) return LOANS_EINVAL;
-    if (flags & ~(LOANS_F_BIAS | LOANS_F_STATS | LOANS_F_MASK | LOANS_F_ADDEND | LOANS_F_ADDEND_MASK)) return LOANS_EINVAL;
+    if (int rc = conv_check_finalize_f32(conv_have(out, CONV_P_OUT) | conv_have(bias, CONV_P_BIAS) | conv_have(stats, CONV_P_STATS) |
+                                             conv_have(ref, CONV_P_REF) | conv_have(addend, CONV_P_ADDEND), flags, rows, C))
+        return rc;
     int rpb, c4b, slabs;
     const int grid = reduce_geometry(rows, C, &rpb, &c4b, &slabs);
     hipLaunchKernelGGL(igemm_finalize_kernel, dim3(grid, slabs), dim3(256), 0, as_stream(stream), out, bias, stats, ref, addend,

@@ -4,6 +4,7 @@
 #include <stdlib.h>
 #include <stdint.h>
 #include "loans_hip.h"
+#include "conv_desc.h"      // (and conv_rows.h: TapGrid)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -32,6 +33,17 @@ template <> struct io4<__bf16> {
     } while (0)
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// what a check of conv_desc.h gets to know about a pointer: `bit` when it is there / when it is off a 16-byte boundary
+static inline unsigned conv_have(const void* p, unsigned bit) { return p ? bit : 0u; }
+static inline unsigned conv_misaligned(const void* p, unsigned bit) { return ((uintptr_t)p & 15) ? bit : 0u; }
+static inline unsigned conv_have_igemm(const void* in, const void* w, const void* out, const void* bias, const void* stats, const void* ref, const void* addend) {
+    return conv_have(in, CONV_P_IN) | conv_have(w, CONV_P_W) | conv_have(out, CONV_P_OUT) | conv_have(bias, CONV_P_BIAS) |
+           conv_have(stats, CONV_P_STATS) | conv_have(ref, CONV_P_REF) | conv_have(addend, CONV_P_ADDEND);
+}
+static inline unsigned conv_misaligned_igemm(const void* in, const void* w, const void* out) {
+    return conv_misaligned(in, CONV_P_IN) | conv_misaligned(w, CONV_P_W) | conv_misaligned(out, CONV_P_OUT);
+}
 
 // ---- per-device launcher state ---------------------------------------------------------------------------------------------
 // "device = the calling thread's current HIP device" (include/loans_hip.h): whatever a launcher caches about the device is
@@ -117,32 +129,26 @@ int loans_stem7_wgrad_launch(const float* x, const float* gy, float* dw, const l
 int loans_stem7_wgrad_bf16_slabs(const loans_igemm_desc* d);
 int loans_stem7_wgrad_bf16_launch(const void* x, const void* gy, float* dw, const loans_igemm_desc* d, float* ws, hipStream_t st);
 int loans_stem7_bf16_rows(int Ho, int Wo, int Wp3, size_t* lds_bytes);
-int loans_stem7_bf16_launch(const float* in, const float* w, void* out, const float* bias, double* stats,
-                            const loans_igemm_desc* d, hipStream_t st);
-int loans_stem7_bf16s_launch(const void* in, const void* w, void* out, const float* bias, double* stats,
-                             const loans_igemm_desc* d, hipStream_t st);
+template <typename TIN>     // float (loans_igemm_bf16_f32) or __bf16 (loans_igemm_bf16s): instantiated in stem.hip
+int loans_stem7_bf16_launch(const TIN* in, const TIN* w, void* out, const float* bias, double* stats, const loans_igemm_desc* d, hipStream_t st);
 
 // halo_bf16.hip: stride-1 convolutions on bf16 storage with the input tile staged once per channel chunk (LOANS_TILE_HALO_*;
 // internal, reached through loans_igemm_bf16s)
-int loans_halo16_covers(const loans_igemm_desc* d, int tile);
 int loans_halo16_launch(const void* in, const void* w, void* out, const float* bias, double* stats, const void* ref,
-                        const void* addend, const loans_igemm_desc* d, int tile, unsigned in_bytes, unsigned w_bytes,
-                        unsigned out_bytes, hipStream_t st);
+                        const void* addend, const loans_igemm_desc* d, int tile, const TapGrid& g, unsigned in_bytes,
+                        unsigned w_bytes, unsigned out_bytes, hipStream_t st);
 
 // pw_bf16.hip: 1 x 1 / 1 convolutions with Cin in {64, 128} on bf16 storage, operands never in LDS (LOANS_TILE_PW; internal,
 // reached through loans_igemm_bf16s; `w` in loans_pw_pack_bf16's fragment order)
-int loans_pw16_covers(const loans_igemm_desc* d);
 int loans_pw16_launch(const void* in, const void* w, void* out, double* stats, const float* aff, const loans_igemm_desc* d, hipStream_t st);
 
 // wgrad_halo_f32.hip: weight gradient of stride-1 3 x 3 convolutions on fp32 tensors with all taps in one block
 // (LOANS_TILE_WGHALO_64; internal, reached through loans_wgrad_f32)
-int loans_wgrad_halo32_covers(const loans_igemm_desc* d);
 int loans_wgrad_halo32_launch(const float* x, const float* gy, float* dw, const loans_igemm_desc* d, int splits,
                               unsigned x_bytes, unsigned gy_bytes, hipStream_t st);
 
 // wgrad_halo_bf16.hip: weight gradient of stride-1 3 x 3 convolutions on bf16 storage with all taps in one block
 // (LOANS_TILE_WGHALO_*; internal, reached through loans_wgrad_bf16s)
-int loans_wgrad_halo16_covers(const loans_igemm_desc* d, int tile);
 int loans_wgrad_halo16_slabs(const loans_igemm_desc* d, int tile, int splits);
 int loans_wgrad_halo16_launch(const void* x, const void* gy, float* dw, const loans_igemm_desc* d, int tile, int splits,
                               unsigned x_bytes, unsigned gy_bytes, float* ws, int* slabs, hipStream_t st);

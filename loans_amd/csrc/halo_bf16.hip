@@ -1087,31 +1087,10 @@ int launch_halo(Halo16Args& a, hipStream_t st) {
 
 }  // namespace
 
-// 1 if the descriptor is a geometry the halo kernels cover (the caller -- loans_igemm_bf16s -- has validated everything else)
-int loans_halo16_covers(const loans_igemm_desc* d, int tile) {
-    if (d->flags & LOANS_F_DENSE) return 0;
-    if ((d->flags & LOANS_F_BNSUMS) && tile == LOANS_TILE_WS64) return 0;        // ws8_kernel's epilogue does not take the BN sums
-    if (d->isy != 1 || d->isx != 1 || d->osy != 1 || d->osx != 1 || d->oy0 || d->ox0) return 0;
-    if (d->gridH != d->outH || d->gridW != d->outW) return 0;
-    if (d->Cin % 64 || d->ntaps > 9) return 0;
-    if ((tile == LOANS_TILE_HALO_256x64 || tile == LOANS_TILE_HALO_128x64S) && d->Cin != 64) return 0;
-    if ((tile == LOANS_TILE_WS64 || tile == LOANS_TILE_WSW64) && (d->Cin != 64 || d->Cout > 64 || d->ntaps != 9 || (d->flags & LOANS_F_RELU_IN))) return 0;
-    int nx = 1;
-    while (nx < d->ntaps && d->dy[nx] == d->dy[0]) ++nx;
-    if (d->ntaps % nx) return 0;
-    const int ny = d->ntaps / nx;
-    if (nx > 3 || ny > 3) return 0;
-    const int sdx = nx > 1 ? d->dx[1] - d->dx[0] : 1, sdy = ny > 1 ? d->dy[nx] - d->dy[0] : 1;
-    if ((sdx != 1 && sdx != -1) || (sdy != 1 && sdy != -1)) return 0;
-    for (int t = 0; t < d->ntaps; ++t)
-        if (d->dy[t] != d->dy[0] + (t / nx) * sdy || d->dx[t] != d->dx[0] + (t % nx) * sdx) return 0;
-    return 1;
-}
-
+// the caller (loans_igemm_bf16s) has run conv_check_igemm16, conv_halo16_covers with it; g = the tap grid of d
 int loans_halo16_launch(const void* in, const void* w, void* out, const float* bias, double* stats, const void* ref,
-                        const void* addend, const loans_igemm_desc* d, int tile, unsigned in_bytes, unsigned w_bytes,
-                        unsigned out_bytes, hipStream_t st) {
-    if (!loans_halo16_covers(d, tile)) return LOANS_EINVAL;
+                        const void* addend, const loans_igemm_desc* d, int tile, const TapGrid& g, unsigned in_bytes,
+                        unsigned w_bytes, unsigned out_bytes, hipStream_t st) {
     Halo16Args a;
     a.in = static_cast<const __bf16*>(in); a.w = static_cast<const __bf16*>(w); a.out = static_cast<__bf16*>(out);
     a.bias = bias; a.stats = stats;
@@ -1125,14 +1104,9 @@ int loans_halo16_launch(const void* in, const void* w, void* out, const float* b
 #ifdef LOANS_EXPERIMENT
     if (const char* e = getenv("LOANS_HALO_DBG")) a.dbg = atoi(e);
 #endif
-    if (in_bytes >= 0x80000000u || w_bytes >= 0x80000000u) return LOANS_ERANGE;       // offsets >= 2^31 mean "no load" here
-    int nx = 1;
-    while (nx < d->ntaps && d->dy[nx] == d->dy[0]) ++nx;
-    a.nx = nx; a.ny = d->ntaps / nx;
-    a.sdx = nx > 1 ? d->dx[1] - d->dx[0] : 1;
-    a.sdy = a.ny > 1 ? d->dy[nx] - d->dy[0] : 1;
-    a.dymin = a.sdy > 0 ? d->dy[0] : d->dy[0] - (a.ny - 1);
-    a.dxmin = a.sdx > 0 ? d->dx[0] : d->dx[0] - (a.nx - 1);
+    a.nx = g.nx; a.ny = g.ny; a.sdx = g.sdx; a.sdy = g.sdy;
+    a.dymin = g.sdy > 0 ? g.dy0 : g.dy0 - (g.ny - 1);
+    a.dxmin = g.sdx > 0 ? g.dx0 : g.dx0 - (g.nx - 1);
     switch (tile) {
         case LOANS_TILE_HALO_128: return launch_halo<8, 16, 128, 2, 2, true>(a, st);
         case LOANS_TILE_HALO_128x64: return launch_halo<8, 16, 64, 4, 1, true>(a, st);
@@ -1140,8 +1114,8 @@ int loans_halo16_launch(const void* in, const void* w, void* out, const float* b
         case LOANS_TILE_HALO_128x64S: return launch_halo<8, 16, 64, 4, 1, false>(a, st);
         case LOANS_TILE_HALO_256x128: return launch_halo<16, 16, 128, 4, 2, true>(a, st);      // 512 threads, one block per CU
         case LOANS_TILE_HALO_256x256: return launch_halo<16, 16, 256, 2, 4, true>(a, st);      // 512 threads: eight 128 x 64 wave tiles
-        case LOANS_TILE_WS64: return a.nx == 3 && a.ny == 3 ? launch_ws8(a, st) : LOANS_EINVAL;
-        case LOANS_TILE_WSW64: return a.nx == 3 && a.ny == 3 ? launch_wsw(a, st) : LOANS_EINVAL;
+        case LOANS_TILE_WS64: return launch_ws8(a, st);
+        case LOANS_TILE_WSW64: return launch_wsw(a, st);
         default: return LOANS_EINVAL;
     }
 }

@@ -869,31 +869,6 @@ int launch_igemm(IgemmArgs& a, hipStream_t st) {
     return relu ? launch_igemm_r<BM, BN, WM, WN, true, false, false>(a, st) : launch_igemm_r<BM, BN, WM, WN, false, false, false>(a, st);
 }
 
-int check_desc(const loans_igemm_desc* d) {
-    if (!d) return LOANS_EINVAL;
-    if (d->B <= 0 || d->inH <= 0 || d->inW <= 0 || d->Cin <= 0 || (d->Cin & 3)) return LOANS_EINVAL;
-    if (d->outH <= 0 || d->outW <= 0 || d->Cout <= 0) return LOANS_EINVAL;
-    if (d->gridH <= 0 || d->gridW <= 0 || d->osy <= 0 || d->osx <= 0 || d->isy <= 0 || d->isx <= 0) return LOANS_EINVAL;
-    if (d->oy0 < 0 || d->ox0 < 0) return LOANS_EINVAL;
-    if ((d->gridH - 1) * d->osy + d->oy0 >= d->outH) return LOANS_EINVAL;
-    if ((d->gridW - 1) * d->osx + d->ox0 >= d->outW) return LOANS_EINVAL;
-    if (d->ntaps < 1 || d->ntaps > LOANS_MAX_TAPS) return LOANS_EINVAL;
-    const int64_t lim = (int64_t)1 << 31;
-    if ((int64_t)d->B * d->inH * d->inW * ((d->flags & LOANS_F_DENSE) ? 1 : d->Cin) >= lim) return LOANS_ERANGE;
-    if ((int64_t)d->B * d->outH * d->outW * d->Cout >= lim) return LOANS_ERANGE;
-    if ((int64_t)d->B * d->gridH * d->gridW >= lim) return LOANS_ERANGE;
-    if ((int64_t)d->ntaps * d->Cin * d->Cout >= lim) return LOANS_ERANGE;
-    if (d->flags & LOANS_F_DENSE) {
-        // no bounds masks in this mode: every K-row of every grid pixel has to lie inside its input row
-        for (int t = 0; t < d->ntaps; ++t) {
-            if (d->dy[t] < 0 || d->dx[t] < 0) return LOANS_EINVAL;
-            if ((d->gridH - 1) * d->isy + d->dy[t] >= d->inH) return LOANS_EINVAL;
-            if ((d->gridW - 1) * d->isx + d->dx[t] + d->Cin > d->inW) return LOANS_EINVAL;
-        }
-    }
-    return LOANS_OK;
-}
-
 }  // namespace
 
 struct IgemmPair {       // second convolution of a pair launch
@@ -909,24 +884,10 @@ struct IgemmClasses {    // class launch: descs[0] is `d`, the weights of class 
     const float* const* w;
 };
 
+// the caller has run its entry's check of conv_desc.h
 static int igemm_impl(const float* in, const float* w, float* out, const float* bias, double* stats,
                       const float* ref, const float* addend, const loans_igemm_desc* d, void* stream, int bf16,
                       const IgemmPair* pair = nullptr, const IgemmClasses* mc = nullptr) {
-    int rc = check_desc(d);
-    if (rc) return rc;
-    if (!in || !w || !out || (d->Cout & 3)) return LOANS_EINVAL;
-    if ((d->flags & LOANS_F_BIAS) && !bias) return LOANS_EINVAL;
-    if ((d->flags & LOANS_F_STATS) && !stats) return LOANS_EINVAL;
-    if ((d->flags & (LOANS_F_MASK | LOANS_F_ADDEND_MASK)) && !ref) return LOANS_EINVAL;
-    if ((d->flags & LOANS_F_ADDEND_MASK) && !(d->flags & LOANS_F_ADDEND)) return LOANS_EINVAL;
-    if ((d->flags & LOANS_F_ADDEND) && !addend) return LOANS_EINVAL;
-    if ((d->flags & LOANS_F_OUT_BF16) && (d->flags & (LOANS_F_MASK | LOANS_F_ADDEND | LOANS_F_ADDEND_MASK))) return LOANS_EINVAL;
-    if (d->flags & LOANS_F_BNSUMS) {        // a data gradient's epilogue takes the sums of the BN below it: nothing else rides along
-        if (!ref || !bias || !stats || pair || mc) return LOANS_EINVAL;
-        if (d->flags & (LOANS_F_BIAS | LOANS_F_STATS | LOANS_F_MASK | LOANS_F_ADDEND | LOANS_F_ADDEND_MASK | LOANS_F_DENSE | LOANS_F_OUT_BF16))
-            return LOANS_EINVAL;
-        if ((d->tile & 0xEF) == LOANS_TILE_FINETAIL) return LOANS_EINVAL;
-    }
     IgemmArgs a;
     a.in = in; a.w = w; a.out = out; a.bias = bias; a.stats = stats; a.ref = ref; a.addend = addend;
     a.d = *d;
@@ -942,38 +903,21 @@ static int igemm_impl(const float* in, const float* w, float* out, const float* 
     a.Ktot = d->ntaps * d->Cin;
     a.nchunks = (a.Ktot + BK - 1) / BK;
     a.tail_groups = (a.Ktot - (a.nchunks - 1) * BK + 7) / 8;
-    {
-        const int64_t ib = (int64_t)d->B * d->inH * d->inW * ((d->flags & LOANS_F_DENSE) ? 1 : d->Cin) * 4;
-        const int64_t wb = (int64_t)d->Cout * a.Ktot * 4;
-        const int64_t ob = (int64_t)d->B * d->outH * d->outW * d->Cout * ((d->flags & LOANS_F_OUT_BF16) ? 2 : 4);
-        if (ib >= 0xFFFFFFF0ll || wb >= 0xFFFFFFF0ll || ob >= 0xFFFFFFF0ll) return LOANS_ERANGE;   // 32-bit buffer offsets
-        a.in_bytes = (unsigned)ib;
-        a.w_bytes = (unsigned)wb;
-        a.out_bytes = (unsigned)ob;
-        a.nt_out = loans_conv_nt((size_t)ob);
-    }
+    ConvBytes b;
+    conv_tensor_bytes(d, 4, (d->flags & LOANS_F_OUT_BF16) ? 2 : 4, CONV_BUFFER_LIMIT, &b);
+    a.in_bytes = b.in; a.w_bytes = b.w; a.out_bytes = b.out;
+    a.nt_out = loans_conv_nt(b.out);
     a.cls[0].g = detect_tap_grid(d);
     if (pair) {
-        const int64_t wb2 = (int64_t)pair->Cout * a.Ktot * 4;
-        const int64_t ob2 = (int64_t)d->B * d->outH * d->outW * pair->Cout * 4;
-        if (wb2 >= 0xFFFFFFF0ll || ob2 >= 0xFFFFFFF0ll) return LOANS_ERANGE;
         a.w2 = pair->w; a.out2 = pair->out; a.stats2 = pair->stats; a.Cout2 = pair->Cout;
-        a.w2_bytes = (unsigned)wb2; a.out2_bytes = (unsigned)ob2;
+        a.w2_bytes = (unsigned)((int64_t)pair->Cout * a.Ktot * 4); a.out2_bytes = (unsigned)((int64_t)d->B * d->outH * d->outW * pair->Cout * 4);
     }
     a.ncls = 1;
     if (mc) {
         // the classes differ in their grid, their output phase and their taps; image, strides, channels and flags are shared
-        if (pair || bf16 || mc->n < 2 || mc->n > LOANS_MAX_CLASSES) return LOANS_EINVAL;
-        if (d->flags & (LOANS_F_DENSE | LOANS_F_STATS | LOANS_F_BIAS)) return LOANS_EINVAL;
         a.ncls = mc->n;
         for (int c = 0; c < mc->n; ++c) {
             const loans_igemm_desc* e = mc->descs + c;
-            if ((rc = check_desc(e))) return rc;
-            if (!mc->w[c] || e->ntaps > LOANS_MAX_CLS_TAPS) return LOANS_EINVAL;
-            if (e->B != d->B || e->inH != d->inH || e->inW != d->inW || e->Cin != d->Cin || e->outH != d->outH ||
-                e->outW != d->outW || e->Cout != d->Cout || e->osy != d->osy || e->osx != d->osx || e->isy != d->isy ||
-                e->isx != d->isx || e->flags != d->flags)
-                return LOANS_EINVAL;
             IgemmArgs::Cls& k = a.cls[c];
             k.g = detect_tap_grid(e);
             k.w = mc->w[c];
@@ -989,18 +933,10 @@ static int igemm_impl(const float* in, const float* w, float* out, const float* 
     }
     hipStream_t st = as_stream(stream);
     int tile = d->tile;
-    if (mc) {
-        const int t = tile & ~LOANS_TILE_DMA;
-        if (t != LOANS_TILE_128x128 && t != LOANS_TILE_128x64 && t != LOANS_TILE_64x64 && t != LOANS_TILE_256x64) return LOANS_EINVAL;
-    }
-    if (pair && ((tile >> 8) || (tile & 0xFF) == LOANS_TILE_SPLIT)) return LOANS_EINVAL;
     a.splits = (tile >> 8) & 0xFF;          // LOANS_TILE_SPLITK(s)
     if (a.splits < 1) a.splits = 1;
     tile &= 0xFF;
-    if (a.splits > 1 && (bf16 || (d->flags & ~(LOANS_F_DENSE | LOANS_F_RELU_IN)) || tile == LOANS_TILE_SPLIT))
-        return LOANS_EINVAL;                // raw partial sums only: the epilogue flags belong to loans_igemm_finalize_f32
     a.dma = (tile & LOANS_TILE_DMA) ? 1 : 0;
-    if (a.dma && bf16) return LOANS_EINVAL;
     tile &= ~LOANS_TILE_DMA;
     if (tile == 0) {
         if (d->Cout <= 64) {
@@ -1023,16 +959,14 @@ static int igemm_impl(const float* in, const float* w, float* out, const float* 
         if (rows_big > 0) {
             IgemmArgs b = a;
             b.M = rows_big;
-            rc = launch_igemm<128, 128, 2, 2>(b, st);
-            if (rc) return rc;
+            if (int rc = launch_igemm<128, 128, 2, 2>(b, st)) return rc;
         }
         if (rows_big == a.M) return LOANS_OK;
         a.m_begin = rows_big;
         return launch_igemm<64, 64, 2, 2>(a, st);
     }
     if (tile == LOANS_TILE_STEM) {          // the dense RGB stem as a direct convolution (stem.hip)
-        if (pair || a.splits > 1 || a.dma || mc) return LOANS_EINVAL;
-        if (bf16) return loans_stem7_bf16_launch(in, w, out, bias, stats, d, st);       // needs LOANS_F_OUT_BF16 (checked there)
+        if (bf16) return loans_stem7_bf16_launch(in, w, out, bias, stats, d, st);       // needs LOANS_F_OUT_BF16
         return loans_stem7_launch(in, w, out, bias, stats, d, st);
     }
     if (tile == LOANS_TILE_FINETAIL) {
@@ -1040,11 +974,6 @@ static int igemm_impl(const float* in, const float* w, float* out, const float* 
         // are cut into K-slices behind them in the SAME launch, so that every CU ends with a small unit instead of some CUs
         // with a whole extra tile (res5 at B = 256: 1568 tiles on 256 CUs = 6.125 each -> 6 + 32 tiles x 8 slices).  The
         // sliced tiles' rows are zeroed here, receive raw partial sums and get bias / statistics from the finalize pass.
-        if (pair || bf16 || a.splits > 1) return LOANS_EINVAL;
-        if (d->flags & (LOANS_F_MASK | LOANS_F_ADDEND | LOANS_F_ADDEND_MASK | LOANS_F_OUT_BF16)) return LOANS_EINVAL;
-        if (d->osy != 1 || d->osx != 1 || d->oy0 || d->ox0 || d->outH != d->gridH || d->outW != d->gridW) return LOANS_EINVAL;
-        const int c4 = d->Cout / 4;
-        if ((d->Cout & 3) || !(c4 <= 256 ? (256 % c4 == 0) : (c4 % 256 == 0))) return LOANS_EINVAL;   // finalize's thread map
         const int cus = loans_device_cus();                 // of the current device
         if (cus <= 0) return LOANS_EINVAL;
         const int tiles_n = (d->Cout + 63) / 64, tiles_m = (a.M + 63) / 64;
@@ -1062,8 +991,7 @@ static int igemm_impl(const float* in, const float* w, float* out, const float* 
         if (hipMemsetAsync(tail_out, 0, (size_t)tail_rows * d->Cout * sizeof(float), st) != hipSuccess) return LOANS_EINVAL;
         a.n_full = n_full;
         a.tail_splits = sl;
-        rc = launch_igemm<64, 64, 2, 2>(a, st);
-        if (rc) return rc;
+        if (int rc = launch_igemm<64, 64, 2, 2>(a, st)) return rc;
         const int fin = d->flags & (LOANS_F_BIAS | LOANS_F_STATS);
         return fin ? loans_igemm_finalize_f32(tail_out, bias, stats, nullptr, nullptr, fin, tail_rows, d->Cout, stream) : LOANS_OK;
     }
@@ -1078,12 +1006,17 @@ static int igemm_impl(const float* in, const float* w, float* out, const float* 
 
 extern "C" int loans_igemm_f32(const float* in, const float* w, float* out, const float* bias, double* stats,
                                const float* ref, const float* addend, const loans_igemm_desc* d, void* stream) {
+    if (int rc = conv_check_igemm32(d, conv_have_igemm(in, w, out, bias, stats, ref, addend), conv_misaligned_igemm(in, w, out), 0)) return rc;
     return igemm_impl(in, w, out, bias, stats, ref, addend, d, stream, 0);
 }
 
 extern "C" int loans_igemm_classes_f32(const float* in, const float* const* w, float* out, const float* ref, const float* addend,
                                        const loans_igemm_desc* descs, int32_t n, void* stream) {
-    if (!descs || !w || n < 1) return LOANS_EINVAL;
+    unsigned w_have = 0;
+    for (int c = 0; w && c < n && c < LOANS_MAX_CLASSES; ++c) w_have |= conv_have(w[c], 1u << c);
+    if (int rc = conv_check_igemm_classes_f32(descs, n, conv_have_igemm(in, nullptr, out, nullptr, nullptr, ref, addend),
+                                              conv_misaligned_igemm(in, nullptr, out), w != nullptr, w_have))
+        return rc;
     if (n == 1) return igemm_impl(in, w[0], out, nullptr, nullptr, ref, addend, descs, stream, 0);
     const IgemmClasses mc = {n, descs, w};
     return igemm_impl(in, w[0], out, nullptr, nullptr, ref, addend, descs, stream, 0, nullptr, &mc);
@@ -1091,15 +1024,16 @@ extern "C" int loans_igemm_classes_f32(const float* in, const float* const* w, f
 
 extern "C" int loans_igemm_pair_f32(const float* in, const float* w_a, float* out_a, double* stats_a, const float* w_b,
                                     float* out_b, double* stats_b, int32_t Cout_b, const loans_igemm_desc* d, void* stream) {
-    if (!d || !w_b || !out_b || Cout_b <= 0 || (Cout_b & 3)) return LOANS_EINVAL;
-    if (d->flags & ~(LOANS_F_STATS | LOANS_F_RELU_IN)) return LOANS_EINVAL;
-    if ((d->flags & LOANS_F_STATS) && !stats_b) return LOANS_EINVAL;
+    const unsigned have = conv_have_igemm(in, w_a, out_a, nullptr, stats_a, nullptr, nullptr) | conv_have(w_b, CONV_P_W2) |
+                          conv_have(out_b, CONV_P_OUT2) | conv_have(stats_b, CONV_P_STATS2);
+    if (int rc = conv_check_igemm_pair_f32(d, have, conv_misaligned_igemm(in, w_a, out_a), Cout_b)) return rc;
     const IgemmPair p = {w_b, out_b, stats_b, Cout_b};
     return igemm_impl(in, w_a, out_a, nullptr, stats_a, nullptr, nullptr, d, stream, 0, &p);
 }
 
 extern "C" int loans_igemm_bf16_f32(const float* in, const float* w, float* out, const float* bias, double* stats,
                                     const float* ref, const float* addend, const loans_igemm_desc* d, void* stream) {
+    if (int rc = conv_check_igemm32(d, conv_have_igemm(in, w, out, bias, stats, ref, addend), conv_misaligned_igemm(in, w, out), 1)) return rc;
     return igemm_impl(in, w, out, bias, stats, ref, addend, d, stream, 1);
 }
 
@@ -1429,7 +1363,7 @@ int launch_wgrad_r(WgradArgs& a, int splits_req, hipStream_t st) {
 template <int BCO, int BJ>
 int launch_wgrad(WgradArgs& a, int splits_req, hipStream_t st) {
     const bool relu = a.d.flags & LOANS_F_RELU_IN;
-    if (a.d.flags & LOANS_F_GY_BF16) return (relu || !a.bf16) ? LOANS_EINVAL : launch_wgrad_r<BCO, BJ, false, true, true>(a, splits_req, st);
+    if (a.d.flags & LOANS_F_GY_BF16) return launch_wgrad_r<BCO, BJ, false, true, true>(a, splits_req, st);      // (not with relu, bf16 arm only)
     if (a.bf16) return relu ? launch_wgrad_r<BCO, BJ, true, true>(a, splits_req, st) : launch_wgrad_r<BCO, BJ, false, true>(a, splits_req, st);
     return relu ? launch_wgrad_r<BCO, BJ, true, false>(a, splits_req, st) : launch_wgrad_r<BCO, BJ, false, false>(a, splits_req, st);
 }
@@ -1463,9 +1397,10 @@ __global__ __launch_bounds__(256) void repack_dgrad_kernel(const RepackArgs a) {
 
 static int wgrad_impl(const float* x, const float* gy, float* dw, const loans_igemm_desc* d, int32_t splits,
                       void* stream, int bf16) {
-    int rc = check_desc(d);
-    if (rc) return rc;
-    if (!x || !gy || !dw || (d->Cout & 3)) return LOANS_EINVAL;
+    ConvBytes b;
+    if (int rc = conv_check_wgrad32(d, conv_have(x, CONV_P_X) | conv_have(gy, CONV_P_GY) | conv_have(dw, CONV_P_DW),
+                                    conv_misaligned(x, CONV_P_X) | conv_misaligned(gy, CONV_P_GY), bf16, &b))
+        return rc;
     WgradArgs a;
     a.x = x; a.gy = gy; a.dw = dw; a.d = *d;
     a.bf16 = bf16;
@@ -1475,23 +1410,17 @@ static int wgrad_impl(const float* x, const float* gy, float* dw, const loans_ig
 #endif
     a.M = d->B * d->gridH * d->gridW;
     a.Ktot = d->ntaps * d->Cin;
-    {
-        const int64_t xb = (int64_t)d->B * d->inH * d->inW * ((d->flags & LOANS_F_DENSE) ? 1 : d->Cin) * 4;
-        const int64_t gb = (int64_t)d->B * d->outH * d->outW * d->Cout * ((d->flags & LOANS_F_GY_BF16) ? 2 : 4);
-        if (xb >= 0xFFFFFFF0ll || gb >= 0xFFFFFFF0ll) return LOANS_ERANGE;
-        a.x_bytes = (unsigned)xb;
-        a.gy_bytes = (unsigned)gb;
-    }
+    a.x_bytes = b.in; a.gy_bytes = b.out;
     hipStream_t st = as_stream(stream);
     const bool small = (d->Cout <= 64) || (a.Ktot <= 64);
     int tile = d->tile;
     if (tile == 0) tile = small ? LOANS_TILE_64x64 : LOANS_TILE_128x128;
-    if (tile == LOANS_TILE_STEM) return bf16 ? LOANS_EINVAL : loans_stem7_wgrad_launch(x, gy, dw, d, st);     // direct (stem.hip)
+    if (tile == LOANS_TILE_STEM) return loans_stem7_wgrad_launch(x, gy, dw, d, st);     // direct (stem.hip)
     if (tile == LOANS_TILE_64x64) return launch_wgrad<64, 64>(a, splits, st);
     if (tile == LOANS_TILE_128x128) return launch_wgrad<128, 128>(a, splits, st);
     if (tile == LOANS_TILE_64x128) return launch_wgrad<64, 128>(a, splits, st);
     if (tile == LOANS_TILE_WGHALO_64)       // all nine taps of a stride-1 3 x 3 layer in one block (wgrad_halo_f32.hip)
-        return bf16 ? LOANS_EINVAL : loans_wgrad_halo32_launch(x, gy, dw, d, splits, a.x_bytes, a.gy_bytes, st);
+        return loans_wgrad_halo32_launch(x, gy, dw, d, splits, a.x_bytes, a.gy_bytes, st);
     return LOANS_EINVAL;
 }
 

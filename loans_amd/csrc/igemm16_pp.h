@@ -487,9 +487,8 @@ int launch_igemm16pp_r(Igemm16Args& a, hipStream_t st) {
     return LOANS_OK;
 }
 
-// not for LOANS_F_DENSE (the packed RGB stem: 4-byte aligned units, no tap masks) nor for raw partial tiles (split-K)
+// not for LOANS_F_DENSE (the packed RGB stem: 4-byte aligned units, no tap masks) nor for raw partial tiles (split-K): conv_check_igemm16
 template <bool M16>
 int launch_igemm16pp(Igemm16Args& a, hipStream_t st) {
-    if ((a.d.flags & LOANS_F_DENSE) || a.partial) return LOANS_EINVAL;
     return (a.d.flags & LOANS_F_RELU_IN) ? launch_igemm16pp_r<true, M16>(a, st) : launch_igemm16pp_r<false, M16>(a, st);
 }

@@ -943,44 +943,10 @@ int launch_wgrad16(Wgrad16Args& a, int splits_req, hipStream_t st) {
 
 }  // namespace
 
+// the caller has run its entry's check of conv_desc.h
 static int igemm_bf16s_impl(const void* in, const void* w, void* out, const float* bias, double* stats, const void* ref,
                            const void* addend, const loans_igemm_desc* d, float* partial, int splits, void* stream,
                            double* pair_stats = nullptr, bool pair = false) {
-    if (!d || !in || !w || (!out && !partial)) return LOANS_EINVAL;
-    if (partial && (d->flags & ~(LOANS_F_RELU_IN | LOANS_F_DENSE))) return LOANS_EINVAL;      // raw partial sums only
-    if (d->B <= 0 || d->inH <= 0 || d->inW <= 0 || d->Cin <= 0 || (d->Cin & 7)) return LOANS_EINVAL;
-    if (d->outH <= 0 || d->outW <= 0 || d->Cout <= 0 || (d->Cout & 7)) return LOANS_EINVAL;
-    if (d->gridH <= 0 || d->gridW <= 0 || d->osy <= 0 || d->osx <= 0 || d->isy <= 0 || d->isx <= 0) return LOANS_EINVAL;
-    if (d->oy0 < 0 || d->ox0 < 0) return LOANS_EINVAL;
-    if ((d->gridH - 1) * d->osy + d->oy0 >= d->outH) return LOANS_EINVAL;
-    if ((d->gridW - 1) * d->osx + d->ox0 >= d->outW) return LOANS_EINVAL;
-    if (d->ntaps < 1 || d->ntaps > LOANS_MAX_TAPS) return LOANS_EINVAL;
-    const bool dense = d->flags & LOANS_F_DENSE;
-    if (!dense && d->ntaps > 32) return LOANS_EINVAL;       // the kernel keeps one 32-bit tap mask per tile row
-    if (dense) {
-        // no bounds masks in this mode: every K-row of every grid pixel has to lie inside its input row; rows and row
-        // steps must keep the 16-byte loads 4-byte aligned (even element counts)
-        if ((d->inW & 1) || (d->isx & 1)) return LOANS_EINVAL;
-        for (int t = 0; t < d->ntaps; ++t) {
-            if (d->dy[t] < 0 || d->dx[t] < 0 || (d->dx[t] & 1)) return LOANS_EINVAL;
-            if ((d->gridH - 1) * d->isy + d->dy[t] >= d->inH) return LOANS_EINVAL;
-            if ((d->gridW - 1) * d->isx + d->dx[t] + d->Cin > d->inW) return LOANS_EINVAL;
-        }
-    }
-    if ((d->flags & LOANS_F_BIAS) && !bias) return LOANS_EINVAL;
-    // the BN + ReLU in front of the convolution on load: the VGPR-fed 1 x 1 kernels only, `bias` = its [scale | shift]
-    if ((d->flags & LOANS_F_AFFINE_IN) && (d->tile != LOANS_TILE_PW || !bias || partial || pair || (d->flags & ~(LOANS_F_AFFINE_IN | LOANS_F_STATS))))
-        return LOANS_EINVAL;
-    if ((d->flags & LOANS_F_STATS) && !stats) return LOANS_EINVAL;
-    if (d->flags & LOANS_F_BNSUMS) {        // a data gradient's epilogue takes the sums of the BN below it: nothing else rides along
-        if (!ref || !bias || !stats || partial || pair) return LOANS_EINVAL;
-        if (d->flags & (LOANS_F_BIAS | LOANS_F_STATS | LOANS_F_MASK | LOANS_F_ADDEND | LOANS_F_ADDEND_MASK | LOANS_F_DENSE)) return LOANS_EINVAL;
-    }
-    if ((d->flags & (LOANS_F_MASK | LOANS_F_ADDEND_MASK)) && !ref) return LOANS_EINVAL;
-    if ((d->flags & LOANS_F_ADDEND_MASK) && !(d->flags & LOANS_F_ADDEND)) return LOANS_EINVAL;
-    if ((d->flags & LOANS_F_ADDEND) && !addend) return LOANS_EINVAL;
-    const int64_t lim = (int64_t)1 << 31;
-    if ((int64_t)d->B * d->gridH * d->gridW >= lim) return LOANS_ERANGE;
     Igemm16Args a;
     a.in = static_cast<const __bf16*>(in); a.w = static_cast<const __bf16*>(w); a.out = static_cast<__bf16*>(out);
     a.bias = bias; a.stats = stats;
@@ -995,22 +961,16 @@ static int igemm_bf16s_impl(const void* in, const void* w, void* out, const floa
     a.partial = partial;
     a.csplit = 0; a.out_c = d->Cout; a.tensor_bytes = 0; a.stats2 = nullptr;
     if (pair) {                 // `d` describes the stacked GEMM: Cout = 2 x the channels of either convolution
-        if (partial || (d->Cout & 63) || (d->flags & ~(LOANS_F_STATS | LOANS_F_RELU_IN))) return LOANS_EINVAL;
-        if ((d->flags & LOANS_F_STATS) && !pair_stats) return LOANS_EINVAL;
         a.csplit = a.out_c = d->Cout / 2;
         a.stats2 = pair_stats;
     }
     a.splits = partial ? splits : 1;
     a.nchunks = (a.Ktot + BKH - 1) / BKH;
-    {
-        const int64_t ib = (int64_t)d->B * d->inH * d->inW * (dense ? 1 : d->Cin) * 2;
-        const int64_t wb = (int64_t)d->Cout * a.Ktot * 2;
-        const int64_t ob = (int64_t)d->B * d->outH * d->outW * d->Cout * 2;
-        if (ib >= 0xFFFFFFF0ll || wb >= 0xFFFFFFF0ll || ob >= 0xFFFFFFF0ll) return LOANS_ERANGE;   // 32-bit buffer offsets
-        a.in_bytes = (unsigned)ib; a.w_bytes = (unsigned)wb; a.out_bytes = (unsigned)ob;
-        a.nt_out = loans_conv_nt((size_t)ob);
-        if (pair) a.tensor_bytes = (unsigned)(ob / 2);
-    }
+    ConvBytes b;
+    conv_tensor_bytes(d, 2, 2, CONV_BUFFER_LIMIT, &b);
+    a.in_bytes = b.in; a.w_bytes = b.w; a.out_bytes = b.out;
+    a.nt_out = loans_conv_nt(b.out);
+    if (pair) a.tensor_bytes = b.out / 2;
     a.g = detect_tap_grid(d);
     hipStream_t st = as_stream(stream);
     int tile = d->tile;
@@ -1018,17 +978,10 @@ static int igemm_bf16s_impl(const void* in, const void* w, void* out, const floa
         const int64_t big = (int64_t)((a.M + 127) / 128) * ((d->Cout + 127) / 128);
         tile = d->Cout <= 64 ? LOANS_TILE_128x64 : (big >= 512 ? LOANS_TILE_128x128 : LOANS_TILE_64x64);
     }
-    const bool halo_tile = (tile >= LOANS_TILE_HALO_128 && tile <= LOANS_TILE_WS64) || tile == LOANS_TILE_HALO_256x128 || tile == LOANS_TILE_HALO_256x256 || tile == LOANS_TILE_WSW64;
-    if (partial && halo_tile) return LOANS_EINVAL;          // the halo tiles have no split-K form
-    if (pair && (tile == LOANS_TILE_STEM || halo_tile)) return LOANS_EINVAL;
-    if (tile == LOANS_TILE_STEM) {          // the dense RGB stem as a direct convolution (stem.hip)
-        if (partial || splits > 1) return LOANS_EINVAL;
-        return loans_stem7_bf16s_launch(in, w, out, bias, stats, d, st);
-    }
-    if (tile == LOANS_TILE_PW) {            // short-K 1 x 1 convolutions, operands never in LDS (pw_bf16.hip); w in fragment order
-        if (partial || splits > 1 || pair) return LOANS_EINVAL;
+    if (tile == LOANS_TILE_STEM)            // the dense RGB stem as a direct convolution (stem.hip)
+        return loans_stem7_bf16_launch(static_cast<const __bf16*>(in), static_cast<const __bf16*>(w), out, bias, stats, d, st);
+    if (tile == LOANS_TILE_PW)              // short-K 1 x 1 convolutions, operands never in LDS (pw_bf16.hip); w in fragment order
         return loans_pw16_launch(in, w, out, stats, (d->flags & LOANS_F_AFFINE_IN) ? bias : nullptr, d, st);
-    }
     switch (tile) {
         case LOANS_TILE_128x128: return launch_igemm16<128, 128, 2, 2>(a, st);
         case LOANS_TILE_128x64: return launch_igemm16<128, 64, 2, 2>(a, st);
@@ -1041,36 +994,31 @@ static int igemm_bf16s_impl(const void* in, const void* w, void* out, const floa
         case LOANS_TILE_256x256: return launch_igemm16<256, 256, 2, 4>(a, st);      // 512 threads: eight 128 x 64 wave tiles
         case LOANS_TILE_256x256PP: return launch_igemm16pp<false>(a, st);           // the same tile, wave rows half a phase apart
         case LOANS_TILE_256x256PP16: return launch_igemm16pp<true>(a, st);          // ... on v_mfma_f32_16x16x32_bf16
-        case LOANS_TILE_HALO_128:
-        case LOANS_TILE_HALO_128x64:
-        case LOANS_TILE_HALO_256x64:
-        case LOANS_TILE_HALO_128x64S:
-        case LOANS_TILE_HALO_256x128:
-        case LOANS_TILE_HALO_256x256:
-        case LOANS_TILE_WSW64:
-        case LOANS_TILE_WS64:
-            return loans_halo16_launch(in, w, out, bias, stats, ref, addend, d, tile, a.in_bytes, a.w_bytes, a.out_bytes, st);
+        case LOANS_TILE_HALO_128: case LOANS_TILE_HALO_128x64: case LOANS_TILE_HALO_256x64: case LOANS_TILE_HALO_128x64S:
+        case LOANS_TILE_HALO_256x128: case LOANS_TILE_HALO_256x256: case LOANS_TILE_WSW64: case LOANS_TILE_WS64:
+            return loans_halo16_launch(in, w, out, bias, stats, ref, addend, d, tile, a.g, a.in_bytes, a.w_bytes, a.out_bytes, st);
         default: return LOANS_EINVAL;
     }
 }
 
 extern "C" int loans_igemm_bf16s(const void* in, const void* w, void* out, const float* bias, double* stats,
                                  const void* ref, const void* addend, const loans_igemm_desc* d, void* stream) {
-    if (!out) return LOANS_EINVAL;
+    if (int rc = conv_check_igemm16(d, conv_have_igemm(in, w, out, bias, stats, ref, addend), conv_misaligned_igemm(in, w, out))) return rc;
     return igemm_bf16s_impl(in, w, out, bias, stats, ref, addend, d, nullptr, 1, stream);
 }
 
 extern "C" int loans_igemm_pair_bf16s(const void* in, const void* w_ab, void* out_ab, double* stats_a, double* stats_b,
                                       const loans_igemm_desc* d, void* stream) {
-    if (!d || !out_ab || d->Cout <= 0 || (d->Cout & 31)) return LOANS_EINVAL;
-    loans_igemm_desc d2 = *d;
-    d2.Cout = 2 * d->Cout;
+    loans_igemm_desc d2;
+    const unsigned have = conv_have_igemm(in, w_ab, out_ab, nullptr, stats_a, nullptr, nullptr) | conv_have(stats_b, CONV_P_STATS2);
+    if (int rc = conv_check_igemm_pair_bf16s(d, have, conv_misaligned_igemm(in, w_ab, out_ab), &d2)) return rc;
     return igemm_bf16s_impl(in, w_ab, out_ab, nullptr, stats_a, nullptr, nullptr, &d2, nullptr, 1, stream, stats_b, true);
 }
 
 extern "C" int loans_igemm_bf16s_splitk(const void* in, const void* w, float* partial, const loans_igemm_desc* d, int32_t splits,
                                         void* stream) {
-    if (!partial || splits < 1 || splits > 64) return LOANS_EINVAL;
+    const unsigned have = conv_have_igemm(in, w, nullptr, nullptr, nullptr, nullptr, nullptr) | conv_have(partial, CONV_P_PARTIAL);
+    if (int rc = conv_check_igemm16(d, have, conv_misaligned_igemm(in, w, nullptr), splits)) return rc;
     return igemm_bf16s_impl(in, w, nullptr, nullptr, nullptr, nullptr, nullptr, d, partial, splits, stream);
 }
 
@@ -1151,18 +1099,11 @@ __global__ __launch_bounds__(256) void igemm16_finalize_kernel(const float* part
 // carry no statistics).
 extern "C" int loans_igemm_finalize_bf16(const float* partial, void* out, const float* bias, double* stats, const void* ref,
                                          const void* addend, int32_t flags, int64_t rows, int32_t Cout, void* stream) {
-    if (!partial || !out || rows <= 0 || Cout <= 0 || (Cout & 7)) return LOANS_EINVAL;
-    const int C8 = Cout / 8;
-    if (C8 > 256 || 256 % C8) return LOANS_EINVAL;          // the thread map: Cout / 8 divides 256
-    if ((flags & LOANS_F_BIAS) && !bias) return LOANS_EINVAL;
-    if ((flags & LOANS_F_STATS) && !stats) return LOANS_EINVAL;
-    if ((flags & (LOANS_F_MASK | LOANS_F_ADDEND_MASK)) && !ref) return LOANS_EINVAL;
-    if ((flags & LOANS_F_ADDEND) && !addend) return LOANS_EINVAL;
-    if (flags & ~(LOANS_F_BIAS | LOANS_F_STATS | LOANS_F_MASK | LOANS_F_ADDEND | LOANS_F_ADDEND_MASK)) return LOANS_EINVAL;
-    const int RL = 256 / C8;
-    int rows_per_block = RL * 8;
-    const int64_t nblk = (rows + rows_per_block - 1) / rows_per_block;
-    if (nblk >= ((int64_t)1 << 31)) return LOANS_ERANGE;
+    int64_t nblk = 0;
+    if (int rc = conv_check_finalize_bf16(conv_have_igemm(nullptr, nullptr, out, bias, stats, ref, addend) | conv_have(partial, CONV_P_PARTIAL),
+                                          flags, rows, Cout, &nblk))
+        return rc;
+    const int C8 = Cout / 8, rows_per_block = 256 / C8 * 8;
     hipLaunchKernelGGL(igemm16_finalize_kernel, dim3((unsigned)nblk), dim3(256), 0, as_stream(stream), partial,
                        static_cast<__bf16*>(out), bias, stats, static_cast<const __bf16*>(ref),
                        static_cast<const __bf16*>(addend), flags, rows, C8, rows_per_block);
@@ -1197,60 +1138,26 @@ extern "C" int loans_repack_dgrad_bf16(const float* src, void* dst, int32_t Cout
 // One implementation behind loans_wgrad_bf16s (atomics into dw), loans_wgrad_bf16s_ws (partial slabs + fold) and
 // loans_wgrad_bf16s_ws_floats (plan only: *need = floats of workspace the request takes, nothing is launched)
 static int wgrad_bf16s_impl(const void* x, const void* gy, float* dw, const loans_igemm_desc* d, int32_t splits, float* ws,
-                            int64_t ws_floats, int64_t* need, void* stream, const float* affine = nullptr) {
+                            int64_t ws_floats, int64_t* need, void* stream, const float* affine = nullptr, bool need_ws = false,
+                            bool need_affine = false) {
     const bool plan_only = need != nullptr;
-    if (!d || (!plan_only && (!x || !gy || !dw))) return LOANS_EINVAL;
-    if (d->B <= 0 || d->inH <= 0 || d->inW <= 0 || d->Cin <= 0 || (d->Cin & 7)) return LOANS_EINVAL;
-    if (d->outH <= 0 || d->outW <= 0 || d->Cout <= 0 || (d->Cout & 7)) return LOANS_EINVAL;
-    if (d->gridH <= 0 || d->gridW <= 0 || d->osy <= 0 || d->osx <= 0 || d->isy <= 0 || d->isx <= 0) return LOANS_EINVAL;
-    if (d->oy0 < 0 || d->ox0 < 0) return LOANS_EINVAL;
-    if ((d->gridH - 1) * d->osy + d->oy0 >= d->outH) return LOANS_EINVAL;
-    if ((d->gridW - 1) * d->osx + d->ox0 >= d->outW) return LOANS_EINVAL;
-    if (d->ntaps < 1 || d->ntaps > LOANS_MAX_TAPS) return LOANS_EINVAL;
-    // the kernel reads the gradient at grid pixel m itself and keeps the input offset incrementally with 24-bit multiplies
-    if (d->osy != 1 || d->osx != 1 || d->oy0 || d->ox0 || d->outH != d->gridH || d->outW != d->gridW) return LOANS_EINVAL;
-    {
-        const int64_t uc = (d->flags & LOANS_F_DENSE) ? 1 : d->Cin;
-        const int64_t xr = ((int64_t)d->isy * d->inW - (int64_t)d->isx * d->gridW) * uc * 2;
-        const int64_t xi = ((int64_t)d->inH - (int64_t)d->isy * d->gridH) * d->inW * uc * 2;
-        const int64_t lim24 = (int64_t)1 << 23;
-        if (xr <= -lim24 || xr >= lim24 || xi <= -lim24 || xi >= lim24) return LOANS_ERANGE;
-        if (d->gridW >= lim24 || d->gridH >= lim24) return LOANS_ERANGE;
-    }
-    const bool dense = d->flags & LOANS_F_DENSE;
-    if (dense) {            // as in loans_igemm_bf16s
-        if ((d->inW & 1) || (d->isx & 1)) return LOANS_EINVAL;
-        for (int t = 0; t < d->ntaps; ++t) {
-            if (d->dy[t] < 0 || d->dx[t] < 0 || (d->dx[t] & 1)) return LOANS_EINVAL;
-            if ((d->gridH - 1) * d->isy + d->dy[t] >= d->inH) return LOANS_EINVAL;
-            if ((d->gridW - 1) * d->isx + d->dx[t] + d->Cin > d->inW) return LOANS_EINVAL;
-        }
-    }
-    if ((int64_t)d->B * d->gridH * d->gridW >= ((int64_t)1 << 31)) return LOANS_ERANGE;
+    const unsigned have = conv_have(x, CONV_P_X) | conv_have(gy, CONV_P_GY) | conv_have(dw, CONV_P_DW) | conv_have(ws, CONV_P_WS) |
+                          conv_have(affine, CONV_P_AFFINE);
+    const unsigned misaligned = conv_misaligned(x, CONV_P_X) | conv_misaligned(gy, CONV_P_GY) | conv_misaligned(ws, CONV_P_WS);
+    ConvBytes b;
+    if (int rc = conv_check_wgrad_bf16s(d, have, misaligned, plan_only, need_ws, need_affine, &b)) return rc;
     Wgrad16Args a;
     a.x = static_cast<const __bf16*>(x); a.gy = static_cast<const __bf16*>(gy); a.dw = dw; a.d = *d;
     a.M = d->B * d->gridH * d->gridW;
     a.Ktot = d->ntaps * d->Cin;
     a.ws = nullptr;
     a.slab = (int64_t)d->Cout * a.Ktot;
-    a.affine = nullptr;
-    if (d->flags & LOANS_F_AFFINE_IN) {     // 1 x 1 / 1 convolutions on the GEMM tiles only; x = the BN's input, affine = [scale | shift][Cin]
-        if (plan_only) { /* the slab count does not depend on it */ }
-        else if (!affine) return LOANS_EINVAL;
-        if (d->ntaps != 1 || d->dy[0] != 0 || d->dx[0] != 0 || d->isy != 1 || d->isx != 1 || (d->flags & ~LOANS_F_AFFINE_IN)) return LOANS_EINVAL;
-        a.affine = affine;
-    }
-    {
-        const int64_t xb = (int64_t)d->B * d->inH * d->inW * (dense ? 1 : d->Cin) * 2;
-        const int64_t gb = (int64_t)d->B * d->outH * d->outW * d->Cout * 2;
-        if (xb >= 0xFFFFFFF0ll || gb >= 0xFFFFFFF0ll) return LOANS_ERANGE;
-        a.x_bytes = (unsigned)xb; a.gy_bytes = (unsigned)gb;
-    }
+    a.affine = (d->flags & LOANS_F_AFFINE_IN) ? affine : nullptr;   // 1 x 1 / 1 convolutions on the GEMM tiles only; x = the BN's input, affine = [scale | shift][Cin]
+    a.x_bytes = b.in; a.gy_bytes = b.out;
     hipStream_t st = as_stream(stream);
     int tile = d->tile;
     if (tile == 0) tile = (d->Cout <= 64) ? (a.Ktot <= 64 ? LOANS_TILE_64x64 : LOANS_TILE_64x128) : LOANS_TILE_128x128;
     const bool halo = tile == LOANS_TILE_WGHALO_64 || tile == LOANS_TILE_WGHALO_128;
-    if (halo && (d->flags & LOANS_F_AFFINE_IN)) return LOANS_EINVAL;
     if (tile == LOANS_TILE_STEM) {          // the dense RGB stem's weight gradient as a direct kernel (stem.hip): one slab per block
         const int slabs = loans_stem7_wgrad_bf16_slabs(d);
         if (slabs < 1) return LOANS_EINVAL;
@@ -1292,14 +1199,12 @@ extern "C" int loans_wgrad_bf16s(const void* x, const void* gy, float* dw, const
 
 extern "C" int loans_wgrad_bf16s_ws(const void* x, const void* gy, float* dw, const loans_igemm_desc* d, int32_t splits,
                                     float* ws, int64_t ws_floats, void* stream) {
-    if (!ws) return LOANS_EINVAL;
-    return wgrad_bf16s_impl(x, gy, dw, d, splits, ws, ws_floats, nullptr, stream);
+    return wgrad_bf16s_impl(x, gy, dw, d, splits, ws, ws_floats, nullptr, stream, nullptr, true);
 }
 
 extern "C" int loans_wgrad_bf16s_affine_ws(const void* x, const void* gy, float* dw, const loans_igemm_desc* d, int32_t splits,
                                            float* ws, int64_t ws_floats, const float* affine, void* stream) {
-    if (!ws || !affine || !d || !(d->flags & LOANS_F_AFFINE_IN)) return LOANS_EINVAL;
-    return wgrad_bf16s_impl(x, gy, dw, d, splits, ws, ws_floats, nullptr, stream, affine);
+    return wgrad_bf16s_impl(x, gy, dw, d, splits, ws, ws_floats, nullptr, stream, affine, true, true);
 }
 
 extern "C" int64_t loans_wgrad_bf16s_ws_floats(const loans_igemm_desc* d, int32_t splits) {

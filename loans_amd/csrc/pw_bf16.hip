@@ -313,22 +313,6 @@ extern "C" int loans_pw_pack_batch_f32(const loans_pw_pack_job* jobs_dev, int32_
     return LOANS_OK;
 }
 
-// what LOANS_TILE_PW covers: a 1 x 1 / 1 forward geometry (grid = input = output pixels), Cin in {64, 128} with Cout a multiple of 64
-// up to 512, or Cin = 256 with Cout a multiple of 128 up to 1024; flags STATS or none
-int loans_pw16_covers(const loans_igemm_desc* d) {
-    if (d->ntaps != 1 || d->dy[0] != 0 || d->dx[0] != 0) return 0;
-    if (d->isy != 1 || d->isx != 1 || d->osy != 1 || d->osx != 1 || d->oy0 != 0 || d->ox0 != 0) return 0;
-    if (d->gridH != d->inH || d->gridW != d->inW || d->gridH != d->outH || d->gridW != d->outW) return 0;
-    if (d->Cin == 256) {
-        if (d->Cout % 128 != 0 || d->Cout < 128 || d->Cout > 1024) return 0;
-    } else {
-        if (d->Cin != 64 && d->Cin != 128) return 0;
-        if (d->Cout % 64 != 0 || d->Cout < 64 || d->Cout > 512) return 0;
-    }
-    if (d->flags & ~(LOANS_F_STATS | LOANS_F_AFFINE_IN)) return 0;
-    return 1;
-}
-
 template <int K, int NC, bool STATS, int OCC, bool AFF>
 static int pw16_launch_n(const void* in, const void* w, void* out, double* stats, int M, int N, int nt_out, const float* aff, hipStream_t st) {
     static loans_device_once lds_limit_set;
@@ -384,18 +368,12 @@ static int pw16_launch_aff(const void* in, const void* w, void* out, double* stp
     return stp ? pw16_launch_k<128, true, AFF>(in, w, out, stp, M, N, nt_out, aff, st) : pw16_launch_k<128, false, AFF>(in, w, out, stp, M, N, nt_out, aff, st);
 }
 
-// aff: float[2][Cin] = scale, shift (LOANS_F_AFFINE_IN), else ignored
+// aff: float[2][Cin] = scale, shift (LOANS_F_AFFINE_IN), else ignored; the caller (loans_igemm_bf16s) has run conv_check_pw16
 int loans_pw16_launch(const void* in, const void* w, void* out, double* stats, const float* aff, const loans_igemm_desc* d, hipStream_t st) {
-    if (!loans_pw16_covers(d)) return LOANS_EINVAL;
-    const int64_t M64 = (int64_t)d->B * d->gridH * d->gridW;
-    if (M64 <= 0 || M64 > 0x7FFFFFFF - 64) return LOANS_ERANGE;
-    const int M = (int)M64, N = d->Cout;
+    const int M = d->B * d->gridH * d->gridW, N = d->Cout;
     double* stp = (d->flags & LOANS_F_STATS) ? stats : nullptr;
     const int nt_out = loans_conv_nt((size_t)M * N * 2);
-    if ((d->flags & LOANS_F_STATS) && !stats) return LOANS_EINVAL;
-    if (d->flags & LOANS_F_AFFINE_IN) {
-        if (!aff) return LOANS_EINVAL;
+    if (d->flags & LOANS_F_AFFINE_IN)
         return pw16_launch_aff<true>(in, w, out, stp, d, M, N, nt_out, aff, st);
-    }
     return pw16_launch_aff<false>(in, w, out, stp, d, M, N, nt_out, nullptr, st);
 }

@@ -676,21 +676,10 @@ int loans_stem7_bf16_rows(int Ho, int Wo, int Wp3, size_t* lds_bytes) {
     return 0;
 }
 
-namespace {
+// LOANS_TILE_STEM of loans_igemm_bf16_f32 (TIN = float: fp32 frame buffer and weights; LOANS_F_OUT_BF16 required: the output is bf16)
+// and of loans_igemm_bf16s (TIN = __bf16).  The descriptor rules of the four stem launchers: conv_check_stem7 (conv_desc.h), run by the entries
 template <typename TIN>
-int stem7_bf16_launch(const TIN* in, const TIN* w, void* out, const float* bias, double* stats, const loans_igemm_desc* d,
-                      hipStream_t st) {
-    if (!(d->flags & LOANS_F_DENSE) || (d->flags & ~(LOANS_F_DENSE | LOANS_F_OUT_BF16 | LOANS_F_BIAS | LOANS_F_STATS))) return LOANS_EINVAL;
-    if (d->ntaps != 7 || d->Cin != 24 || d->Cout != 64 || d->isy != 2 || d->isx != 6) return LOANS_EINVAL;
-    if ((d->inW & 1) || (d->inH & 1) || (reinterpret_cast<uintptr_t>(in) & 15) || (reinterpret_cast<uintptr_t>(w) & 15) ||
-        (reinterpret_cast<uintptr_t>(out) & 15))
-        return LOANS_EINVAL;
-    for (int t = 0; t < 7; ++t)
-        if (d->dy[t] != t || d->dx[t] != 0) return LOANS_EINVAL;
-    if (d->osy != 1 || d->osx != 1 || d->oy0 || d->ox0 || d->outH != d->gridH || d->outW != d->gridW) return LOANS_EINVAL;
-    if (2 * (d->gridH - 1) + 7 > d->inH || 6 * (d->gridW - 1) + 24 > d->inW) return LOANS_EINVAL;
-    if ((int64_t)d->B * d->inH * d->inW >= ((int64_t)1 << 31) || (int64_t)d->B * d->gridH * d->gridW * 64 >= ((int64_t)1 << 31))
-        return LOANS_ERANGE;
+int loans_stem7_bf16_launch(const TIN* in, const TIN* w, void* out, const float* bias, double* stats, const loans_igemm_desc* d, hipStream_t st) {
     size_t lds = 0;
     const int R = loans_stem7_bf16_rows(d->gridH, d->gridW, d->inW, &lds);
     if (!R) return LOANS_EINVAL;
@@ -708,39 +697,17 @@ int stem7_bf16_launch(const TIN* in, const TIN* w, void* out, const float* bias,
     LOANS_LAUNCH_CHECK();
     return LOANS_OK;
 }
-}  // namespace
-
-// LOANS_TILE_STEM of loans_igemm_bf16_f32 (fp32 frame buffer and weights; LOANS_F_OUT_BF16 required: the output is bf16)
-int loans_stem7_bf16_launch(const float* in, const float* w, void* out, const float* bias, double* stats,
-                            const loans_igemm_desc* d, hipStream_t st) {
-    if (!(d->flags & LOANS_F_OUT_BF16)) return LOANS_EINVAL;
-    return stem7_bf16_launch<float>(in, w, out, bias, stats, d, st);
-}
-
-// LOANS_TILE_STEM of loans_igemm_bf16s (bf16 frame buffer and weights)
-int loans_stem7_bf16s_launch(const void* in, const void* w, void* out, const float* bias, double* stats,
-                             const loans_igemm_desc* d, hipStream_t st) {
-    if (d->flags & LOANS_F_OUT_BF16) return LOANS_EINVAL;       // implied there
-    return stem7_bf16_launch<__bf16>(reinterpret_cast<const __bf16*>(in), reinterpret_cast<const __bf16*>(w), out, bias, stats, d, st);
-}
+template int loans_stem7_bf16_launch<float>(const float*, const float*, void*, const float*, double*, const loans_igemm_desc*, hipStream_t);
+template int loans_stem7_bf16_launch<__bf16>(const __bf16*, const __bf16*, void*, const float*, double*, const loans_igemm_desc*, hipStream_t);
 
 // LOANS_TILE_STEM of loans_wgrad_f32: `d` is the dense 7x7 / 2, Cout = 64 forward geometry; dw [64][7][24] (+=; the three
 // window-padding columns of every row are left alone)
 int loans_stem7_wgrad_launch(const float* x, const float* gy, float* dw, const loans_igemm_desc* d, hipStream_t st) {
-    if (d->flags != LOANS_F_DENSE) return LOANS_EINVAL;
-    if (d->ntaps != 7 || d->Cin != 24 || d->Cout != 64 || d->isy != 2 || d->isx != 6) return LOANS_EINVAL;
-    if ((d->inW & 1) || (d->inH & 1) || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(gy) & 15)) return LOANS_EINVAL;
-    for (int t = 0; t < 7; ++t)
-        if (d->dy[t] != t || d->dx[t] != 0) return LOANS_EINVAL;
-    if (d->osy != 1 || d->osx != 1 || d->oy0 || d->ox0 || d->outH != d->gridH || d->outW != d->gridW) return LOANS_EINVAL;
-    if (2 * (d->gridH - 1) + 7 > d->inH || 6 * (d->gridW - 1) + 24 > d->inW) return LOANS_EINVAL;
-    if ((int64_t)d->B * d->inH * d->inW >= ((int64_t)1 << 31) || (int64_t)d->B * d->gridH * d->gridW * 64 >= ((int64_t)1 << 31))
-        return LOANS_ERANGE;
     size_t lds = (size_t)2 * (swg_x_pieces(d->inW) + swg_g_pieces(d->gridW)) * 1024;
     if (lds < (size_t)SWG_NW * 32 * 33 * sizeof(float)) lds = (size_t)SWG_NW * 32 * 33 * sizeof(float);
     if (lds > 156 * 1024) return LOANS_EINVAL;
-    const int64_t xb = (int64_t)d->B * d->inH * d->inW * 4, gb = (int64_t)d->B * d->gridH * d->gridW * 256;
-    if (xb >= 0xFFFFFFF0ll || gb >= 0xFFFFFFF0ll) return LOANS_ERANGE;
+    ConvBytes b;        // x, and gy: B x gridH x gridW x 64 floats
+    if (int rc_ = conv_tensor_bytes(d, 4, 4, CONV_BUFFER_LIMIT, &b, false)) return rc_;
     static loans_device_once lds_limit_set;
     if (int rc_ = loans_raise_lds_limit(lds_limit_set, reinterpret_cast<const void*>(stem7_wgrad_kernel), 156 * 1024)) return rc_;
     const int cus = loans_device_cus();
@@ -748,8 +715,7 @@ int loans_stem7_wgrad_launch(const float* x, const float* gy, float* dw, const l
     const int per_cu = 1;                   // eight waves with 160 accumulator registers each fill the register file
     const int units = d->B * d->gridH;
     const int nblk = units < per_cu * cus ? units : per_cu * cus;
-    hipLaunchKernelGGL(stem7_wgrad_kernel, dim3(nblk), dim3(64 * SWG_NW), lds, st, x, gy, dw, d->inH, d->inW, d->gridH, d->gridW, units,
-                       (unsigned)xb, (unsigned)gb);
+    hipLaunchKernelGGL(stem7_wgrad_kernel, dim3(nblk), dim3(64 * SWG_NW), lds, st, x, gy, dw, d->inH, d->inW, d->gridH, d->gridW, units, b.in, b.out);
     LOANS_LAUNCH_CHECK();
     return LOANS_OK;
 }
@@ -757,16 +723,6 @@ int loans_stem7_wgrad_launch(const float* x, const float* gy, float* dw, const l
 // LOANS_TILE_STEM of loans_igemm_f32: `d` must be the dense 7x7 / 2, Cout = 64 forward geometry
 int loans_stem7_launch(const float* in, const float* w, float* out, const float* bias, double* stats,
                        const loans_igemm_desc* d, hipStream_t st) {
-    if (!(d->flags & LOANS_F_DENSE) || (d->flags & ~(LOANS_F_DENSE | LOANS_F_BIAS | LOANS_F_STATS))) return LOANS_EINVAL;
-    if (d->ntaps != 7 || d->Cin != 24 || d->Cout != 64 || d->isy != 2 || d->isx != 6) return LOANS_EINVAL;
-    // a block's image starts at row 2 oy0 of frame b: 16-byte aligned when row length and row count are even
-    if ((d->inW & 1) || (d->inH & 1) || (reinterpret_cast<uintptr_t>(in) & 15) || (reinterpret_cast<uintptr_t>(w) & 15)) return LOANS_EINVAL;
-    for (int t = 0; t < 7; ++t)
-        if (d->dy[t] != t || d->dx[t] != 0) return LOANS_EINVAL;
-    if (d->osy != 1 || d->osx != 1 || d->oy0 || d->ox0 || d->outH != d->gridH || d->outW != d->gridW) return LOANS_EINVAL;
-    if (2 * (d->gridH - 1) + 7 > d->inH || 6 * (d->gridW - 1) + 24 > d->inW) return LOANS_EINVAL;
-    if ((int64_t)d->B * d->inH * d->inW >= ((int64_t)1 << 31) || (int64_t)d->B * d->gridH * d->gridW * 64 >= ((int64_t)1 << 31))
-        return LOANS_ERANGE;
     size_t lds = 0;
     const int R = loans_stem7_rows(d->gridH, d->gridW, d->inW, &lds);
     if (!R) return LOANS_EINVAL;
@@ -784,15 +740,8 @@ int loans_stem7_launch(const float* in, const float* w, float* out, const float*
 // LOANS_TILE_STEM of loans_wgrad_bf16s: `d` is the dense 7x7 / 2, Cout = 64 forward geometry on the bf16 frame buffer.
 // loans_stem7_wgrad_bf16_slabs: the blocks (= slabs of 64 x 168 floats) a launch runs, 0 = this geometry is not covered
 int loans_stem7_wgrad_bf16_slabs(const loans_igemm_desc* d) {
-    if (d->flags != LOANS_F_DENSE) return 0;
-    if (d->ntaps != 7 || d->Cin != 24 || d->Cout != 64 || d->isy != 2 || d->isx != 6) return 0;
-    if ((d->inH & 1) || (d->gridW & 15) || d->gridW > 64 * SWB_PG) return 0;
-    if (d->inW != 6 * (d->gridW + 3)) return 0;                 // rows of whole 12-byte cells, Wo + 3 of them (even frame widths)
-    if (7 * (d->gridW + 3) > 64 * SWB_NW * SWB_PC) return 0;
-    for (int t = 0; t < 7; ++t)
-        if (d->dy[t] != t || d->dx[t] != 0) return 0;
-    if (d->osy != 1 || d->osx != 1 || d->oy0 || d->ox0 || d->outH != d->gridH || d->outW != d->gridW) return 0;
-    if (2 * (d->gridH - 1) + 7 > d->inH) return 0;
+    if (!conv_stem7_wgrad_bf16_covers(d)) return 0;
+    if (d->gridW > 64 * SWB_PG || 7 * (d->gridW + 3) > 64 * SWB_NW * SWB_PC) return 0;
     const size_t lds = (size_t)2 * (swb_patch_bytes(d->gridW) + d->gridW * SWB_GS * 2);
     if (lds > 156 * 1024) return 0;
     const int cus = loans_device_cus();
@@ -804,16 +753,14 @@ int loans_stem7_wgrad_bf16_slabs(const loans_igemm_desc* d) {
 int loans_stem7_wgrad_bf16_launch(const void* x, const void* gy, float* dw, const loans_igemm_desc* d, float* ws, hipStream_t st) {
     const int nblk = loans_stem7_wgrad_bf16_slabs(d);
     if (nblk <= 0) return LOANS_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(gy) & 15) || (reinterpret_cast<uintptr_t>(ws) & 15)) return LOANS_EINVAL;
-    const int64_t xb = (int64_t)d->B * d->inH * d->inW * 2, gb = (int64_t)d->B * d->gridH * d->gridW * 128;
-    if (xb >= 0x7FFFFFF0ll || gb >= 0x7FFFFFF0ll) return LOANS_ERANGE;       // bit 31 of an offset marks a piece that is not loaded
+    ConvBytes b;        // bit 31 of an offset marks a piece that is not loaded
+    if (int rc_ = conv_tensor_bytes(d, 2, 2, 0x7FFFFFF0ll, &b, false)) return rc_;
     size_t lds = (size_t)2 * (swb_patch_bytes(d->gridW) + d->gridW * SWB_GS * 2);
     if (lds < (size_t)SWB_NW * 32 * 33 * sizeof(float)) lds = (size_t)SWB_NW * 32 * 33 * sizeof(float);
     static loans_device_once lds_limit_set;
     if (int rc_ = loans_raise_lds_limit(lds_limit_set, reinterpret_cast<const void*>(stem7_wgrad_bf16_kernel), 156 * 1024)) return rc_;
     hipLaunchKernelGGL(stem7_wgrad_bf16_kernel, dim3(nblk), dim3(64 * SWB_NW), lds, st, reinterpret_cast<const __bf16*>(x),
-                       reinterpret_cast<const __bf16*>(gy), dw, ws, d->inH, d->inW, d->gridH, d->gridW, d->B * d->gridH, (unsigned)xb,
-                       (unsigned)gb);
+                       reinterpret_cast<const __bf16*>(gy), dw, ws, d->inH, d->inW, d->gridH, d->gridW, d->B * d->gridH, b.in, b.out);
     LOANS_LAUNCH_CHECK();
     return LOANS_OK;
 }

@@ -268,25 +268,8 @@ void fill_args(WgHaloArgs& a, const loans_igemm_desc* d) {
 
 }  // namespace
 
-// LOANS_TILE_WGHALO_* covers: the forward geometry of a stride-1 convolution with a 3 x 3 tap grid (row-major, any padding),
-// Cin % 64 == 0, Cout % (64 | 128) == 0, not the dense RGB layout
-int loans_wgrad_halo16_covers(const loans_igemm_desc* d, int tile) {
-    if (tile != LOANS_TILE_WGHALO_64 && tile != LOANS_TILE_WGHALO_128) return 0;
-    if (d->flags & ~LOANS_F_RELU_IN) return 0;
-    if (d->isy != 1 || d->isx != 1 || d->osy != 1 || d->osx != 1 || d->oy0 || d->ox0) return 0;
-    if (d->inH != d->outH || d->inW != d->outW || d->gridH != d->outH || d->gridW != d->outW) return 0;
-    if ((d->Cin % BC) || (d->Cout % (tile == LOANS_TILE_WGHALO_64 ? 64 : 128))) return 0;
-    if (d->ntaps != 9) return 0;
-    for (int t = 0; t < 9; ++t)
-        if (d->dy[t] != d->dy[0] + t / 3 || d->dx[t] != d->dx[0] + t % 3) return 0;
-    if (d->dy[0] < -2 || d->dy[0] > 0 || d->dx[0] < -2 || d->dx[0] > 0) return 0;
-    if ((int64_t)d->B * d->inH * d->inW * (d->Cin > d->Cout ? d->Cin : d->Cout) * 2 >= 0xFFFFFFF0ll) return 0;
-    return 1;
-}
-
 // slabs the launch below would write for this request (>= 1), or an error code
 int loans_wgrad_halo16_slabs(const loans_igemm_desc* d, int tile, int splits) {
-    if (!loans_wgrad_halo16_covers(d, tile)) return LOANS_EINVAL;
     WgHaloArgs a;
     fill_args(a, d);
     return tile == LOANS_TILE_WGHALO_64 ? plan_splits<64, 4>(a, splits) : plan_splits<128, 8>(a, splits);
@@ -296,7 +279,6 @@ int loans_wgrad_halo16_slabs(const loans_igemm_desc* d, int tile, int splits) {
 // Cout * 9 * Cin floats (the caller folds them, loans_fold_slabs_f32); dw is not touched
 int loans_wgrad_halo16_launch(const void* x, const void* gy, float* dw, const loans_igemm_desc* d, int tile, int splits,
                               unsigned x_bytes, unsigned gy_bytes, float* ws, int* slabs, hipStream_t st) {
-    if (!loans_wgrad_halo16_covers(d, tile)) return LOANS_EINVAL;
     WgHaloArgs a;
     a.x = static_cast<const __bf16*>(x); a.gy = static_cast<const __bf16*>(gy); a.dw = dw;
     fill_args(a, d);

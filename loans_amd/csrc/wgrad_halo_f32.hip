@@ -378,24 +378,9 @@ int launch_pair(WgHalo32Args& a, int splits_req, hipStream_t st) {
 
 }  // namespace
 
-// LOANS_TILE_WGHALO_64 of loans_wgrad_f32 covers: the forward geometry of a stride-1 convolution with a 3 x 3 tap grid
-// (row-major, any padding), Cin % 64 == 0, Cout % 64 == 0, not the dense RGB layout
-int loans_wgrad_halo32_covers(const loans_igemm_desc* d) {
-    if (d->flags & ~LOANS_F_RELU_IN) return 0;
-    if (d->isy != 1 || d->isx != 1 || d->osy != 1 || d->osx != 1 || d->oy0 || d->ox0) return 0;
-    if (d->inH != d->outH || d->inW != d->outW || d->gridH != d->outH || d->gridW != d->outW) return 0;
-    if ((d->Cin % BC) || (d->Cout % BC)) return 0;
-    if (d->ntaps != 9) return 0;
-    for (int t = 0; t < 9; ++t)
-        if (d->dy[t] != d->dy[0] + t / 3 || d->dx[t] != d->dx[0] + t % 3) return 0;
-    if (d->dy[0] < -2 || d->dy[0] > 0 || d->dx[0] < -2 || d->dx[0] > 0) return 0;
-    return 1;
-}
-
-// dw += the gradient by fp32 atomics; LOANS_EINVAL (nothing launched) for a geometry the kernel does not cover
+// dw += the gradient by fp32 atomics; the caller (loans_wgrad_f32) has run conv_wgrad_halo_covers
 int loans_wgrad_halo32_launch(const float* x, const float* gy, float* dw, const loans_igemm_desc* d, int splits,
                               unsigned x_bytes, unsigned gy_bytes, hipStream_t st) {
-    if (!loans_wgrad_halo32_covers(d)) return LOANS_EINVAL;
     WgHalo32Args a;
     a.x = x; a.gy = gy; a.dw = dw;
     a.B = d->B; a.H = d->inH; a.W = d->inW; a.Cin = d->Cin; a.Cout = d->Cout;

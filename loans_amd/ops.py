@@ -523,7 +523,7 @@ PW = True
 
 @_memo
 def _pw_tiles(geo, plain):
-    """LOANS_TILE_PW where loans_pw16_covers holds: a 1 x 1 / 1 convolution, Cin 64 or 128 with Cout a multiple of 64 up to 512 or
+    """LOANS_TILE_PW where conv_pw16_covers (csrc/conv_desc.h) holds: a 1 x 1 / 1 convolution, Cin 64 or 128 with Cout a multiple of 64 up to 512 or
     Cin 256 with Cout a multiple of 128 up to 1024, no epilogue beyond the BN statistics (plain = no ReLU on the input, no bias, no
     addend).  ResNet-50's res2 / res3 / res4 expansions."""
     if not PW or not plain or geo.dense or geo.k != 1 or geo.stride != 1 or geo.pad != 0:
@@ -651,7 +651,7 @@ def _igemm16_splitk(lib, src, d_list, out, flags, tile, bias, stats, ref, addend
 
 @_memo
 def _halo_tiles(geo, gathered_channels, out_channels, out_hw, relu_in=False):
-    """halo-tile candidates of a bf16-storage convolution / data gradient (the conditions of loans_halo16_covers), offered
+    """halo-tile candidates of a bf16-storage convolution / data gradient (the conditions of conv_halo16_covers, csrc/conv_desc.h), offered
     where a 8 x 16 pixel tile is not mostly empty"""
     if not HALO or geo.dense or geo.stride != 1 or geo.k > 3 or gathered_channels % 64 or min(out_hw) < 6 or out_hw[1] < 12:
         return ()
@@ -817,7 +817,7 @@ def stem_tile_rows(geo):
 
 @_memo
 def stem_wgrad_ok(geo):
-    """LOANS_TILE_STEM of loans_wgrad_f32 covers this geometry (loans_stem7_wgrad_launch of csrc/stem.hip)"""
+    """LOANS_TILE_STEM of loans_wgrad_f32 covers this geometry (conv_check_stem7 of csrc/conv_desc.h and loans_stem7_wgrad_launch of csrc/stem.hip)"""
     if not (STEM_DIRECT and geo.dense and geo.k == 7 and geo.stride == 2 and geo.pad == 3 and geo.Cout == 64):
         return False
     if 2 * geo.Ho + 5 > geo.Hp or geo.Hp % 2:
@@ -1446,7 +1446,7 @@ def wghalo_f32_ntiles(B, H, W):
 
 @_memo
 def wghalo_tiles(geo, f32=False):
-    """the halo weight-gradient tiles that cover this geometry (loans_wgrad_halo16_covers; f32: loans_wgrad_halo32_covers),
+    """the halo weight-gradient tiles that cover this geometry (conv_wgrad_halo_covers of csrc/conv_desc.h),
     where an 8 x 16 pixel tile (f32: a 7 x 8 one) is not mostly empty"""
     if not WGHALO or geo.dense or geo.k != 3 or geo.stride != 1 or geo.Cin % 64 or geo.Cout % 64 or (geo.Ho, geo.Wo) != (geo.H, geo.W):
         return ()
