@@ -171,6 +171,14 @@ typedef struct loans_igemm_desc {
                                   mask / addend to the finished sums with loans_igemm_finalize_f32 */
 #define LOANS_TILE_DMA    16   /* igemm, fp32 arm, OR-ed onto a tile shape: operand tiles staged by LDS-DMA (buffer_load ... lds)
                                   into XOR-swizzled unpadded LDS rows instead of through registers; same results bit for bit */
+#define LOANS_TILE_POSMAJOR 128 /* loans_igemm_f32, OR-ed onto LOANS_TILE_64x64 (| LOANS_TILE_DMA): a row tile holds the SAME grid position of 64
+                                  consecutive images instead of 64 consecutive (image, y, x) rows, so the taps that fall outside the frame are
+                                  the same for the whole block and its K loop leaves them out (a corner of a 3 x 3 / pad 1 frame runs four
+                                  taps of nine).  Cin % 32 == 0, not LOANS_F_DENSE, taps on a grid, B >= 64; an ordinary launch only (no pair,
+                                  no classes, no split-K).  The plain tile's sums in the plain tile's order minus the products with a gathered
+                                  zero: for finite operands the same output bit for bit up to the sign of an exact zero -- but a non-finite
+                                  WEIGHT under a tap that no pixel of the position reads no longer turns the output into NaN.  STATS / BNSUMS
+                                  partial sums group other rows (a rounding, as between any two tiles).  LOANS_EINVAL otherwise. */
 
 /* ---- convolution (replaces cuDNN ConvolutionForward / BackwardData / BackwardFilter behind
  *      L.Convolution2D: sheep/resnet.py:43,128-133,151-153 ; common/net.py:15-17,37-39,59-60) ---- */

@@ -174,6 +174,10 @@ inline int conv_check_igemm32(const loans_igemm_desc* d, unsigned have, unsigned
     if (pair && ((tile >> 8) || (tile & 0xFF) == LOANS_TILE_SPLIT)) return LOANS_EINVAL;
     const int splits = (tile >> 8) & 0xFF;  // LOANS_TILE_SPLITK(s)
     tile &= 0xFF;
+    if (tile & LOANS_TILE_POSMAJOR) {       // image-strided row tiles: the per-tap loader of the 64x64 tile, an ordinary fp32 launch of whole images
+        if (bf16 || pair || mc || (d->tile >> 8) || (tile & ~(LOANS_TILE_DMA | LOANS_TILE_POSMAJOR)) != LOANS_TILE_64x64) return LOANS_EINVAL;
+        return ((d->Cin & 31) || (d->flags & (LOANS_F_DENSE | LOANS_F_OUT_BF16)) || d->B < 64 || detect_tap_grid(d).nx == 0) ? LOANS_EINVAL : LOANS_OK;
+    }
     if (splits > 1 && (bf16 || (d->flags & ~(LOANS_F_DENSE | LOANS_F_RELU_IN)) || tile == LOANS_TILE_SPLIT))
         return LOANS_EINVAL;                // raw partial sums only: the epilogue flags belong to loans_igemm_finalize_f32
     const bool dma = tile & LOANS_TILE_DMA;

@@ -147,3 +147,82 @@ CONV_ROWS_FN void row_prologue(const loans_igemm_desc& d, const TapGrid g, const
         w.advance(STEP);
     }
 }
+
+// ---- image-strided row tiles (LOANS_TILE_POSMAJOR) ----------------------------------------------------------------------------
+// A row tile holds ONE grid position of BM consecutive images: rows pos + (ig * BM + j) * gridH * gridW of the ordinary GEMM row
+// space, j = 0 .. BM - 1.  The tap mask then is the same for every row of the block, and the block's K loop leaves out the taps
+// that read outside the frame.  tests/conv_posmajor/test_rows_cpu.py owns this arithmetic.
+
+// row tile -> (image group, grid position): the position is the fast index, so that the tiles next to each other (one XCD's, after
+// the remap) gather neighbouring -- overlapping -- input pixels of the same images
+CONV_ROWS_FN void images_tile(int tile_m, int npos, int* ig, int* pos) {
+    *ig = tile_m / npos;
+    *pos = tile_m - *ig * npos;
+}
+CONV_ROWS_FN int images_tiles(int B, int gridH, int gridW, int BM) { return gridH * gridW * ((B + BM - 1) / BM); }
+
+// the taps a block at grid position `pos` runs: bit t SET when tap t reads inside the frame there, and how many are.  From
+// block-uniform values only.  A position with no tap inside (1 x 1 / pad 1 at the rim) keeps tap 0 -- its lanes are masked and read
+// zeros -- so that no block runs an empty K loop.
+struct BlockTaps {
+    unsigned long long mask;
+    int count;
+};
+CONV_ROWS_FN BlockTaps block_taps(const loans_igemm_desc& d, const TapGrid& g, int gridW, int pos, int ntaps, const int8_t* dy,
+                                  const int8_t* dx) {
+    const int y = pos / gridW, x = pos - y * gridW;
+    unsigned long long m = tap_mask(g, false, y * d.isy, x * d.isx, d.inH, d.inW, ntaps, dy, dx);
+    if (!m) m = 1ull;
+    return {m, __builtin_popcountll(m)};
+}
+
+// The per-tap loader's walk along K over the taps of `mask` only, `cpc` 32-deep chunks per tap: the tap and the chunk within it of
+// the chunk loaded next, the scalar byte offsets into the tap's channels (sof_a) and along a weight row (sof_b; rows keep ALL taps).
+struct TapWalk {
+    unsigned long long left;        // the taps not yet finished, the current one included
+    int ktap, kcw;
+    unsigned sof_a, sof_b;
+};
+CONV_ROWS_FN void tap_walk_begin(TapWalk& w, unsigned long long mask, int cpc) {
+    w.left = mask;
+    w.ktap = __builtin_ctzll(mask);         // (mask != 0: block_taps)
+    w.kcw = 0;
+    w.sof_a = 0u;
+    w.sof_b = 128u * (unsigned)(w.ktap * cpc);
+}
+// one chunk on; true when that chunk starts another tap (behind the last tap the state stays on it: nothing is loaded from there)
+CONV_ROWS_FN bool tap_walk_next(TapWalk& w, int cpc) {
+    w.sof_a += 128u;
+    w.sof_b += 128u;
+    if (++w.kcw != cpc) return false;
+    w.kcw = 0;
+    w.sof_a = 0u;
+    w.left &= w.left - 1ull;
+    if (w.left) {
+        w.ktap = __builtin_ctzll(w.left);
+        w.sof_b = 128u * (unsigned)(w.ktap * cpc);
+    }
+    return true;
+}
+
+// row_prologue for such a tile: l.m0 = this thread's first IMAGE (ig * BM + its row of the tile), l.M = the image count; row i is
+// image l.m0 + STEP * i at grid position `pos` and exists iff that image does.  Same rowoff / opix / badmask as row_prologue().
+template <int RA, int STEP, typename MaskT>
+CONV_ROWS_FN void row_prologue_images(const loans_igemm_desc& d, const TapGrid g, const RowLaunch l, int pos,
+                                      unsigned (&rowoff)[RA], MaskT (&badmask)[RA], unsigned* opix, bool store_opix) {
+    const int inH = d.inH, inW = d.inW, isy = d.isy, isx = d.isx, outH = d.outH, outW = d.outW, osy = d.osy, osx = d.osx;
+    const int y = pos / l.gridW, x = pos - y * l.gridW;
+    const int iy0 = y * isy, ix0 = x * isx;
+    const unsigned long long mask = tap_mask(g, l.dense, iy0, ix0, inH, inW, l.ntaps, l.dy, l.dx);
+#ifdef __HIPCC__
+#pragma unroll
+#endif
+    for (int i = 0; i < RA; ++i) {
+        const int b = l.m0 + STEP * i;
+        const bool exists = b < l.M;
+        rowoff[i] = exists ? (unsigned)((b * inH + iy0) * inW + ix0) * l.in_unit_bytes : 0u;
+        badmask[i] = (MaskT)~(exists ? mask : 0ull);
+        if (store_opix)
+            opix[STEP * i] = exists ? (unsigned)((b * outH + y * osy + l.oy0) * outW + x * osx + l.ox0) * l.out_pixel_bytes : 0xFFFFFFFFu;
+    }
+}

@@ -117,9 +117,12 @@ constexpr size_t igemm_aux_floats() {       // offset (floats) of the tap table 
     return stage > cs ? stage : cs;
 }
 
-template <int BM, int BN, int WM, int WN, bool RELU, bool BF16, bool DMA>
+// PM = true (LOANS_TILE_POSMAJOR; fp32 arms, the per-tap loader only): a row tile is one grid position of BM consecutive images
+// (conv_rows.h), the taps outside the frame are the same for the whole block, and the K loop walks the other ones only.
+template <int BM, int BN, int WM, int WN, bool RELU, bool BF16, bool DMA, bool PM = false>
 __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
     static_assert(!(DMA && BF16), "the bf16 arm converts while it stages through registers");
+    static_assert(!(PM && BF16), "image-strided tiles run the fp32 per-tap loader");
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
     constexpr int RA = BM / 32, RB = BN / 32;
     constexpr int NMMA = TM * TN * 4;          // MFMAs per 8-deep k group
@@ -182,7 +185,15 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
     const int cps = (fine && !fine_tail) ? k.nchunks : (a.ncls > 1 ? k.nchunks : a.chunks_per_split);
     const int c_begin = split * cps;                    // this block's K chunks
     const int c_end = min(c_begin + cps, k.nchunks);
-    const int nch = c_end - c_begin;
+    // PM: the row tile is (image group, grid position); the block's K is the chunks of the taps inside the frame at that position
+    int pm_pos = 0, pm_img0 = 0;
+    BlockTaps pm_taps = {1ull, 1};
+    if constexpr (PM) {
+        images_tile(tm, k.gridH * k.gridW, &pm_img0, &pm_pos);
+        pm_img0 *= BM;
+        pm_taps = block_taps(d, k.g, k.gridW, pm_pos, k.ntaps, reinterpret_cast<const int8_t*>(tap_dy), reinterpret_cast<const int8_t*>(tap_dx));
+    }
+    const int nch = PM ? pm_taps.count * (d.Cin >> 5) : c_end - c_begin;
     const int tail_groups = c_end == k.nchunks ? k.tail_groups : 4;
     const int lrow = tid >> 3;
     const int lu = DMA ? ((tid & 7) ^ ((tid >> 4) & 7)) : (tid & 7);   // K unit this thread stages (DMA: slot ^ row key)
@@ -203,7 +214,12 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
     {
         const RowLaunch rl = {a.m_begin + tm * BM + lrow, k.M, k.gridH, k.gridW, k.oy0, k.ox0, k.ntaps, tap_dy, tap_dx,
                               (unsigned)Cout * ((d.flags & LOANS_F_OUT_BF16) ? 2u : 4u), (unsigned)ubytes, dense};
-        row_prologue<RA, 32>(d, k.g, rl, rowoff, badmask, opix + lrow, lu == 0);
+        if constexpr (PM) {
+            const RowLaunch ri = {pm_img0 + lrow, d.B, k.gridH, k.gridW, k.oy0, k.ox0, k.ntaps, tap_dy, tap_dx, rl.out_pixel_bytes, (unsigned)ubytes, dense};
+            row_prologue_images<RA, 32>(d, k.g, ri, pm_pos, rowoff, badmask, opix + lrow, lu == 0);
+        } else {
+            row_prologue<RA, 32>(d, k.g, rl, rowoff, badmask, opix + lrow, lu == 0);
+        }
 #ifdef LOANS_EXPERIMENT
         if (a.dbg & 4)      // cache-hot gathers
             for (int i = 0; i < RA; ++i) { rowoff[i] = (unsigned)((d.inW + 1) * ubytes) + (rowoff[i] & 0xFFFu); badmask[i] = 0; }
@@ -247,11 +263,17 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
         const unsigned bad = 0u - ((unsigned)(badmask[i] >> tc) & 1u);
         voff_a[i] = (rowlane[i] + (unsigned)taps[tc]) | bad;
     };
+    TapWalk pm_walk = {0ull, 0, 0, 0u, 0u};     // PM: the walk over the block's taps (SGPRs)
     auto tap_begin = [&]() {                    // called on the per-tap path only: nothing of it is live on the other one
+        if constexpr (PM) {
+            tap_walk_begin(pm_walk, pm_taps.mask, cpc);
+            ktap = pm_walk.ktap; kcw = 0; sof_a = 0u; sof_b = pm_walk.sof_b;
+        } else {
         ktap = c_begin / cpc;
         kcw = c_begin - ktap * cpc;
         sof_a = 128u * (unsigned)kcw;
         sof_b = 128u * (unsigned)c_begin;
+        }
 #pragma unroll
         for (int i = 0; i < RA; ++i) {
             rowlane[i] = rowoff[i] + (unsigned)lu * 16u;
@@ -325,6 +347,15 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
             else if (!DBGSKIP(16))
                 rb[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_w, (int)voff_b[i], (int)sof_b, 0));
         } else if (p == RA + RB) {
+            if constexpr (PM) {                 // the next tap inside the frame; sof_b jumps over the weights of the ones left out
+                const bool new_tap = tap_walk_next(pm_walk, cpc);
+                ktap = pm_walk.ktap; sof_a = pm_walk.sof_a; sof_b = pm_walk.sof_b;
+                if (new_tap) {
+#pragma unroll
+                    for (int i = 0; i < RA; ++i) tap_voff(i);
+                }
+                return;
+            }
             sof_b += 128u;
             sof_a += 128u;
             if (++kcw == cpc) {
@@ -519,7 +550,8 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
         }
     }
     };
-    if (per_tap) k_loop(std::true_type{});
+    if constexpr (PM) k_loop(std::true_type{});
+    else if (per_tap) k_loop(std::true_type{});
     else k_loop(std::false_type{});
     } else {
     // ---- software-pipelined K loop ---------------------------------------------------------------
@@ -620,7 +652,8 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs a) {
         }
     }
     };
-    if (per_tap) k_loop(std::true_type{});
+    if constexpr (PM) k_loop(std::true_type{});
+    else if (per_tap) k_loop(std::true_type{});
     else k_loop(std::false_type{});
     }   // fp32 / bf16 K loop
 #ifdef LOANS_STAMPS
@@ -816,7 +849,7 @@ void fill_class0(IgemmArgs& a) {
     k.M = a.M; k.Ktot = a.Ktot; k.nchunks = a.nchunks; k.tail_groups = a.tail_groups; k.tiles_m = a.tiles_m; k.blk0 = 0; k.per_xcd = 0;
 }
 
-template <int BM, int BN, int WM, int WN, bool RELU, bool BF16, bool DMA>
+template <int BM, int BN, int WM, int WN, bool RELU, bool BF16, bool DMA, bool PM = false>
 int launch_igemm_r(IgemmArgs& a, hipStream_t st) {
     static loans_device_once lds_limit_set;       // per template instance = per kernel, one bit per device
 #ifdef LOANS_STAMPS
@@ -826,10 +859,11 @@ int launch_igemm_r(IgemmArgs& a, hipStream_t st) {
 #else
     constexpr size_t lds = igemm_lds_bytes<BM, BN, DMA>();
 #endif
-    auto kern = igemm_kernel<BM, BN, WM, WN, RELU, BF16, DMA>;
+    auto kern = igemm_kernel<BM, BN, WM, WN, RELU, BF16, DMA, PM>;
     if (int rc_ = loans_raise_lds_limit(lds_limit_set, reinterpret_cast<const void*>(kern), lds)) return rc_;
-    a.tiles_m = (a.M - a.m_begin + BM - 1) / BM;
+    a.tiles_m = PM ? images_tiles(a.d.B, a.d.gridH, a.d.gridW, BM) : (a.M - a.m_begin + BM - 1) / BM;
     a.tiles_n = (a.d.Cout + BN - 1) / BN;
+    if (PM && (a.ncls > 1 || a.w2 || a.splits != 1 || a.n_full > 0 || a.m_begin)) return LOANS_EINVAL;
     a.tiles_n2 = a.w2 ? (a.Cout2 + BN - 1) / BN : 0;
     if (a.ncls > 1) {           // class launch: every class at full K, its tiles behind the previous class's
         if (a.w2 || a.splits != 1 || a.n_full > 0 || a.m_begin) return LOANS_EINVAL;
@@ -867,6 +901,13 @@ int launch_igemm(IgemmArgs& a, hipStream_t st) {
     if (a.bf16) return relu ? launch_igemm_r<BM, BN, WM, WN, true, true, false>(a, st) : launch_igemm_r<BM, BN, WM, WN, false, true, false>(a, st);
     if (a.dma) return relu ? launch_igemm_r<BM, BN, WM, WN, true, false, true>(a, st) : launch_igemm_r<BM, BN, WM, WN, false, false, true>(a, st);
     return relu ? launch_igemm_r<BM, BN, WM, WN, true, false, false>(a, st) : launch_igemm_r<BM, BN, WM, WN, false, false, false>(a, st);
+}
+
+// LOANS_TILE_POSMAJOR: the 64x64 tile over image-strided rows, register-staged or LDS-DMA (conv_check_igemm32 has seen the rules)
+int launch_igemm_posmajor(IgemmArgs& a, hipStream_t st) {
+    const bool relu = a.d.flags & LOANS_F_RELU_IN;
+    if (a.dma) return relu ? launch_igemm_r<64, 64, 2, 2, true, false, true, true>(a, st) : launch_igemm_r<64, 64, 2, 2, false, false, true, true>(a, st);
+    return relu ? launch_igemm_r<64, 64, 2, 2, true, false, false, true>(a, st) : launch_igemm_r<64, 64, 2, 2, false, false, false, true>(a, st);
 }
 
 }  // namespace
@@ -938,6 +979,7 @@ static int igemm_impl(const float* in, const float* w, float* out, const float* 
     tile &= 0xFF;
     a.dma = (tile & LOANS_TILE_DMA) ? 1 : 0;
     tile &= ~LOANS_TILE_DMA;
+    if (tile & LOANS_TILE_POSMAJOR) return (bf16 || pair || mc) ? LOANS_EINVAL : launch_igemm_posmajor(a, st);
     if (tile == 0) {
         if (d->Cout <= 64) {
             tile = LOANS_TILE_128x64;

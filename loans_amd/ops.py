@@ -854,6 +854,49 @@ def stem16_tile_rows(geo):
     return 0
 
 
+TILE_POSMAJOR = 128     # LOANS_TILE_POSMAJOR, OR-ed onto the 64x64 tile (3, 19): a row tile is one grid position of 64 images, its K loop
+POSMAJOR_MAX_FRAME = 18     # skips the taps outside the frame.  Offered up to this frame size and from this share of skipped
+POSMAJOR_MIN_SKIP = 0.05    # pixel-tap pairs on (3 x 3 / pad 1: 18.1 % at 7 x 7, 9.3 % at 14 x 14, 7.3 % at 18 x 18, 4.7 % at 28 x 28)
+
+
+def posmajor_ok(d, B, dense=False):
+    """LOANS_TILE_POSMAJOR takes this descriptor (conv_check_igemm32 of csrc/conv_desc.h): whole 32-channel chunks per tap, not
+    dense, taps on a row-major grid with unit steps, at least one full tile of images"""
+    if dense or d.Cin % 32 or B < 64:
+        return False
+    dy, dx, n = list(d.dy[:d.ntaps]), list(d.dx[:d.ntaps]), d.ntaps
+    nx = 1
+    while nx < n and dy[nx] == dy[0]:
+        nx += 1
+    if n % nx or nx >= 64:
+        return False
+    sdx = dx[1] - dx[0] if nx > 1 else 1
+    sdy = dy[nx] - dy[0] if n > nx else 1
+    return abs(sdx) == 1 and abs(sdy) == 1 and all(dy[t] == dy[0] + (t // nx) * sdy and dx[t] == dx[0] + (t % nx) * sdx for t in range(n))
+
+
+def posmajor_skipped(d):
+    """share of the (grid position, tap) pairs of a launch that read outside the frame: the K such a tile leaves out"""
+    inside = 0
+    for t in range(d.ntaps):
+        ny = sum(1 for y in range(d.gridH) if 0 <= y * d.isy + d.dy[t] < d.inH)
+        nx = sum(1 for x in range(d.gridW) if 0 <= x * d.isx + d.dx[t] < d.inW)
+        inside += ny * nx
+    return 1.0 - inside / float(d.gridH * d.gridW * d.ntaps)
+
+
+@_memo
+def _posmajor_candidates(geo, dgrad):
+    """the two image-strided forms of the 64x64 tile for a forward convolution or a one-class (stride-1) data gradient on the
+    fp32 arm, where the frame is small enough for the skipped taps to matter"""
+    if COMPUTE != 'f32' or geo.dense or (dgrad and (len(geo.dgrad) != 1 or geo.dgrad_has_empty_class)):
+        return ()
+    d = geo.dgrad[0][0] if dgrad else geo.fwd
+    if max(d.gridH, d.gridW) > POSMAJOR_MAX_FRAME or not posmajor_ok(d, geo.B) or posmajor_skipped(d) < POSMAJOR_MIN_SKIP:
+        return ()
+    return (3 | TILE_POSMAJOR, 19 | TILE_POSMAJOR)
+
+
 TILE_FINETAIL = 8       # LOANS_TILE_FINETAIL (+16 = LDS-DMA): whole 64x64 tiles, then K-slices of the uneven rest in the same launch
 FINETAIL = True
 STEM_DIRECT = True
@@ -930,8 +973,9 @@ def conv_fprop(x, w, geo, out=None, bias=None, stats=None, relu_in=False, addend
         if STEM_DIRECT and not relu_in and addend is None:
             if (stem_tile_rows(geo) if not out_bf16 else stem16_tile_rows(geo)) and (COMPUTE == 'f32') != out_bf16:
                 stem = (TILE_STEM,)
+        pm = () if out_bf16 else _posmajor_candidates(geo, False)
         return (COMPUTE + 'fprop' + ('_stats' if stats is not None else '') + ('_sk' if sk else '') + ('_ft' if ft else '') +
-                ('_st' if stem else ''), run, _FPROP_TILES + sk + ft + stem, False)   # fp32 scratch output: the tile choice carries over
+                ('_st' if stem else ''), run, _FPROP_TILES + sk + ft + stem + pm, False)   # fp32 scratch output: the tile choice carries over
     tile = _resolved_tile(geo, tile, ('fprop', stats is not None, out_bf16, addend is None, relu_in, bias is not None), plan)
     _fprop_account(addend, (geo, x, w, out))
     ev = _event_begin()
@@ -1188,7 +1232,7 @@ def conv_dgrad(gy, w, geo, out=None, mask_ref=None, addend=None, addend_mask_ref
             return ('bf16s_dgrad' + ('_h' if halo else '') + ('_sk' if sk else '') + ('_bn' if bn_sums is not None else ''), run,
                     _IGEMM16_TILES + halo + sk, False)
         cl = _class_candidates(geo)
-        cands, key = _IGEMM_TILES + cl, COMPUTE + 'dgrad' + ('_cl' if cl else '')
+        cands, key = _IGEMM_TILES + cl + _posmajor_candidates(geo, True), COMPUTE + 'dgrad' + ('_cl' if cl else '')
         if bn_sums is not None:
             key += '_bn'
         elif sk_ok and reduce_channels_ok(geo.Cin):

@@ -61,6 +61,7 @@ def main():
     names.update({t + 16: n + 'D' for t, n in list(names.items()) if t in (1, 2, 3, 4, 6)})
     names[7] = '256x128'
     names[8] = 'finetail'
+    names[3 | ops.TILE_POSMAJOR], names[19 | ops.TILE_POSMAJOR] = '64x64P', '64x64PD'      # LOANS_TILE_POSMAJOR (B >= 64, small frames)
     s16 = args.storage == 'bf16'
     if s16:
         ops.set_compute_dtype('bf16')
