@@ -568,6 +568,15 @@ int loans_linear_wide_bwd_f32(const float* x, const float* W, const float* gy, f
  * (argmax == t, first index wins a tie);  out[0] = sum(row_loss) / count, out[1] = sum(row_hit) / B, both summed in a fixed order. */
 int loans_softmax_xent_fwd_f32(const float* z, const int32_t* t, float* gz, float* row_loss, float* row_hit,
                                float* out, int32_t B, int32_t N, void* stream);
+/* The same with a label-smoothed target and a top-k hit: q = (1 - eps) onehot(t) + eps / N (uniform over all N classes, the
+ * convention of torch's label_smoothing), row_loss = lse - (1 - eps) z_t - eps mean(z), gz = (softmax(z) - q) / count.  count and
+ * ignored rows as above (an ignored row: loss 0, gz row 0, row_hit 0, row_hitk 0).  row_hitk[b] = 1 iff
+ * #{ j : z_j > z_t or (z_j == z_t and j < t) } < k -- for k = 1 that is row_hit; k > N: every valid row hits.
+ * out[0] = sum(row_loss) / count, out[1] = sum(row_hit) / B, out[2] = sum(row_hitk) / B, summed in a fixed order.  eps == 0
+ * gives the bits of loans_softmax_xent_fwd_f32 in out[0], out[1], gz, row_loss and row_hit.  Limits as above, 0 <= eps < 1, k >= 1. */
+int loans_softmax_xent_ls_fwd_f32(const float* z, const int32_t* t, float* gz, float* row_loss, float* row_hit,
+                                  float* row_hitk, float* out /* [3] */, int32_t B, int32_t N, double eps, int32_t k,
+                                  void* stream);
 /* y[i] = x[i] * s[0], s on the device (the loss's upstream gradient times gz) */
 int loans_scale_by_scalar_f32(const float* x, const float* s, float* y, int64_t n, void* stream);
 /* y = x * mask (elementwise, n floats) -- RotationDropout forward/backward (functions/rotation_droput.py:26-48) */
@@ -644,6 +653,13 @@ int loans_adam_amsgrad_devlr_f32(float* p, const float* g, float* m, float* v, f
 int loans_adam_f32(float* p, const float* g, float* m, float* v, int64_t n, double lr_t, const float* lr_t_dev,
                    double beta1, double beta2, double eps, double eta, double weight_decay_rate, double grad_scale,
                    void* stream);
+
+/* chainer.optimizers.MomentumSGD with the WeightDecay hook applied to the gradient first, one launch over a flat range:
+ *   g' = g * grad_scale + weight_decay_rate * p;   v = momentum * v - lr * g';   p = p + v
+ * lr_dev != NULL: the rate is read from device memory when the kernel runs (hipGraph), lr is ignored.  p, g, v: 16-byte
+ * aligned like the Adam entries' buffers (four floats per thread); n need not be a multiple of four. */
+int loans_momentum_sgd_f32(float* p, const float* g, float* v, int64_t n, double lr, const float* lr_dev, double momentum,
+                           double weight_decay_rate, double grad_scale, void* stream);
 
 /* ---- input contract on the GPU (common/datasets/image_dataset.py:16-28 `resize_image` -> Pillow
  *      Image.resize(LANCZOS); :98 `image / 255`).  Bit-exact restatement of Pillow's 8-bit two-pass resampler

@@ -1,5 +1,6 @@
 // The ImageNet classification head: a wide Linear layer (9 .. 2^16 outputs) in three directions on the fp32 matrix cores
-// (v_mfma_f32_32x32x2_f32), and softmax cross-entropy with top-1 accuracy in one pass over the logits.
+// (v_mfma_f32_32x32x2_f32), and softmax cross-entropy with top-1 accuracy in one pass over the logits (and its label-smoothed
+// form with a top-k hit).
 // No atomics anywhere in this file: every output element is owned by one lane (GEMM) or one block (loss rows) and is summed
 // in an order that depends on the shape alone, so two launches on the same inputs give the same bits.
 #include "common.h"
@@ -182,6 +183,113 @@ __global__ __launch_bounds__(256) void softmax_xent_reduce_kernel(const float* _
     if (tid == 0) { out[0] = L / (float)count; out[1] = A / (float)B; }
 }
 
+// The label-smoothed form with a top-k hit beside the top-1 one (loans_softmax_xent_ls_fwd_f32).  Target distribution
+//   q = (1 - eps) onehot(t) + eps / N          (uniform over all N classes: torch's label_smoothing)
+//   loss = lse - (1 - eps) z_t - eps mean(z),  gz = (softmax(z) - q) / count
+//   hitk = #{ j : z_j > z_t or (z_j == z_t and j < t) } < k        (k = 1: the top-1 hit, first index wins a tie)
+// mean(z) and the rank are two more block reductions over the LDS row.  eps == 0 (uniform over the launch) takes the expressions
+// of softmax_xent_rows_kernel, so loss, gz and hit carry its bits.
+struct XentLs { float eps, omeps, q_off, q_on; int k; };        // q_off = eps / N, q_on = (1 - eps) + eps / N
+
+__global__ __launch_bounds__(256) void softmax_xent_ls_rows_kernel(const float* __restrict__ z, const int* __restrict__ t,
+                                                                   float* __restrict__ gz, float* __restrict__ row_loss,
+                                                                   float* __restrict__ row_hit, float* __restrict__ row_hitk,
+                                                                   int B, int N, XentLs ls) {
+    extern __shared__ __attribute__((aligned(16))) float row[];
+    __shared__ float shf[4];
+    __shared__ int shi[4];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const float* zr = z + (int64_t)b * N;
+    float* gr = gz + (int64_t)b * N;
+
+    int valid = 0;
+    for (int i = tid; i < B; i += 256) valid += (unsigned)t[i] < (unsigned)N;
+    const int count = max(block_count_256(valid, shi), 1);
+
+    float m = -INFINITY;
+    int am = 0x7fffffff;
+    for (int i = tid; i < N; i += 256) {
+        const float v = zr[i];
+        row[i] = v;
+        if (v > m || am == 0x7fffffff) { m = v; am = i; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float om = __shfl_xor(m, o, 64);
+        const int oa = __shfl_xor(am, o, 64);
+        if (oa != 0x7fffffff && (am == 0x7fffffff || om > m || (om == m && oa < am))) { m = om; am = oa; }
+    }
+    __syncthreads();
+    if ((tid & 63) == 0) { shf[tid >> 6] = m; shi[tid >> 6] = am; }
+    __syncthreads();
+    m = shf[0]; am = shi[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+        const float om = shf[w];
+        const int oa = shi[w];
+        if (oa != 0x7fffffff && (am == 0x7fffffff || om > m || (om == m && oa < am))) { m = om; am = oa; }
+    }
+
+    const int label = t[b];
+    if (tid == 0) row_hit[b] = (am == label) ? 1.f : 0.f;
+    if ((unsigned)label >= (unsigned)N) {       // ignored row (uniform per block)
+        for (int i = tid; i < N; i += 256) gr[i] = 0.f;
+        if (tid == 0) { row_loss[b] = 0.f; row_hitk[b] = 0.f; }
+        return;
+    }
+    const float zt = row[label];
+    int ahead = 0;
+    for (int i = tid; i < N; i += 256) {
+        const float v = row[i];
+        ahead += (v > zt) || (v == zt && i < label);
+    }
+    const int rank = block_count_256(ahead, shi);
+    if (tid == 0) row_hitk[b] = (rank < ls.k) ? 1.f : 0.f;
+
+    float s = 0.f;
+    for (int i = tid; i < N; i += 256) s += expf(row[i] - m);
+    const float S = block_sum_256(s, shf);
+    const float fc = (float)count;
+    if (ls.eps == 0.f) {
+        if (tid == 0) row_loss[b] = (m + logf(S)) - zt;
+        for (int i = tid; i < N; i += 256) {
+            const float p = expf(row[i] - m) / S;
+            gr[i] = (p - (i == label ? 1.f : 0.f)) / fc;
+        }
+        return;
+    }
+    float zs = 0.f;
+    for (int i = tid; i < N; i += 256) zs += row[i];
+    const float mean = block_sum_256(zs, shf) / (float)N;
+    if (tid == 0) row_loss[b] = ((m + logf(S)) - ls.omeps * zt) - ls.eps * mean;
+    for (int i = tid; i < N; i += 256) {
+        const float p = expf(row[i] - m) / S;
+        gr[i] = (p - (i == label ? ls.q_on : ls.q_off)) / fc;
+    }
+}
+
+// out[0] = (sum_b row_loss[b]) / count ; out[1] = (sum_b row_hit[b]) / B ; out[2] = (sum_b row_hitk[b]) / B
+__global__ __launch_bounds__(256) void softmax_xent_ls_reduce_kernel(const float* __restrict__ row_loss, const float* __restrict__ row_hit,
+                                                                     const float* __restrict__ row_hitk, const int* __restrict__ t,
+                                                                     float* __restrict__ out, int B, int N) {
+    __shared__ float shf[4];
+    __shared__ int shi[4];
+    const int tid = threadIdx.x;
+    int valid = 0;
+    float l = 0.f, a = 0.f, ak = 0.f;
+    for (int i = tid; i < B; i += 256) {
+        valid += (unsigned)t[i] < (unsigned)N;
+        l += row_loss[i];
+        a += row_hit[i];
+        ak += row_hitk[i];
+    }
+    const int count = max(block_count_256(valid, shi), 1);
+    const float L = block_sum_256(l, shf);
+    const float A = block_sum_256(a, shf);
+    const float AK = block_sum_256(ak, shf);
+    if (tid == 0) { out[0] = L / (float)count; out[1] = A / (float)B; out[2] = AK / (float)B; }
+}
+
 __global__ __launch_bounds__(256) void scale_by_scalar_kernel(const float* __restrict__ x, const float* __restrict__ s,
                                                               float* __restrict__ y, int64_t n) {
     const float g = s[0];
@@ -242,6 +350,23 @@ extern "C" int loans_softmax_xent_fwd_f32(const float* z, const int32_t* t, floa
     hipLaunchKernelGGL(softmax_xent_rows_kernel, dim3(B), dim3(256), (size_t)N * sizeof(float), st, z, t, gz, row_loss, row_hit, B, N);
     LOANS_LAUNCH_CHECK();
     hipLaunchKernelGGL(softmax_xent_reduce_kernel, dim3(1), dim3(256), 0, st, row_loss, row_hit, t, out, B, N);
+    LOANS_LAUNCH_CHECK();
+    return LOANS_OK;
+}
+
+extern "C" int loans_softmax_xent_ls_fwd_f32(const float* z, const int32_t* t, float* gz, float* row_loss, float* row_hit,
+                                             float* row_hitk, float* out, int32_t B, int32_t N, double eps, int32_t k,
+                                             void* stream) {
+    if (!z || !t || !gz || !row_loss || !row_hit || !row_hitk || !out || B <= 0 || N <= 0) return LOANS_EINVAL;
+    if (!(eps >= 0.0 && eps < 1.0) || k < 1) return LOANS_EINVAL;
+    if (N > XENT_MAX_N || B > XENT_MAX_B) return LOANS_ERANGE;
+    XentLs ls;
+    ls.eps = (float)eps; ls.omeps = (float)(1.0 - eps); ls.q_off = (float)(eps / N); ls.q_on = ls.omeps + ls.q_off; ls.k = k;
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(softmax_xent_ls_rows_kernel, dim3(B), dim3(256), (size_t)N * sizeof(float), st, z, t, gz, row_loss, row_hit,
+                       row_hitk, B, N, ls);
+    LOANS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(softmax_xent_ls_reduce_kernel, dim3(1), dim3(256), 0, st, row_loss, row_hit, row_hitk, t, out, B, N);
     LOANS_LAUNCH_CHECK();
     return LOANS_OK;
 }

@@ -1,5 +1,5 @@
 // Small kernels around the conv stacks: preprocessing, GAP, Linear heads, rotation-dropout
-// multiply, spatial transformer (grid + bilinear sampler), losses and the fused Adam-AMSGrad.
+// multiply, spatial transformer (grid + bilinear sampler), losses, the fused Adam-AMSGrad and momentum SGD.
 // None of them is GEMM-shaped; they are coalesced streaming / wave-shuffle reduction kernels.
 #include "common.h"
 
@@ -460,6 +460,37 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, flo
     }
 }
 
+// ---- momentum SGD (Chainer 4.1 MomentumSGDRule, the WeightDecay hook applied to the gradient first) --------------------------
+struct SgdHyper { float lr, momentum, wd, gscale; };
+
+__device__ __forceinline__ void sgd1(float& p, float g, float& v, const SgdHyper& h) {
+    g = g * h.gscale + h.wd * p;
+    v = h.momentum * v - h.lr * g;
+    p += v;
+}
+
+// the structure of adam_kernel: g read once, v read and written once per step -- non-temporal; p stays cacheable for the same
+// reason as there (the bf16 cast and the re-packs of the next step read it).  20 bytes per parameter against plain Adam's 28.
+__global__ __launch_bounds__(256) void momentum_sgd_kernel(float* p, const float* g, float* v, int64_t n, SgdHyper h,
+                                                           const float* lr_dev) {
+    if (lr_dev) h.lr = *lr_dev;         // read from device memory: the launch can live in a hipGraph
+    const int64_t n4 = n >> 2;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        f32x4 pp = ld4(p + i * 4), gg = ldnt4(g + i * 4), vv = ldnt4(v + i * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float a = pp[e], b = vv[e];
+            sgd1(a, gg[e], b, h);
+            pp[e] = a; vv[e] = b;
+        }
+        st4(p + i * 4, pp); stnt4(v + i * 4, vv);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const int64_t i = n4 * 4 + threadIdx.x;
+        sgd1(p[i], g[i], v[i], h);
+    }
+}
+
 }  // namespace
 
 extern "C" int loans_prep_images_f32(const float* images_nchw, float* out_nhwc4, int32_t B, int32_t H, int32_t W, void* stream) {
@@ -701,6 +732,16 @@ extern "C" int loans_adam_f32(float* p, const float* g, float* m, float* v, int6
     h.eps = (float)eps; h.eta = (float)eta; h.wd = (float)weight_decay_rate; h.gscale = (float)grad_scale;
     hipLaunchKernelGGL(adam_kernel, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, as_stream(stream), p, g, m, v, (float*)nullptr, n,
                        h, lr_t_dev);
+    LOANS_LAUNCH_CHECK();
+    return LOANS_OK;
+}
+
+extern "C" int loans_momentum_sgd_f32(float* p, const float* g, float* v, int64_t n, double lr, const float* lr_dev,
+                                      double momentum, double weight_decay_rate, double grad_scale, void* stream) {
+    if (!p || !g || !v || n <= 0) return LOANS_EINVAL;
+    SgdHyper h;
+    h.lr = (float)lr; h.momentum = (float)momentum; h.wd = (float)weight_decay_rate; h.gscale = (float)grad_scale;
+    hipLaunchKernelGGL(momentum_sgd_kernel, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, as_stream(stream), p, g, v, n, h, lr_dev);
     LOANS_LAUNCH_CHECK();
     return LOANS_OK;
 }

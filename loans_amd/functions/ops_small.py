@@ -149,6 +149,19 @@ class SoftmaxCrossEntropy(Function):
         self.gz = None
 
 
+class SoftmaxCrossEntropyTopK(SoftmaxCrossEntropy):
+    """The same against the label-smoothed target ``(1 - label_smoothing) onehot + label_smoothing / N`` (torch's convention),
+    with the top-``topk`` accuracy as a third output: (loss, accuracy, accuracy_topk).  The backward is the parent's."""
+
+    def __init__(self, label_smoothing, topk):
+        self.label_smoothing, self.topk = float(label_smoothing), int(topk)
+
+    def forward(self, inputs):
+        x, t = inputs[0].contiguous(), inputs[1].contiguous()
+        out, self.gz, _, _, _ = ops.softmax_xent_ls_fwd(x, t, self.label_smoothing, self.topk)
+        return out[0], out[1], out[2]
+
+
 def _as_labels(x, t):
     import numpy as np
     if isinstance(t, Variable):
@@ -163,6 +176,13 @@ def softmax_cross_entropy_with_accuracy(x, t, ignore_label=-1):
     if ignore_label != -1:
         raise ValueError('only ignore_label=-1 (Chainer\'s default) is built')
     return SoftmaxCrossEntropy()(x, _as_labels(x, t))
+
+
+def softmax_cross_entropy_with_topk_accuracy(x, t, label_smoothing=0.0, topk=1, ignore_label=-1):
+    """(loss, accuracy, accuracy_topk): the label-smoothed loss, the top-1 and the top-``topk`` accuracy from one pass"""
+    if ignore_label != -1:
+        raise ValueError('only ignore_label=-1 (Chainer\'s default) is built')
+    return SoftmaxCrossEntropyTopK(label_smoothing, topk)(x, _as_labels(x, t))
 
 
 def softmax_cross_entropy(x, t, ignore_label=-1):

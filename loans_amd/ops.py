@@ -2443,6 +2443,25 @@ def softmax_xent_fwd(z, t):
     return out, gz, row_loss, row_hit
 
 
+def softmax_xent_ls_fwd(z, t, eps, k):
+    """softmax_xent_fwd against the label-smoothed target (1 - eps) onehot + eps / N, with a top-k hit beside the top-1 one
+    -> (out, gz, row_loss, row_hit, row_hitk): out[0] the batch loss, out[1] / out[2] the top-1 / top-k accuracy.  eps = 0 gives
+    softmax_xent_fwd's bits.  No host synchronisation."""
+    assert z.dtype == torch.float32 and z.dim() == 2 and z.is_contiguous(), 'logits must be a contiguous (B, N) fp32 array'
+    assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == z.shape[0] and t.device == z.device, \
+        'labels must be int32, one per row, on the logits\' device'
+    B, N = z.shape
+    gz = _empty_like(z)
+    row_loss = _empty((B,), device=z.device, dtype=torch.float32)
+    row_hit = _empty((B,), device=z.device, dtype=torch.float32)
+    row_hitk = _empty((B,), device=z.device, dtype=torch.float32)
+    out = _empty((3,), device=z.device, dtype=torch.float32)
+    if CLASS_COUNT is not None: _acct('heads', 0, _nbytes(z), _nbytes(gz))
+    check(_lib.load().loans_softmax_xent_ls_fwd_f32(_ptr(z), _ptr(t), _ptr(gz), _ptr(row_loss), _ptr(row_hit), _ptr(row_hitk),
+                                                    _ptr(out), B, N, float(eps), int(k), _stream()), 'loans_softmax_xent_ls_fwd_f32')
+    return out, gz, row_loss, row_hit, row_hitk
+
+
 def scale_by_scalar(x, s):
     """x * s[0] with s a one-element device tensor"""
     assert s.dtype == torch.float32 and s.numel() == 1 and s.device == x.device
@@ -2617,3 +2636,13 @@ def adam_amsgrad(p, g, m, v, vhat, lr_t, beta1, beta2, eps, eta, weight_decay_ra
     check(_lib.load().loans_adam_amsgrad_f32(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(vhat), p.numel(), lr_t, beta1,
                                              beta2, eps, eta, weight_decay_rate, grad_scale, _stream()),
           'loans_adam_amsgrad_f32')
+
+
+def momentum_sgd(p, g, v, lr, momentum, weight_decay_rate, grad_scale=1.0):
+    """lr: a Python float, or a 1-element device tensor read by the kernel when it runs (graph-capturable)."""
+    if CLASS_COUNT is not None: _acct('optimizer', 0, _nbytes(p, g, v), _nbytes(p, v))
+    dev_lr = torch.is_tensor(lr)
+    if dev_lr:
+        assert lr.dtype == torch.float32 and lr.numel() == 1 and lr.is_cuda
+    check(_lib.load().loans_momentum_sgd_f32(_ptr(p), _ptr(g), _ptr(v), p.numel(), 0.0 if dev_lr else lr, _ptr(lr) if dev_lr else 0,
+                                             momentum, weight_decay_rate, grad_scale, _stream()), 'loans_momentum_sgd_f32')

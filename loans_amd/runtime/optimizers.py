@@ -1,7 +1,10 @@
-"""``chainer.optimizers.Adam(alpha, amsgrad=True)`` (train_sheep_localizer.py:130-134)
-as ONE fused kernel launch over the model's flat parameter arena.
+"""The optimisers, each ONE fused kernel launch over the model's flat parameter arena: ``chainer.optimizers.Adam(alpha,
+amsgrad=True)`` (train_sheep_localizer.py:130-134) and ``chainer.optimizers.MomentumSGD`` with the ``WeightDecay`` hook folded
+in (the ImageNet pre-training recipe, train_imagenet.py).  ``GradientMethod`` holds what is not an update rule's arithmetic:
+hooks, the ``lossfun`` path, the data-parallel gradient exchange, the stepped prefix and the capture hooks; an optimiser
+supplies its state buffers (``_new_state``), its rate (``lr``) and its kernel call (``_step``).
 
-Chainer 4.1.0 semantics (oracle/chainer_ops.py:adam_amsgrad_update): eps sits outside
+Adam, Chainer 4.1.0 semantics (oracle/chainer_ops.py:adam_amsgrad_update): eps sits outside
 the bias correction, ``lr_t = alpha * sqrt(1 - beta2^t) / (1 - beta1^t)``, parameters
 without a gradient are updated with zeros (``reallocate_cleared_grads``): for a parameter
 that never had one (m = v = 0) that is a no-op, so the arena's never-used tail -- res6 / res7
@@ -17,11 +20,13 @@ import torch
 from .. import ops
 
 
-class Adam:
+class GradientMethod:
+    """``chainer.GradientMethod`` over one arena.  A subclass sets ``self.hyperparam`` and provides ``_new_state(zeros)`` (its
+    state buffers, each the size of the arena), the property ``lr`` (the rate of step ``self.t``) and
+    ``_step(arena, n, state, lr, grad_scale)`` (one kernel launch over the first ``n`` floats; ``lr`` is a float, or the device
+    scalar of a captured step)."""
 
-    def __init__(self, alpha=0.001, beta1=0.9, beta2=0.999, eps=1e-8, eta=1.0, weight_decay_rate=0, amsgrad=False):
-        self.hyperparam = SimpleNamespace(alpha=alpha, beta1=beta1, beta2=beta2, eps=eps, eta=eta,
-                                          weight_decay_rate=weight_decay_rate, amsgrad=amsgrad)
+    def __init__(self):
         self.t = 0
         self.target = None
         self.comm = None
@@ -51,30 +56,12 @@ class Adam:
         for hook in list(self._hooks.values()):
             hook(self)
 
-    @property
-    def alpha(self):
-        return self.hyperparam.alpha
-
-    @alpha.setter
-    def alpha(self, v):
-        self.hyperparam.alpha = v
-
-    @property
-    def lr(self):
-        hp = self.hyperparam
-        if self.t == 0:
-            raise RuntimeError("Can't determine the learning rate of Adam optimizer because the update steps have not been started.")
-        fix1 = 1. - math.pow(hp.beta1, self.t)
-        fix2 = 1. - math.pow(hp.beta2, self.t)
-        return hp.alpha * math.sqrt(fix2) / fix1
-
     def _ensure_state(self):
         arena = self.target.arena
         if arena is None:
             arena = self.target.finalize()
         if self._state is None or self._state[0].numel() != arena.numel:
-            z = lambda: torch.zeros(arena.numel, device=arena.device, dtype=torch.float32)   # noqa: E731
-            self._state = (z(), z(), z())
+            self._state = tuple(self._new_state(lambda: torch.zeros(arena.numel, device=arena.device, dtype=torch.float32)))
         return arena
 
     def update(self, lossfun=None, *args, **kwds):
@@ -111,8 +98,6 @@ class Adam:
                     raise RuntimeError('optimizer hooks run on the host: not inside a captured step')
             else:
                 self.call_hooks()
-        hp = self.hyperparam
-        m, v, vhat = self._state
         # parameters beyond the prefix the current graph touches have no gradient.  Those that never had one are skipped
         # (m = v = 0: Chainer's zero-gradient step is a no-op); those that were trained before -- the frame height crossed
         # 224 / 300 px between steps -- are stepped with a zero gradient like Chainer does (their m decays, they keep moving)
@@ -128,14 +113,13 @@ class Adam:
             # being recorded into a hipGraph (SheepAssessor(use_graph=True)): nothing executes now, and the replays
             # must not bake in this step's rate -- the kernel reads it from device memory, `begin_replay()` advances it
             if getattr(self, '_lr_dev', None) is None:
-                raise RuntimeError('call prepare_capture() before recording Adam.update() into a graph')
+                raise RuntimeError('call prepare_capture() before recording %s.update() into a graph' % type(self).__name__)
             lr = self._lr_dev
             self._captured = True
         else:
             self.t += 1
             lr = self.lr
-        ops.adam_amsgrad(arena.data[:n], arena.grad[:n], m[:n], v[:n], vhat[:n] if hp.amsgrad else None, lr, hp.beta1, hp.beta2,
-                         hp.eps, hp.eta, hp.weight_decay_rate, grad_scale)
+        self._step(arena, n, self._state, lr, grad_scale)
 
     def _exchange_active(self):
         return self.comm is not None and getattr(self.comm, 'active', self.comm.size > 1) and \
@@ -199,7 +183,67 @@ class Adam:
             self._lr_dev = torch.zeros(1, device=arena.device, dtype=torch.float32)
 
     def begin_replay(self):
-        """Before replaying a captured step: count it and publish its bias-corrected rate to the kernel."""
+        """Before replaying a captured step: count it and publish its rate (Adam: bias-corrected) to the kernel."""
         if getattr(self, '_captured', False):
             self.t += 1
             self._lr_dev.fill_(self.lr)
+
+
+class Adam(GradientMethod):
+
+    def __init__(self, alpha=0.001, beta1=0.9, beta2=0.999, eps=1e-8, eta=1.0, weight_decay_rate=0, amsgrad=False):
+        super().__init__()
+        self.hyperparam = SimpleNamespace(alpha=alpha, beta1=beta1, beta2=beta2, eps=eps, eta=eta,
+                                          weight_decay_rate=weight_decay_rate, amsgrad=amsgrad)
+
+    @property
+    def alpha(self):
+        return self.hyperparam.alpha
+
+    @alpha.setter
+    def alpha(self, v):
+        self.hyperparam.alpha = v
+
+    @property
+    def lr(self):
+        hp = self.hyperparam
+        if self.t == 0:
+            raise RuntimeError("Can't determine the learning rate of Adam optimizer because the update steps have not been started.")
+        fix1 = 1. - math.pow(hp.beta1, self.t)
+        fix2 = 1. - math.pow(hp.beta2, self.t)
+        return hp.alpha * math.sqrt(fix2) / fix1
+
+    def _new_state(self, zeros):
+        return zeros(), zeros(), zeros()        # m, v, vhat
+
+    def _step(self, arena, n, state, lr, grad_scale):
+        hp = self.hyperparam
+        m, v, vhat = state
+        ops.adam_amsgrad(arena.data[:n], arena.grad[:n], m[:n], v[:n], vhat[:n] if hp.amsgrad else None, lr, hp.beta1, hp.beta2,
+                         hp.eps, hp.eta, hp.weight_decay_rate, grad_scale)
+
+
+class MomentumSGD(GradientMethod):
+    """``chainer.optimizers.MomentumSGD(lr, momentum)`` with ``chainer.optimizer.WeightDecay(weight_decay_rate)`` applied to the
+    gradient first: ``g' = g + rate * p; v = momentum * v - lr * g'; p += v``.  State: one ``v`` the size of the arena.  The
+    prefix rule of the module docstring holds as it stands: v = 0 and g = 0 make the step of a never-used parameter a no-op,
+    and a parameter that was stepped before keeps moving by its decaying ``v``."""
+
+    def __init__(self, lr=0.01, momentum=0.9, weight_decay_rate=0.0):
+        super().__init__()
+        self.hyperparam = SimpleNamespace(lr=lr, momentum=momentum, weight_decay_rate=weight_decay_rate)
+
+    @property
+    def lr(self):
+        return self.hyperparam.lr
+
+    @lr.setter
+    def lr(self, v):
+        self.hyperparam.lr = v
+
+    def _new_state(self, zeros):
+        return (zeros(),)
+
+    def _step(self, arena, n, state, lr, grad_scale):
+        hp = self.hyperparam
+        ops.momentum_sgd(arena.data[:n], arena.grad[:n], state[0][:n], lr, hp.momentum, hp.weight_decay_rate, grad_scale)

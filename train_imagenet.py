@@ -1,18 +1,26 @@
 #!/usr/bin/env python
 """ImageNet pre-training of the localizer backbones (the ``train_imagenet=True`` arm of the reference's localizers,
 sheep/sheep_localizer.py:20-49,122-152): ``Classifier(SheepLocalizer(train_imagenet=True))`` -- softmax cross-entropy over
-the 1000-way head -- trained with Adam.  The snapshot it writes is what ``train_sheep_localizer.py --rl`` starts a LoANs
-run from: ``load_pretrained_model`` is not strict, so the backbone is taken and ``fc`` / ``fc6`` are ignored.
+the 1000-way head -- trained with Adam (the default) or with the recipe every ResNet is trained with: momentum SGD, weight
+decay, a stepped learning rate, label smoothing, top-1 and top-5 accuracy.  The snapshot it writes is what
+``train_sheep_localizer.py --rl`` starts a LoANs run from: ``load_pretrained_model`` is not strict, so the backbone is taken
+and ``fc`` / ``fc6`` are ignored.
 
     python train_imagenet.py train.tsv val.tsv --use-resnet-18 -b 64
     python train_imagenet.py --use-resnet-18 -b 32 --iterations 20            (seeded synthetic classes)
+    python train_imagenet.py train.tsv val.tsv -b 256 --optimizer sgd --lr 0.1 --weight-decay 1e-4 \
+        --lr-drop-epochs 30 60 90 --label-smoothing 0.1 --topk 5
     python train_sheep_localizer.py --use-resnet-18 --rl <log dir>/SheepLocalizer_20.npz
 
 ``train_file`` / ``val_file`` hold one tab-separated ``path<TAB>class`` line per image, paths relative to the file; the
 literal ``synthetic`` (the default) is a seeded set of low-frequency textures, one per class.
 
-Not built (follow-ups): ``--gpus N``, ``--use-graph``, a momentum-SGD optimiser, top-5 accuracy, label smoothing and
-random-resized-crop augmentation.
+``--lr-drop-epochs`` multiplies the rate (``lr``, or Adam's ``alpha``) by ``--lr-drop-factor`` from the first iteration of
+each listed epoch on -- a host-side assignment, like Chainer's ``ExponentialShift``.  Label smoothing applies to the training
+loss only; the validation loss stays the plain cross-entropy.
+
+Not built (follow-ups): ``--gpus N``, ``--use-graph`` and random-resized-crop augmentation (it needs a row pitch in
+``loans_resample_job``, a change of that ABI structure).
 """
 import argparse
 import datetime
@@ -52,8 +60,14 @@ def parse_args(argv=None):
     parser.add_argument("--use-resnet-18", action='store_true', default=False, help="SheepLocalizer (ResNet-18 variant) instead of the ResNet-50 one")
     parser.add_argument("-b", "--batch-size", type=int, default=32, help="batch size")
     parser.add_argument("-g", "--gpu", type=int, default=-1, help="gpu id to use (-1: the current device)")
-    parser.add_argument("--lr", "--learning-rate", dest="learning_rate", type=float, default=0.001, help="Adam's alpha")
-    parser.add_argument("--weight-decay", type=float, default=0.0, help="Adam's weight_decay_rate")
+    parser.add_argument("--lr", "--learning-rate", dest="learning_rate", type=float, default=0.001, help="Adam's alpha / momentum SGD's lr")
+    parser.add_argument("--weight-decay", type=float, default=0.0, help="weight_decay_rate of the optimiser")
+    parser.add_argument("--optimizer", default='adam', choices=['adam', 'sgd'], help="Adam, or SGD with momentum")
+    parser.add_argument("--momentum", type=float, default=0.9, help="momentum of --optimizer sgd")
+    parser.add_argument("--lr-drop-epochs", type=int, nargs='+', default=(), help="epochs at whose first iteration the rate is multiplied by --lr-drop-factor")
+    parser.add_argument("--lr-drop-factor", type=float, default=0.1, help="factor of each learning rate step")
+    parser.add_argument("--label-smoothing", type=float, default=0.0, help="label smoothing of the training loss (uniform over all classes)")
+    parser.add_argument("--topk", type=int, default=None, help="also report top-k accuracy (default: 5 with --optimizer sgd, off with adam; 0: off)")
     parser.add_argument("--num-epoch", type=int, default=100, help="number of epochs to train")
     parser.add_argument("--iterations", type=int, default=None, help="stop after this many iterations (before --num-epoch epochs)")
     parser.add_argument("--image-size", type=int, nargs=2, default=(224, 224), help="input size")
@@ -75,12 +89,26 @@ def parse_args(argv=None):
     return parser.parse_args(argv)
 
 
+def scheduled_lr(base, epoch, drop_epochs, factor):
+    """the stepped rate of ``epoch``: ``base`` times ``factor`` once per listed epoch that has begun -- a pure function, so a
+    resumed run and a fresh one agree"""
+    return base * factor ** sum(1 for e in set(drop_epochs) if e <= epoch)
+
+
+def resolved_topk(args):
+    """k of the reported top-k accuracy, or None: ``--topk`` where given (0: off), else 5 with SGD and off with Adam"""
+    if args.topk is None:
+        return 5 if args.optimizer == 'sgd' else None
+    return args.topk if args.topk > 0 else None
+
+
 def build_model(args):
     """the localizer in its ``train_imagenet`` form under a ``Classifier``; host side only"""
     if args.seed is not None:
         np.random.seed(args.seed)
     localizer_class = loans_amd.SheepLocalizer if args.use_resnet_18 else loans_amd.Resnet50SheepLocalizer
-    model = loans_amd.Classifier(localizer_class((75, 75), train_imagenet=True))
+    model = loans_amd.Classifier(localizer_class((75, 75), train_imagenet=True), label_smoothing=args.label_smoothing,
+                                 topk=resolved_topk(args))
     model.materialize()         # the ResNet-18 variant's lazily sized fc
     return model
 
@@ -127,8 +155,13 @@ def run(args, log=print):
         model.set_precision('bf16', 'bf16')
     model.to_gpu(args.gpu)
 
-    optimizer = loans_amd.Adam(alpha=args.learning_rate, weight_decay_rate=args.weight_decay)
+    if args.optimizer == 'sgd':
+        optimizer, rate_name = loans_amd.MomentumSGD(lr=args.learning_rate, momentum=args.momentum, weight_decay_rate=args.weight_decay), 'lr'
+    else:
+        optimizer, rate_name = loans_amd.Adam(alpha=args.learning_rate, weight_decay_rate=args.weight_decay), 'alpha'
     optimizer.setup(model)
+    topk = 'accuracy_top%d' % model.topk if model.topk is not None else None
+    train_keys = ('loss', 'accuracy') + ((topk,) if topk else ())
     updater = training.StandardUpdater(train_iter, optimizer, converter=converter, device=args.gpu)
 
     evaluator = None
@@ -139,7 +172,10 @@ def run(args, log=print):
         def eval_func(x, t):
             with loans_amd.using_config('train', False), loans_amd.using_config('enable_backprop', False):
                 model(x, t)
-            return {'validation/loss': float(model.loss.data), 'validation/accuracy': float(model.accuracy.data)}
+            result = {'validation/loss': float(model.loss.data), 'validation/accuracy': float(model.accuracy.data)}
+            if topk:
+                result['validation/' + topk] = float(model.accuracy_topk.data)
+            return result
 
         evaluator = training.Evaluator(validation_iter, model, converter=converter, device=args.gpu, eval_func=eval_func)
 
@@ -157,23 +193,30 @@ def run(args, log=print):
     t0 = time.time()
     it = 0
     while updater.epoch < args.num_epoch and (args.iterations is None or it < args.iterations):
+        lr = scheduled_lr(args.learning_rate, updater.epoch, args.lr_drop_epochs, args.lr_drop_factor)
+        setattr(optimizer, rate_name, lr)
         updater.update()
         it = updater.iteration
         last = (args.iterations is not None and it == args.iterations) or updater.epoch >= args.num_epoch
         if updater.is_new_epoch or it % args.log_interval == 0 or last:
             # the only host synchronisation of an iteration
             obs = loans_amd.reporter.observation
-            entry = {'iteration': it, 'epoch': updater.epoch, 'loss': float(obs['loss']), 'accuracy': float(obs['accuracy'])}
+            entry = {'iteration': it, 'epoch': updater.epoch}
+            entry.update({k: float(obs[k]) for k in train_keys})
+            entry['lr'] = lr                    # the rate this iteration was stepped with
             if evaluator is not None:
-                keep = (obs['loss'], obs['accuracy'])
+                keep = {k: obs[k] for k in train_keys}
                 entry.update({k: v for k, v in evaluator.evaluate().items() if k.startswith('validation/')})
-                loans_amd.report({'loss': keep[0], 'accuracy': keep[1]})
+                loans_amd.report(keep)
             entry['elapsed_time'] = time.time() - t0
+            top = '  top-%d %%.4f' % model.topk if topk else ''
             val = ''
             if 'validation/loss' in entry:
                 val = '  validation loss %.5f accuracy %.4f' % (entry['validation/loss'], entry['validation/accuracy'])
-            log('iteration %4d  epoch %d  loss %.5f  accuracy %.4f%s  (%.1f s)' % (
-                it, updater.epoch, entry['loss'], entry['accuracy'], val, entry['elapsed_time']))
+                if topk:
+                    val += top % entry['validation/' + topk]
+            log('iteration %4d  epoch %d  lr %g  loss %.5f  accuracy %.4f%s%s  (%.1f s)' % (
+                it, updater.epoch, lr, entry['loss'], entry['accuracy'], top % entry[topk] if topk else '', val, entry['elapsed_time']))
             if not log_entries:
                 entry.update(data_to_log)
             log_entries.append(entry)
