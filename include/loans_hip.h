@@ -691,6 +691,34 @@ int loans_resize_lanczos_u8_f32(const uint8_t* src, uint8_t* tmp, float* dst, in
 /* [B][H][W][3] uint8 -> [B][3][H][W] float32 / 255 (frames that need no resize) */
 int loans_u8hwc3_to_f32chw(const uint8_t* src, float* dst, int32_t B, int32_t H, int32_t W, void* stream);
 
+/* ---- crop + resize feed of the ImageNet pre-training arm (csrc/croprs.hip): random-resized-crop / centre crop, i.e.
+ *      Image.fromarray(frame[y0:y0+h, x0:x0+w]) [.transpose(FLIP_LEFT_RIGHT)] .resize((outW, outH), Image.BILINEAR) / 255 in
+ *      CHW, bit for bit, for a whole batch in ONE launch.  The crop is read IN PLACE: job j names the first byte of its frame
+ *      (or of the rows staged for it) in `src`, the row pitch in bytes, and the crop's origin and size in pixels of that
+ *      frame; the tables are those of the crop's width and height (`tables` as in loans_resize_ragged_u8_f32: per axis bounds
+ *      [out][2] then coefficients [out][ks], offsets in int32 words).  `flip`: crop, mirror, resize -- pixel x of the crop is
+ *      pixel x0 + w - 1 - x of the row.  Job j writes dst[j] ([3][outH][outW] float32).  blockIdx.y = the frame, blockIdx.x = a
+ *      band of loans_crop_band_rows(outH, outW) output rows; a block runs the horizontal pass over the crop rows its band
+ *      needs into LDS (uint8 [rows][outW][3]; static LDS, LOANS_CROP_LDS_BYTES at most -- a smaller image, more blocks per
+ *      CU, where max_vks allows it), then the vertical pass out of LDS; a band whose rows do not fit takes several fills.  No intermediate in HBM.  The one shape it cannot do is an output row that
+ *      needs more crop rows than fit: LOANS_EINVAL when max_vks (the largest vks of the jobs, from the host) exceeds
+ *      LOANS_CROP_LDS_BYTES / (outW * 3), as for null pointers, non-positive sizes and njobs > 65535 -- before any launch.
+ *      The jobs themselves are device memory and are NOT checked here: the host wrapper validates them
+ *      (loans_amd/common/datasets/crop_resize.py). ---- */
+#define LOANS_CROP_LDS_BYTES 65536
+typedef struct loans_crop_job {
+    int64_t src_off;            /* byte offset in src of pixel (0, 0) of the frame the box refers to */
+    int32_t pitch;              /* bytes from one row of that frame to the next (>= 3 * its width) */
+    int32_t y0, x0, h, w;       /* the crop, in pixels of that frame */
+    int32_t hb_off, hk_off, hks;    /* tables of resample_coeffs(w, outW, 'bilinear') */
+    int32_t vb_off, vk_off, vks;    /* tables of resample_coeffs(h, outH, 'bilinear') */
+    int32_t flip;
+} loans_crop_job;
+int loans_crop_resize_u8_f32(const uint8_t* src, float* dst, const loans_crop_job* jobs, int32_t njobs,
+                             const int32_t* tables, int32_t max_vks, int32_t outH, int32_t outW, void* stream);
+/* output rows per block of that launch (host arithmetic only; <= 0 for non-positive sizes) */
+int loans_crop_band_rows(int32_t outH, int32_t outW);
+
 /* library / build identification */
 const char* loans_hip_version(void);
 

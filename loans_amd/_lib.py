@@ -120,6 +120,8 @@ SIGNATURES = {
     'loans_resize_lanczos_u8_f32': [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _i32, _p, _p, _i32, _p],
     'loans_resize_ragged_u8_f32': [_p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p],
     'loans_u8hwc3_to_f32chw': [_p, _p, _i32, _i32, _i32, _p],
+    'loans_crop_resize_u8_f32': [_p, _p, _p, _i32, _p, _i32, _i32, _i32, _p],
+    'loans_crop_band_rows': [_i32, _i32],
     'loans_prep_images_f32': [_p, _p, _i32, _i32, _i32, _p],
     'loans_prep_images_dense_f32': [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p],
     'loans_prep_images_dense_bf16': [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p],
@@ -169,7 +171,7 @@ SIGNATURES = {
 }
 
 # every entry point returns int (0 / LOANS_E* / hipError_t) except:
-RESTYPES = {'loans_wgrad_bf16s_ws_floats': C.c_int64}
+RESTYPES = {'loans_wgrad_bf16s_ws_floats': C.c_int64, 'loans_crop_band_rows': C.c_int}      # (sizes / counts, not a status)
 
 _lib = None
 

@@ -1348,7 +1348,15 @@ def side_stream_cus(device=None):
 
 
 def _new_side_stream(device):
-    return torch.cuda.Stream(device=device)
+    """torch hands out the streams of a device from a pool of 32, round-robin: one drawn 32 draws after another IS that one (the
+    feeding iterators draw from the same pool).  A draw that coincides with a side stream already in use is repeated, so that
+    LOANS_WGRAD_STREAMS streams are that many queues."""
+    taken = {s.cuda_stream for s in [_side.get(device.index)] + list(_side_more.get(device.index, ())) if s is not None}
+    for _ in range(32):
+        st = torch.cuda.Stream(device=device)
+        if st.cuda_stream not in taken:
+            break
+    return st
 
 
 # Consecutive weight gradients are independent of each other: with LOANS_WGRAD_STREAMS = n > 1 they rotate over n streams, so that

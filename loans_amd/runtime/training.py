@@ -266,7 +266,8 @@ class MultithreadIterator(SerialIterator):
         _, batch, ev = item
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(ev)
-        batch.record_stream(cur)
+        for tensor in (batch if isinstance(batch, tuple) else (batch,)):      # (frames, labels) of the classification datasets
+            tensor.record_stream(cur)
         return batch
 
     next = __next__

@@ -19,8 +19,15 @@ literal ``synthetic`` (the default) is a seeded set of low-frequency textures, o
 each listed epoch on -- a host-side assignment, like Chainer's ``ExponentialShift``.  Label smoothing applies to the training
 loss only; the validation loss stays the plain cross-entropy.
 
-Not built (follow-ups): ``--gpus N``, ``--use-graph`` and random-resized-crop augmentation (it needs a row pitch in
-``loans_resample_job``, a change of that ABI structure).
+``--augment rrc`` is the usual input pipeline, finished on the GPU: training frames are a random-resized-crop (area fraction
+``--rrc-scale``, aspect ratio ``--rrc-ratio``) mirrored with probability one half, validation frames the centre crop
+(``--val-crop-pct`` of the largest box of the output's aspect ratio), both Pillow's BILINEAR resize to ``--image-size`` byte
+for byte.  uint8 frames go up as they are -- only the rows a crop needs -- and one kernel launch per batch, on the iterator's
+own stream, crops, mirrors, resizes and writes ``/ 255`` float32 CHW (loans_amd/common/datasets/crop_resize.py,
+csrc/croprs.hip); the synthetic classes are kept in HBM as uint8 and cropped in place.  ``--augment-seed`` seeds the draws.
+``--augment none`` (the default) is the squash to ``--image-size`` on the host, as before.
+
+Not built (follow-ups): ``--gpus N``, ``--use-graph`` and cropping out of the decode-once frame cache.
 """
 import argparse
 import datetime
@@ -51,6 +58,19 @@ class SyntheticClasses:
         return self.x[i], self.t[i]
 
     get_example = __getitem__
+
+
+class Arguments(argparse.Namespace):
+    """The options of the input pipeline are read from here where the command line does not give them: a namespace parsed from
+    a command line without them holds exactly the options of a ``--augment none`` run, and ``run`` writes the ones it ran with
+    into it (and so into the first log entry, beside the other arguments)."""
+    augment = 'none'
+    rrc_scale = (0.08, 1.0)
+    rrc_ratio = (3 / 4, 4 / 3)
+    val_crop_pct = 0.875
+    augment_seed = None
+
+    _PIPELINE = ('augment', 'rrc_scale', 'rrc_ratio', 'val_crop_pct', 'augment_seed')
 
 
 def parse_args(argv=None):
@@ -86,7 +106,13 @@ def parse_args(argv=None):
     parser.add_argument("--data-seed", type=int, default=10, help="seed of the synthetic set")
     parser.add_argument("--flat-log-dir", action='store_true', help="write into --log-dir itself (no <time>_<name> sub-directory)")
     parser.add_argument("--loader-threads", type=int, default=4, help="decode threads per iterator")
-    return parser.parse_args(argv)
+    # the input pipeline
+    parser.add_argument("--augment", default=argparse.SUPPRESS, choices=['none', 'rrc'], help="none: squash every frame to --image-size on the host; rrc: random-resized-crop + mirror (training) and centre crop (validation) on the GPU")
+    parser.add_argument("--rrc-scale", type=float, nargs=2, default=argparse.SUPPRESS, metavar=('LO', 'HI'), help="area fraction of a random-resized-crop (default 0.08 1)")
+    parser.add_argument("--rrc-ratio", type=float, nargs=2, default=argparse.SUPPRESS, metavar=('LO', 'HI'), help="aspect ratio (width / height) of a random-resized-crop (default 3/4 4/3)")
+    parser.add_argument("--val-crop-pct", type=float, default=argparse.SUPPRESS, help="side of the validation centre crop as a fraction of the largest fitting box (default 0.875)")
+    parser.add_argument("--augment-seed", type=int, default=argparse.SUPPRESS, help="seed of the crop / mirror draws")
+    return parser.parse_args(argv, namespace=Arguments())
 
 
 def scheduled_lr(base, epoch, drop_epochs, factor):
@@ -134,6 +160,22 @@ def build_datasets(args):
     return train, validation
 
 
+def build_crop_datasets(args, device):
+    """(train, validation or None) of ``--augment rrc``: datasets that finish their batches on ``device``"""
+    from loans_amd.common.datasets.classification_dataset import ClassificationImageDataset, ResidentClassificationSource
+    crops = dict(image_size=tuple(args.image_size), scale=tuple(args.rrc_scale), ratio=tuple(args.rrc_ratio),
+                 crop_pct=args.val_crop_pct, augment_seed=args.augment_seed)
+
+    def dataset(path, n, split, train):
+        if path == SYNTHETIC:
+            x, t = synthetic.make_classification_set(args.data_seed, n, args.synthetic_classes, args.image_size[0], args.image_size[1], split=split)
+            return ResidentClassificationSource.from_float_chw(x, t, device, train=train, **crops)
+        return ClassificationImageDataset(path, os.path.dirname(path), train=train, **crops)
+
+    train = dataset(args.train_file, args.dataset_size, 0, True)
+    return train, (dataset(args.val_file, args.validation_size, 1, False) if args.validation else None)
+
+
 def converter(batch, device=None):
     """(frames (B,3,H,W) float32, labels (B,) int32) on the device; a label read from a file is a one-element row"""
     images, labels = training.concat_examples(batch, device)[:2]
@@ -145,9 +187,17 @@ def run(args, log=print):
     if args.gpu < 0:
         args.gpu = torch.cuda.current_device()
     torch.cuda.set_device(args.gpu)
+    for name in Arguments._PIPELINE:             # the values this run uses, logged with the other arguments
+        setattr(args, name, getattr(args, name, getattr(Arguments, name)))
 
-    train_dataset, validation_dataset = build_datasets(args)
-    train_iter = training.MultithreadIterator(train_dataset, args.batch_size, shuffle=not args.no_shuffle, n_threads=args.loader_threads)
+    # --augment rrc: the iterators hand out (frames, labels) already resident on the device
+    feed, batch_converter = {}, converter
+    if args.augment == 'rrc':
+        train_dataset, validation_dataset = build_crop_datasets(args, torch.device('cuda', args.gpu))
+        feed, batch_converter = {'device': args.gpu}, training.identity_converter
+    else:
+        train_dataset, validation_dataset = build_datasets(args)
+    train_iter = training.MultithreadIterator(train_dataset, args.batch_size, shuffle=not args.no_shuffle, n_threads=args.loader_threads, **feed)
 
     model = build_model(args)
     localizer = model.predictor
@@ -162,12 +212,12 @@ def run(args, log=print):
     optimizer.setup(model)
     topk = 'accuracy_top%d' % model.topk if model.topk is not None else None
     train_keys = ('loss', 'accuracy') + ((topk,) if topk else ())
-    updater = training.StandardUpdater(train_iter, optimizer, converter=converter, device=args.gpu)
+    updater = training.StandardUpdater(train_iter, optimizer, converter=batch_converter, device=args.gpu)
 
     evaluator = None
     if validation_dataset is not None:
         validation_iter = training.MultithreadIterator(validation_dataset, args.batch_size, repeat=False, shuffle=False,
-                                                       n_threads=args.loader_threads)
+                                                       n_threads=args.loader_threads, **feed)
 
         def eval_func(x, t):
             with loans_amd.using_config('train', False), loans_amd.using_config('enable_backprop', False):
@@ -177,7 +227,7 @@ def run(args, log=print):
                 result['validation/' + topk] = float(model.accuracy_topk.data)
             return result
 
-        evaluator = training.Evaluator(validation_iter, model, converter=converter, device=args.gpu, eval_func=eval_func)
+        evaluator = training.Evaluator(validation_iter, model, converter=batch_converter, device=args.gpu, eval_func=eval_func)
 
     if not args.flat_log_dir:
         args.log_dir = os.path.join(args.log_dir, "{}_{}".format(datetime.datetime.now().isoformat(), args.ln))
