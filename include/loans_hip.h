@@ -577,6 +577,14 @@ int loans_softmax_xent_fwd_f32(const float* z, const int32_t* t, float* gz, floa
 int loans_softmax_xent_ls_fwd_f32(const float* z, const int32_t* t, float* gz, float* row_loss, float* row_hit,
                                   float* row_hitk, float* out /* [3] */, int32_t B, int32_t N, double eps, int32_t k,
                                   void* stream);
+/* Evaluation: the plain loss (eps = 0), the top-1 and the top-k hit of every row as defined above, summed into running totals;
+ * no gradient is written.  rows: 3 * B floats of scratch (row loss, hit, top-k hit).  acc[5], doubles, read-modify-write:
+ * acc[0] += sum of row losses, acc[1] += top-1 hits, acc[2] += top-k hits, acc[3] += rows not ignored, acc[4] += B.  The five sums
+ * of the batch are formed in double in a fixed order and added by one thread: no atomics, two runs give the same bits.
+ * Limits as above, k >= 1. */
+int loans_softmax_xent_eval_f32(const float* z, const int32_t* t, float* rows /* scratch, 3*B floats */,
+                                double* acc /* 5 doubles, read-modify-write */,
+                                int32_t B, int32_t N, int32_t k, void* stream);
 /* y[i] = x[i] * s[0], s on the device (the loss's upstream gradient times gz) */
 int loans_scale_by_scalar_f32(const float* x, const float* s, float* y, int64_t n, void* stream);
 /* y = x * mask (elementwise, n floats) -- RotationDropout forward/backward (functions/rotation_droput.py:26-48) */

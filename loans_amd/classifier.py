@@ -6,8 +6,8 @@ runs), ``topk=k`` also reports ``accuracy_top<k>``; with neither, the loss funct
 import torch
 
 from . import ops
-from .functions.ops_small import softmax_cross_entropy_with_accuracy, softmax_cross_entropy_with_topk_accuracy
-from .runtime.core import Chain, Variable, config, report
+from .functions.ops_small import _as_labels, softmax_cross_entropy_with_accuracy, softmax_cross_entropy_with_topk_accuracy
+from .runtime.core import Chain, Variable, config, report, using_config
 
 
 class Classifier(Chain):
@@ -34,8 +34,7 @@ class Classifier(Chain):
             if hasattr(link, 'materialize_head'):
                 link.materialize_head()
 
-    def __call__(self, *args):
-        *xs, t = args
+    def _predict(self, *xs):
         if self._arena is None:
             self.materialize()
         first = xs[0].data if isinstance(xs[0], Variable) else xs[0]
@@ -44,6 +43,18 @@ class Classifier(Chain):
         for link in self.predictor.links():         # a predictor that finalises itself (the localizers do) finds this arena
             link.__dict__['_arena'] = arena
         self.y = self.predictor(*xs)
+        return self.y
+
+    def evaluate(self, x, t, metrics):
+        """A test-mode forward without backprop whose logits go into ``metrics`` (``ClassificationMetrics.add``: one launch, no
+        host synchronisation).  No loss function runs, no gradient is written, nothing is reported."""
+        with using_config('train', False), using_config('enable_backprop', False):
+            self._predict(x)
+        metrics.add(self.y, t)
+
+    def __call__(self, *args):
+        *xs, t = args
+        self._predict(*xs)
         if self.label_smoothing == 0.0 and self.topk is None:
             self.loss, self.accuracy = softmax_cross_entropy_with_accuracy(self.y, t)
             report({'loss': self.loss, 'accuracy': self.accuracy}, self)
@@ -54,3 +65,42 @@ class Classifier(Chain):
         if self.topk is not None:
             report({'accuracy_top%d' % self.topk: self.accuracy_topk}, self)
         return self.loss
+
+
+class ClassificationMetrics:
+    """Running sums of a classification pass in five doubles on the device: the sum of the row losses (plain cross-entropy), the
+    top-1 hits, the top-``topk`` hits, the rows with a label and the rows.  ``add`` is one kernel call that synchronises nothing;
+    ``result`` sums over the ranks of a communicator and reads the five numbers -- the only host synchronisation of a pass.
+    Sums, not means of batch means: a ragged last batch and shards of different lengths weigh what they hold.  The loss divides
+    by the rows with a label, the accuracies by all rows, as the loss kernels do per batch."""
+
+    def __init__(self, topk=None, device=None):
+        if topk is not None and topk < 1:
+            raise ValueError('topk must be at least 1')
+        self.topk, self.device, self.acc = topk, (torch.device(device) if device is not None else None), None
+
+    def reset(self, device=None):
+        if self.acc is None:
+            device = self.device or device or torch.device('cuda', torch.cuda.current_device())
+            self.acc = torch.zeros(5, device=device, dtype=torch.float64)
+        else:
+            self.acc.zero_()
+
+    def add(self, logits, labels):
+        z = logits.data if isinstance(logits, Variable) else logits
+        if self.acc is None:
+            self.reset(z.device)
+        ops.softmax_xent_eval(z.contiguous(), _as_labels(z, labels).data.reshape(-1).contiguous(), self.acc, self.topk or 1)
+
+    def result(self, comm=None):
+        if self.acc is None:
+            self.reset()
+        total = self.acc
+        if comm is not None and comm.active:
+            total = comm.allreduce_sum(total.clone())
+        loss, hits, hitsk, valid, rows = total.tolist()
+        out = {'loss': loss / max(valid, 1), 'accuracy': hits / max(rows, 1)}
+        if self.topk:
+            out['accuracy_top%d' % self.topk] = hitsk / max(rows, 1)
+        out['rows'], out['valid'] = int(rows), int(valid)
+        return out

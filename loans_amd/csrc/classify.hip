@@ -1,6 +1,6 @@
 // The ImageNet classification head: a wide Linear layer (9 .. 2^16 outputs) in three directions on the fp32 matrix cores
 // (v_mfma_f32_32x32x2_f32), and softmax cross-entropy with top-1 accuracy in one pass over the logits (and its label-smoothed
-// form with a top-k hit).
+// form with a top-k hit), and the evaluation form that writes no gradient and adds the batch to running sums in double.
 // No atomics anywhere in this file: every output element is owned by one lane (GEMM) or one block (loss rows) and is summed
 // in an order that depends on the shape alone, so two launches on the same inputs give the same bits.
 #include "common.h"
@@ -104,26 +104,13 @@ __device__ __forceinline__ int block_count_256(int v, int* sh) {
     return sh[0] + sh[1] + sh[2] + sh[3];
 }
 
-// one block per row; the row is read from memory once and kept in LDS (dynamic, N floats)
-//   m = max z, first index wins a tie;  S = sum exp(z - m);  lse = m + log S;  loss = lse - z[t]
-//   gz = (exp(z - m) / S - onehot) / count        count = max(#rows with a label in [0, N), 1)
-// rows whose label is outside [0, N) (-1 = ignore_label; anything else out of range is treated the same way): loss 0, gz 0.
-__global__ __launch_bounds__(256) void softmax_xent_rows_kernel(const float* __restrict__ z, const int* __restrict__ t,
-                                                                float* __restrict__ gz, float* __restrict__ row_loss,
-                                                                float* __restrict__ row_hit, int B, int N) {
-    extern __shared__ __attribute__((aligned(16))) float row[];
-    __shared__ float shf[4];
-    __shared__ int shi[4];
-    const int tid = threadIdx.x, b = blockIdx.x;
-    const float* zr = z + (int64_t)b * N;
-    float* gr = gz + (int64_t)b * N;
-
-    int valid = 0;
-    for (int i = tid; i < B; i += 256) valid += (unsigned)t[i] < (unsigned)N;
-    const int count = max(block_count_256(valid, shi), 1);
-
-    float m = -INFINITY;
-    int am = 0x7fffffff;
+// ---- one row of logits, shared by the three row kernels below (256 threads, the row kept in LDS) -----------------------------
+// stage zr[0 .. N) into row[] and leave its maximum and the first index that holds it in every thread
+__device__ __forceinline__ void row_stage_argmax(const float* __restrict__ zr, float* row, int N, float* shf, int* shi,
+                                                 float& m, int& am) {
+    const int tid = threadIdx.x;
+    m = -INFINITY;
+    am = 0x7fffffff;
     for (int i = tid; i < N; i += 256) {
         const float v = zr[i];
         row[i] = v;
@@ -145,6 +132,46 @@ __global__ __launch_bounds__(256) void softmax_xent_rows_kernel(const float* __r
         const int oa = shi[w];
         if (oa != 0x7fffffff && (am == 0x7fffffff || om > m || (om == m && oa < am))) { m = om; am = oa; }
     }
+}
+
+// S = sum exp(row - m), in the fixed tree
+__device__ __forceinline__ float row_sum_exp(const float* row, int N, float m, float* shf) {
+    float s = 0.f;
+    for (int i = threadIdx.x; i < N; i += 256) s += expf(row[i] - m);
+    return block_sum_256(s, shf);
+}
+
+// #{ j : row_j > zt or (row_j == zt and j < label) }: the label's place in the row, 0 = first
+__device__ __forceinline__ int row_rank(const float* row, int N, int label, float zt, int* shi) {
+    int ahead = 0;
+    for (int i = threadIdx.x; i < N; i += 256) {
+        const float v = row[i];
+        ahead += (v > zt) || (v == zt && i < label);
+    }
+    return block_count_256(ahead, shi);
+}
+
+// one block per row; the row is read from memory once and kept in LDS (dynamic, N floats)
+//   m = max z, first index wins a tie;  S = sum exp(z - m);  lse = m + log S;  loss = lse - z[t]
+//   gz = (exp(z - m) / S - onehot) / count        count = max(#rows with a label in [0, N), 1)
+// rows whose label is outside [0, N) (-1 = ignore_label; anything else out of range is treated the same way): loss 0, gz 0.
+__global__ __launch_bounds__(256) void softmax_xent_rows_kernel(const float* __restrict__ z, const int* __restrict__ t,
+                                                                float* __restrict__ gz, float* __restrict__ row_loss,
+                                                                float* __restrict__ row_hit, int B, int N) {
+    extern __shared__ __attribute__((aligned(16))) float row[];
+    __shared__ float shf[4];
+    __shared__ int shi[4];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const float* zr = z + (int64_t)b * N;
+    float* gr = gz + (int64_t)b * N;
+
+    int valid = 0;
+    for (int i = tid; i < B; i += 256) valid += (unsigned)t[i] < (unsigned)N;
+    const int count = max(block_count_256(valid, shi), 1);
+
+    float m;
+    int am;
+    row_stage_argmax(zr, row, N, shf, shi, m, am);
 
     const int label = t[b];
     if (tid == 0) row_hit[b] = (am == label) ? 1.f : 0.f;
@@ -153,9 +180,7 @@ __global__ __launch_bounds__(256) void softmax_xent_rows_kernel(const float* __r
         if (tid == 0) row_loss[b] = 0.f;
         return;
     }
-    float s = 0.f;
-    for (int i = tid; i < N; i += 256) s += expf(row[i] - m);
-    const float S = block_sum_256(s, shf);
+    const float S = row_sum_exp(row, N, m, shf);
     if (tid == 0) row_loss[b] = (m + logf(S)) - row[label];
     const float fc = (float)count;
     for (int i = tid; i < N; i += 256) {
@@ -206,29 +231,9 @@ __global__ __launch_bounds__(256) void softmax_xent_ls_rows_kernel(const float* 
     for (int i = tid; i < B; i += 256) valid += (unsigned)t[i] < (unsigned)N;
     const int count = max(block_count_256(valid, shi), 1);
 
-    float m = -INFINITY;
-    int am = 0x7fffffff;
-    for (int i = tid; i < N; i += 256) {
-        const float v = zr[i];
-        row[i] = v;
-        if (v > m || am == 0x7fffffff) { m = v; am = i; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float om = __shfl_xor(m, o, 64);
-        const int oa = __shfl_xor(am, o, 64);
-        if (oa != 0x7fffffff && (am == 0x7fffffff || om > m || (om == m && oa < am))) { m = om; am = oa; }
-    }
-    __syncthreads();
-    if ((tid & 63) == 0) { shf[tid >> 6] = m; shi[tid >> 6] = am; }
-    __syncthreads();
-    m = shf[0]; am = shi[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-        const float om = shf[w];
-        const int oa = shi[w];
-        if (oa != 0x7fffffff && (am == 0x7fffffff || om > m || (om == m && oa < am))) { m = om; am = oa; }
-    }
+    float m;
+    int am;
+    row_stage_argmax(zr, row, N, shf, shi, m, am);
 
     const int label = t[b];
     if (tid == 0) row_hit[b] = (am == label) ? 1.f : 0.f;
@@ -238,17 +243,10 @@ __global__ __launch_bounds__(256) void softmax_xent_ls_rows_kernel(const float* 
         return;
     }
     const float zt = row[label];
-    int ahead = 0;
-    for (int i = tid; i < N; i += 256) {
-        const float v = row[i];
-        ahead += (v > zt) || (v == zt && i < label);
-    }
-    const int rank = block_count_256(ahead, shi);
+    const int rank = row_rank(row, N, label, zt, shi);
     if (tid == 0) row_hitk[b] = (rank < ls.k) ? 1.f : 0.f;
 
-    float s = 0.f;
-    for (int i = tid; i < N; i += 256) s += expf(row[i] - m);
-    const float S = block_sum_256(s, shf);
+    const float S = row_sum_exp(row, N, m, shf);
     const float fc = (float)count;
     if (ls.eps == 0.f) {
         if (tid == 0) row_loss[b] = (m + logf(S)) - zt;
@@ -288,6 +286,68 @@ __global__ __launch_bounds__(256) void softmax_xent_ls_reduce_kernel(const float
     const float A = block_sum_256(a, shf);
     const float AK = block_sum_256(ak, shf);
     if (tid == 0) { out[0] = L / (float)count; out[1] = A / (float)B; out[2] = AK / (float)B; }
+}
+
+// Evaluation (loans_softmax_xent_eval_f32): the plain loss, the top-1 and the top-k hit of every row -- the eps == 0 expressions
+// of softmax_xent_ls_rows_kernel on the same row code -- and no gradient.  rows: [0, B) loss, [B, 2B) hit, [2B, 3B) top-k hit.
+__global__ __launch_bounds__(256) void softmax_xent_eval_rows_kernel(const float* __restrict__ z, const int* __restrict__ t,
+                                                                     float* __restrict__ rows, int B, int N, int k) {
+    extern __shared__ __attribute__((aligned(16))) float row[];
+    __shared__ float shf[4];
+    __shared__ int shi[4];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    float m;
+    int am;
+    row_stage_argmax(z + (int64_t)b * N, row, N, shf, shi, m, am);
+    const int label = t[b];
+    if ((unsigned)label >= (unsigned)N) {       // ignored row (uniform per block)
+        if (tid == 0) { rows[b] = 0.f; rows[B + b] = 0.f; rows[2 * B + b] = 0.f; }
+        return;
+    }
+    const float zt = row[label];
+    const int rank = row_rank(row, N, label, zt, shi);
+    const float S = row_sum_exp(row, N, m, shf);
+    if (tid == 0) {
+        rows[b] = (m + logf(S)) - zt;
+        rows[B + b] = (am == label) ? 1.f : 0.f;
+        rows[2 * B + b] = (rank < k) ? 1.f : 0.f;
+    }
+}
+
+__device__ __forceinline__ double block_sum_256_d(double v, double* sh) {
+    v = wave_sum_d(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+// acc[0] += sum row loss (in double, the fixed tree), acc[1] += hits, acc[2] += top-k hits, acc[3] += valid rows, acc[4] += B:
+// one block, thread 0 alone touches acc
+__global__ __launch_bounds__(256) void softmax_xent_eval_reduce_kernel(const float* __restrict__ rows, const int* __restrict__ t,
+                                                                       double* __restrict__ acc, int B, int N) {
+    __shared__ double shd[4];
+    __shared__ int shi[4];
+    const int tid = threadIdx.x;
+    int valid = 0, h = 0, hk = 0;
+    double l = 0.0;
+    for (int i = tid; i < B; i += 256) {
+        valid += (unsigned)t[i] < (unsigned)N;
+        l += (double)rows[i];
+        h += rows[B + i] != 0.f;
+        hk += rows[2 * B + i] != 0.f;
+    }
+    const double L = block_sum_256_d(l, shd);
+    const int H = block_count_256(h, shi);
+    const int HK = block_count_256(hk, shi);
+    const int V = block_count_256(valid, shi);
+    if (tid == 0) {
+        acc[0] += L;
+        acc[1] += (double)H;
+        acc[2] += (double)HK;
+        acc[3] += (double)V;
+        acc[4] += (double)B;
+    }
 }
 
 __global__ __launch_bounds__(256) void scale_by_scalar_kernel(const float* __restrict__ x, const float* __restrict__ s,
@@ -367,6 +427,18 @@ extern "C" int loans_softmax_xent_ls_fwd_f32(const float* z, const int32_t* t, f
                        row_hitk, B, N, ls);
     LOANS_LAUNCH_CHECK();
     hipLaunchKernelGGL(softmax_xent_ls_reduce_kernel, dim3(1), dim3(256), 0, st, row_loss, row_hit, row_hitk, t, out, B, N);
+    LOANS_LAUNCH_CHECK();
+    return LOANS_OK;
+}
+
+extern "C" int loans_softmax_xent_eval_f32(const float* z, const int32_t* t, float* rows, double* acc, int32_t B, int32_t N,
+                                           int32_t k, void* stream) {
+    if (!z || !t || !rows || !acc || B <= 0 || N <= 0 || k < 1) return LOANS_EINVAL;
+    if (N > XENT_MAX_N || B > XENT_MAX_B) return LOANS_ERANGE;
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(softmax_xent_eval_rows_kernel, dim3(B), dim3(256), (size_t)N * sizeof(float), st, z, t, rows, B, N, k);
+    LOANS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(softmax_xent_eval_reduce_kernel, dim3(1), dim3(256), 0, st, rows, t, acc, B, N);
     LOANS_LAUNCH_CHECK();
     return LOANS_OK;
 }

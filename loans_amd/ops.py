@@ -2470,6 +2470,22 @@ def softmax_xent_ls_fwd(z, t, eps, k):
     return out, gz, row_loss, row_hit, row_hitk
 
 
+def softmax_xent_eval(z, t, acc, k=1):
+    """Evaluation: add the batch's plain loss sum, top-1 hits, top-k hits, valid rows and rows to ``acc`` (5 float64 on the
+    device, read-modify-write).  No gradient is written.  No host synchronisation."""
+    assert z.dtype == torch.float32 and z.dim() == 2 and z.is_contiguous(), 'logits must be a contiguous (B, N) fp32 array'
+    assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == z.shape[0] and t.device == z.device, \
+        'labels must be int32, one per row, on the logits\' device'
+    assert acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() >= 5 and acc.device == z.device, \
+        'the accumulator is 5 float64 on the logits\' device'
+    B, N = z.shape
+    rows = _empty((3 * B,), device=z.device, dtype=torch.float32)
+    if CLASS_COUNT is not None: _acct('heads', 0, _nbytes(z), _nbytes(rows))
+    check(_lib.load().loans_softmax_xent_eval_f32(_ptr(z), _ptr(t), _ptr(rows), _ptr(acc), B, N, int(k), _stream()),
+          'loans_softmax_xent_eval_f32')
+    return acc
+
+
 def scale_by_scalar(x, s):
     """x * s[0] with s a one-element device tensor"""
     assert s.dtype == torch.float32 and s.numel() == 1 and s.device == x.device

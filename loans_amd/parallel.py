@@ -38,10 +38,24 @@ class Communicator:
             return
         arena = link.arena or link.finalize()
         dist.broadcast(arena.data, src=0, group=self.group)
+        self.bcast_persistents(link)
+
+    def bcast_persistents(self, link):
+        """Rank 0's persistents (the BN running statistics) to everyone: the second half of ``bcast_data``, and what a
+        validation pass calls first so that every rank evaluates the model rank 0 writes into its snapshot."""
+        if not self.active:
+            return
         for _, l, n in link.namedpersistents():
             v = getattr(l, n)
             if torch.is_tensor(v):
                 dist.broadcast(v, src=0, group=self.group)
+
+    def allreduce_sum(self, tensor):
+        """Sum ``tensor`` over all ranks, in place (any dtype the backend carries: the float64 metric sums travel through it);
+        returns it.  Without an active communicator it stays as it is."""
+        if self.active:
+            dist.all_reduce(tensor, op=dist.ReduceOp.SUM, group=self.group)
+        return tensor
 
     def allreduce_grad(self, arena, async_op=False):
         """Sum the gradient arena over all ranks, in place, in large buckets.  ``async_op``: return the work handles

@@ -27,20 +27,45 @@ own stream, crops, mirrors, resizes and writes ``/ 255`` float32 CHW (loans_amd/
 csrc/croprs.hip); the synthetic classes are kept in HBM as uint8 and cropped in place.  ``--augment-seed`` seeds the draws.
 ``--augment none`` (the default) is the squash to ``--image-size`` on the host, as before.
 
-Not built (follow-ups): ``--gpus N``, ``--use-graph`` and cropping out of the decode-once frame cache.
+``--gpus N`` trains data parallel on N GPUs of the node, one process per GPU (loans_amd/launch.py forks them; under a
+launcher of your own -- ``RANK`` / ``WORLD_SIZE`` set -- the script is a rank).  Every rank builds the same dataset and takes
+every N-th example of it (loans_amd/common/datasets/shard.py: the training share padded by wrapping, so that all ranks make the
+same iterations; the validation share not, so that every example counts once); gradients are summed over the ranks and
+averaged in the optimiser's kernel.  ``-b`` is the batch PER GPU -- a step sees N x b frames -- and ``--lr`` is the rate of the
+whole run: nothing is scaled automatically.  ``--warmup-epochs E`` ramps the rate linearly from ``--warmup-start-factor`` times
+the scheduled rate at the start to the scheduled rate at epoch E, the gradual warm-up large batches need.  Validation under
+``--gpus N`` (and with ``--validation-sums`` in one process) sums loss and hits over all examples on the device
+(``ClassificationMetrics``: no host synchronisation per batch, a ragged last batch weighs what it holds), after rank 0's BN
+running statistics went to every rank; its entries also carry ``validation/rows`` and ``validation/valid`` under ``--gpus N``.
+Rank 0 alone prints, logs and writes snapshots.
+
+Not built (follow-ups): ``--use-graph`` and cropping out of the decode-once frame cache.
 """
-import argparse
-import datetime
-import json
 import os
-import time
 
-import numpy as np
-import torch
+if __name__ == "__main__":
+    # `--gpus N` (N > 1) outside a launcher: fork the N ranks as a child process group before anything touches the GPU; does
+    # not return
+    import importlib.util
+    _spec = importlib.util.spec_from_file_location(
+        '_loans_launch', os.path.join(os.path.dirname(os.path.abspath(__file__)), 'loans_amd', 'launch.py'))
+    _launch = importlib.util.module_from_spec(_spec)
+    _spec.loader.exec_module(_launch)
+    _launch.launch_if_parent(os.path.abspath(__file__))
 
-import loans_amd
-from loans_amd.datasets import synthetic
-from loans_amd.runtime import training
+import argparse             # noqa: E402
+import datetime             # noqa: E402
+import json                 # noqa: E402
+import time                 # noqa: E402
+
+import numpy as np          # noqa: E402
+import torch                # noqa: E402
+
+import loans_amd            # noqa: E402
+from loans_amd import parallel                                      # noqa: E402
+from loans_amd.common.datasets.shard import ShardedDataset          # noqa: E402
+from loans_amd.datasets import synthetic                            # noqa: E402
+from loans_amd.runtime import training                              # noqa: E402
 
 SYNTHETIC = 'synthetic'
 
@@ -70,7 +95,14 @@ class Arguments(argparse.Namespace):
     val_crop_pct = 0.875
     augment_seed = None
 
+    # data parallel
+    gpus = 1
+    warmup_epochs = 0.0
+    warmup_start_factor = 0.1
+    validation_sums = False
+
     _PIPELINE = ('augment', 'rrc_scale', 'rrc_ratio', 'val_crop_pct', 'augment_seed')
+    _PARALLEL = ('gpus', 'warmup_epochs', 'warmup_start_factor', 'validation_sums')
 
 
 def parse_args(argv=None):
@@ -112,6 +144,11 @@ def parse_args(argv=None):
     parser.add_argument("--rrc-ratio", type=float, nargs=2, default=argparse.SUPPRESS, metavar=('LO', 'HI'), help="aspect ratio (width / height) of a random-resized-crop (default 3/4 4/3)")
     parser.add_argument("--val-crop-pct", type=float, default=argparse.SUPPRESS, help="side of the validation centre crop as a fraction of the largest fitting box (default 0.875)")
     parser.add_argument("--augment-seed", type=int, default=argparse.SUPPRESS, help="seed of the crop / mirror draws")
+    # data parallel
+    parser.add_argument("--gpus", type=int, default=argparse.SUPPRESS, help="train data parallel on this many GPUs of the node, one process each (-b is the batch per GPU)")
+    parser.add_argument("--warmup-epochs", type=float, default=argparse.SUPPRESS, help="ramp the rate linearly up to the scheduled one over this many epochs (default 0: off)")
+    parser.add_argument("--warmup-start-factor", type=float, default=argparse.SUPPRESS, help="fraction of the scheduled rate the warm-up starts from (default 0.1)")
+    parser.add_argument("--validation-sums", action='store_true', default=argparse.SUPPRESS, help="validate by summing loss and hits over all examples on the device (always on with --gpus N)")
     return parser.parse_args(argv, namespace=Arguments())
 
 
@@ -119,6 +156,14 @@ def scheduled_lr(base, epoch, drop_epochs, factor):
     """the stepped rate of ``epoch``: ``base`` times ``factor`` once per listed epoch that has begun -- a pure function, so a
     resumed run and a fresh one agree"""
     return base * factor ** sum(1 for e in set(drop_epochs) if e <= epoch)
+
+
+def warmup_factor(epoch_detail, warmup_epochs, start_factor):
+    """the factor of the gradual warm-up at ``epoch_detail`` (epochs done, fractional): linear from ``start_factor`` at 0 to 1 at
+    ``warmup_epochs``, 1 from there on and without a warm-up -- a pure function, like ``scheduled_lr``, which it multiplies"""
+    if warmup_epochs <= 0 or epoch_detail >= warmup_epochs:
+        return 1.0
+    return start_factor + (1.0 - start_factor) * max(epoch_detail, 0.0) / warmup_epochs
 
 
 def resolved_topk(args):
@@ -160,11 +205,13 @@ def build_datasets(args):
     return train, validation
 
 
-def build_crop_datasets(args, device):
-    """(train, validation or None) of ``--augment rrc``: datasets that finish their batches on ``device``"""
+def build_crop_datasets(args, device, rank=0):
+    """(train, validation or None) of ``--augment rrc``: datasets that finish their batches on ``device``.  Rank r of a data
+    parallel run draws its crops from the stream of ``--augment-seed`` + 7919 r."""
     from loans_amd.common.datasets.classification_dataset import ClassificationImageDataset, ResidentClassificationSource
     crops = dict(image_size=tuple(args.image_size), scale=tuple(args.rrc_scale), ratio=tuple(args.rrc_ratio),
-                 crop_pct=args.val_crop_pct, augment_seed=args.augment_seed)
+                 crop_pct=args.val_crop_pct,
+                 augment_seed=None if args.augment_seed is None else args.augment_seed + 7919 * rank)
 
     def dataset(path, n, split, train):
         if path == SYNTHETIC:
@@ -184,19 +231,29 @@ def converter(batch, device=None):
 
 def run(args, log=print):
     """The training loop.  Returns (log entries, model)."""
-    if args.gpu < 0:
+    comm = parallel.init_from_env()
+    if comm.size > 1:
+        args.gpu = int(os.environ.get('LOCAL_RANK', '0')) % torch.cuda.device_count()
+    elif args.gpu < 0:
         args.gpu = torch.cuda.current_device()
     torch.cuda.set_device(args.gpu)
-    for name in Arguments._PIPELINE:             # the values this run uses, logged with the other arguments
+    for name in Arguments._PIPELINE + Arguments._PARALLEL:      # the values this run uses, logged with the other arguments
         setattr(args, name, getattr(args, name, getattr(Arguments, name)))
+    args.gpus = comm.size
+    chief = comm.rank == 0                       # prints, logs and writes snapshots
 
     # --augment rrc: the iterators hand out (frames, labels) already resident on the device
     feed, batch_converter = {}, converter
     if args.augment == 'rrc':
-        train_dataset, validation_dataset = build_crop_datasets(args, torch.device('cuda', args.gpu))
+        train_dataset, validation_dataset = build_crop_datasets(args, torch.device('cuda', args.gpu), comm.rank)
         feed, batch_converter = {'device': args.gpu}, training.identity_converter
     else:
         train_dataset, validation_dataset = build_datasets(args)
+    # every rank built the same sets and takes every comm.size-th example: the training share padded by wrapping (all ranks make
+    # the same iterations and epochs), the validation share not (every example is counted once; shares may differ by one)
+    train_dataset = ShardedDataset(train_dataset, comm.rank, comm.size, pad=True)
+    if validation_dataset is not None:
+        validation_dataset = ShardedDataset(validation_dataset, comm.rank, comm.size, pad=False)
     train_iter = training.MultithreadIterator(train_dataset, args.batch_size, shuffle=not args.no_shuffle, n_threads=args.loader_threads, **feed)
 
     model = build_model(args)
@@ -204,17 +261,20 @@ def run(args, log=print):
     if args.dtype == 'bf16':
         model.set_precision('bf16', 'bf16')
     model.to_gpu(args.gpu)
+    comm.bcast_data(model)
 
     if args.optimizer == 'sgd':
         optimizer, rate_name = loans_amd.MomentumSGD(lr=args.learning_rate, momentum=args.momentum, weight_decay_rate=args.weight_decay), 'lr'
     else:
         optimizer, rate_name = loans_amd.Adam(alpha=args.learning_rate, weight_decay_rate=args.weight_decay), 'alpha'
     optimizer.setup(model)
+    parallel.create_multi_node_optimizer(optimizer, comm)
     topk = 'accuracy_top%d' % model.topk if model.topk is not None else None
     train_keys = ('loss', 'accuracy') + ((topk,) if topk else ())
-    updater = training.StandardUpdater(train_iter, optimizer, converter=batch_converter, device=args.gpu)
+    updater = training.StandardUpdater(train_iter, optimizer, converter=batch_converter, device=args.gpu, comm=comm)
 
-    evaluator = None
+    evaluator = validate = None
+    summed = comm.size > 1 or args.validation_sums
     if validation_dataset is not None:
         validation_iter = training.MultithreadIterator(validation_dataset, args.batch_size, repeat=False, shuffle=False,
                                                        n_threads=args.loader_threads, **feed)
@@ -228,10 +288,34 @@ def run(args, log=print):
             return result
 
         evaluator = training.Evaluator(validation_iter, model, converter=batch_converter, device=args.gpu, eval_func=eval_func)
+        metrics = loans_amd.ClassificationMetrics(topk=model.topk, device=torch.device('cuda', args.gpu))
+
+        def summed_validation():
+            """loss and hits summed over every example of every share: rank 0's BN running statistics to all ranks (the ones
+            its snapshot holds), one launch per batch into the five doubles, no collective inside the loop -- the shares may
+            differ in length --, one all-reduce and one host synchronisation at the end"""
+            comm.bcast_persistents(model)
+            metrics.reset()
+            validation_iter.reset()
+            for batch in validation_iter:
+                x, t = batch_converter(batch, args.gpu)
+                model.evaluate(x, t, metrics)
+            total = metrics.result(comm)
+            result = {'validation/loss': total['loss'], 'validation/accuracy': total['accuracy']}
+            if topk:
+                result['validation/' + topk] = total[topk]
+            if comm.size > 1:
+                result.update({'validation/rows': total['rows'], 'validation/valid': total['valid']})
+            return result
+
+        validate = summed_validation if summed else evaluator.evaluate
 
     if not args.flat_log_dir:
-        args.log_dir = os.path.join(args.log_dir, "{}_{}".format(datetime.datetime.now().isoformat(), args.ln))
-    os.makedirs(args.log_dir, exist_ok=True)
+        stamp = datetime.datetime.now().isoformat() if comm.size == 1 else os.environ.get('TORCHELASTIC_RUN_ID', 'dp') + \
+            '_' + datetime.datetime.now().strftime('%Y-%m-%dT%H')
+        args.log_dir = os.path.join(args.log_dir, "{}_{}".format(stamp, args.ln))
+    if chief:
+        os.makedirs(args.log_dir, exist_ok=True)
     data_to_log = {'log_dir': args.log_dir, 'image_size': list(args.image_size), 'localizer': [localizer.__class__.__name__, 'localizer.py']}
     for argument in filter(lambda x: not x.startswith('_'), dir(args)):
         data_to_log[argument] = getattr(args, argument)
@@ -243,20 +327,30 @@ def run(args, log=print):
     t0 = time.time()
     it = 0
     while updater.epoch < args.num_epoch and (args.iterations is None or it < args.iterations):
-        lr = scheduled_lr(args.learning_rate, updater.epoch, args.lr_drop_epochs, args.lr_drop_factor)
+        lr = scheduled_lr(args.learning_rate, updater.epoch, args.lr_drop_epochs, args.lr_drop_factor) * \
+            warmup_factor(updater.epoch_detail, args.warmup_epochs, args.warmup_start_factor)
         setattr(optimizer, rate_name, lr)
         updater.update()
         it = updater.iteration
         last = (args.iterations is not None and it == args.iterations) or updater.epoch >= args.num_epoch
+        # LOCK STEP.  Everything below that holds a collective -- the mean of the training metrics, the validation pass -- and the
+        # end of this loop depend on `iteration`, `epoch`, `is_new_epoch` and the arguments alone, and those are the same on
+        # every rank: the padded training shares have one length, so every iterator makes the same (epoch, is_new_epoch)
+        # sequence.  A condition that read anything a rank computed for itself (a loss, a clock) would leave a peer waiting.
         if updater.is_new_epoch or it % args.log_interval == 0 or last:
             # the only host synchronisation of an iteration
             obs = loans_amd.reporter.observation
             entry = {'iteration': it, 'epoch': updater.epoch}
-            entry.update({k: float(obs[k]) for k in train_keys})
+            if comm.active:                     # equal batches per rank: the mean over ranks is the mean of the global batch
+                mean = torch.stack([getattr(obs[k], 'data', obs[k]).detach().reshape(()).to(torch.float64) for k in train_keys])
+                mean = (comm.allreduce_sum(mean) / comm.size).tolist()
+                entry.update(dict(zip(train_keys, mean)))
+            else:
+                entry.update({k: float(obs[k]) for k in train_keys})
             entry['lr'] = lr                    # the rate this iteration was stepped with
-            if evaluator is not None:
+            if validate is not None:
                 keep = {k: obs[k] for k in train_keys}
-                entry.update({k: v for k, v in evaluator.evaluate().items() if k.startswith('validation/')})
+                entry.update({k: v for k, v in validate().items() if k.startswith('validation/')})
                 loans_amd.report(keep)
             entry['elapsed_time'] = time.time() - t0
             top = '  top-%d %%.4f' % model.topk if topk else ''
@@ -265,26 +359,30 @@ def run(args, log=print):
                 val = '  validation loss %.5f accuracy %.4f' % (entry['validation/loss'], entry['validation/accuracy'])
                 if topk:
                     val += top % entry['validation/' + topk]
-            log('iteration %4d  epoch %d  lr %g  loss %.5f  accuracy %.4f%s%s  (%.1f s)' % (
-                it, updater.epoch, lr, entry['loss'], entry['accuracy'], top % entry[topk] if topk else '', val, entry['elapsed_time']))
+            if chief:
+                log('iteration %4d  epoch %d  lr %g  loss %.5f  accuracy %.4f%s%s  (%.1f s)' % (
+                    it, updater.epoch, lr, entry['loss'], entry['accuracy'], top % entry[topk] if topk else '', val, entry['elapsed_time']))
             if not log_entries:
                 entry.update(data_to_log)
             log_entries.append(entry)
-            with open(os.path.join(args.log_dir, 'log'), 'w') as f:
-                json.dump(log_entries, f, indent=4, default=str)
-        if it % args.snapshot_interval == 0:
+            if chief:
+                with open(os.path.join(args.log_dir, 'log'), 'w') as f:
+                    json.dump(log_entries, f, indent=4, default=str)
+        if chief and it % args.snapshot_interval == 0:
             loans_amd.save_npz(snapshot_path(it), localizer)
     train_iter.finalize()
     if evaluator is not None:
         validation_iter.finalize()
-    if not os.path.exists(snapshot_path(updater.iteration)):
-        loans_amd.save_npz(snapshot_path(updater.iteration), localizer)
-    log('snapshot: %s' % snapshot_path(updater.iteration))
+    if chief:
+        if not os.path.exists(snapshot_path(updater.iteration)):
+            loans_amd.save_npz(snapshot_path(updater.iteration), localizer)
+        log('snapshot: %s' % snapshot_path(updater.iteration))
     return log_entries, model
 
 
 def main(argv=None):
     run(parse_args(argv))
+    parallel.shutdown()
 
 
 if __name__ == "__main__":
