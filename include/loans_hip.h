@@ -724,6 +724,13 @@ typedef struct loans_crop_job {
 } loans_crop_job;
 int loans_crop_resize_u8_f32(const uint8_t* src, float* dst, const loans_crop_job* jobs, int32_t njobs,
                              const int32_t* tables, int32_t max_vks, int32_t outH, int32_t outW, void* stream);
+/* The same launch over SEVERAL source buffers (a batch that mixes frames resident in cache slabs with frames uploaded this
+ * moment): `srcs` is a DEVICE table of nsrcs base pointers, `src_index` a DEVICE array of njobs entries -- job n's src_off is
+ * relative to srcs[src_index[n]]; everything else as above, loans_crop_job unchanged.  A block reads its job's index once and
+ * writes nothing where it lies outside [0, nsrcs).  LOANS_EINVAL also for a null table or index array and for nsrcs <= 0. */
+int loans_crop_resize_srcs_u8_f32(const uint8_t* const* srcs, const int32_t* src_index, int32_t nsrcs, float* dst,
+                                  const loans_crop_job* jobs, int32_t njobs, const int32_t* tables, int32_t max_vks,
+                                  int32_t outH, int32_t outW, void* stream);
 /* output rows per block of that launch (host arithmetic only; <= 0 for non-positive sizes) */
 int loans_crop_band_rows(int32_t outH, int32_t outW);
 

@@ -121,6 +121,7 @@ SIGNATURES = {
     'loans_resize_ragged_u8_f32': [_p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p],
     'loans_u8hwc3_to_f32chw': [_p, _p, _i32, _i32, _i32, _p],
     'loans_crop_resize_u8_f32': [_p, _p, _p, _i32, _p, _i32, _i32, _i32, _p],
+    'loans_crop_resize_srcs_u8_f32': [_p, _p, _i32, _p, _p, _i32, _p, _i32, _i32, _i32, _p],
     'loans_crop_band_rows': [_i32, _i32],
     'loans_prep_images_f32': [_p, _p, _i32, _i32, _i32, _p],
     'loans_prep_images_dense_f32': [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p],

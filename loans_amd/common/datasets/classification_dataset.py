@@ -7,7 +7,10 @@ Pillow's crop + BILINEAR resize).
 that already lies in HBM as one uint8 [N][H][W][3] tensor -- its batches are cut straight out of that tensor, the only upload
 is the job table.  Both offer ``get_example`` (the host reference: Pillow) and ``decode_batch`` / ``finish_batch`` in the
 shape ``MultithreadIterator(device=...)`` expects; a finished batch is ``(frames [B][3][oh][ow] float32, labels [B] int32)``
-on the device."""
+on the device.
+
+``ClassificationImageDataset(cache=RaggedFrameCache(...))`` decodes a file once: from the second epoch on a batch is cut out of
+frames kept in HBM (or, in host mode, out of decoded arrays kept in host memory) -- only the draws change between epochs."""
 import csv
 import os
 import random
@@ -16,7 +19,8 @@ import numpy
 import torch
 from PIL import Image
 
-from .crop_resize import center_crop_box, crop_resize_device, crop_resize_host, sample_rrc_box
+from .crop_resize import center_crop_box, crop_resize_device, crop_resize_device_multi, crop_resize_host, sample_rrc_box
+from .frame_cache import CachedFrame
 
 
 class _CropDraws:
@@ -46,10 +50,17 @@ class _CropDraws:
         return self.finish_batch(self.decode_batch(indices, map_fn), device, map_fn)
 
 
+class FeedBatch(tuple):
+    """``(frames, labels)`` of a dataset with a frame cache, with what the cache did for it: ``cache_hits`` / ``cache_misses``
+    -- counted where the batch is consumed, the lookups themselves run batches ahead"""
+    cache_hits = cache_misses = 0
+
+
 class ClassificationImageDataset(_CropDraws):
 
     def __init__(self, pairs, root='.', image_size=(224, 224), train=True, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3),
-                 crop_pct=0.875, augment_seed=None):
+                 crop_pct=0.875, augment_seed=None, cache=None):
+        self.cache = cache          # a RaggedFrameCache (frame_cache.py) or None
         if isinstance(pairs, str):
             with open(pairs) as pairs_file:
                 pairs = [(pair[0], int(pair[1])) for pair in csv.reader(pairs_file, delimiter='\t') if pair]
@@ -82,17 +93,32 @@ class ClassificationImageDataset(_CropDraws):
         box, flip = self._draw(*frame.shape[:2])
         return crop_resize_host(frame, box, self.image_size, flip), numpy.int32(self._pairs[i][1])
 
-    def decode_batch(self, indices, map_fn=map, farm=None):
-        """Host half: ``map_fn`` (a thread pool's ``map``) or the decode farm decodes; the draws are taken afterwards in index
-        order, so a pooled batch consumes the stream like ``[get_example(i) for i in indices]``."""
-        indices = list(indices)
+    def _decode(self, indices, map_fn, farm):
         if farm is not None:
             frames = farm.decode([self._path(i) for i in indices], map_fn) if indices else []
-            frames = [self._read_u8(i) if isinstance(f, int) else f for i, f in zip(indices, frames)]
+            return [self._read_u8(i) if isinstance(f, int) else f for i, f in zip(indices, frames)]
+        return list(map_fn(self._read_u8, indices))
+
+    def decode_batch(self, indices, map_fn=map, farm=None):
+        """Host half: ``map_fn`` (a thread pool's ``map``) or the decode farm decodes; the draws are taken afterwards in index
+        order, so a pooled batch consumes the stream like ``[get_example(i) for i in indices]``.  With a cache every index is
+        looked up first and only the misses are decoded: a frame resident in HBM is a ``CachedFrame`` placeholder of its shape,
+        one kept on the host the array itself -- the draws see shapes alone, hit or miss -- and the indices travel with the
+        result."""
+        indices = list(indices)
+        if self.cache is None:
+            frames = self._decode(indices, map_fn, farm)
         else:
-            frames = list(map_fn(self._read_u8, indices))
+            frames = [self.cache.lookup(i) for i in indices]
+            missing = [n for n, f in enumerate(frames) if f is None]
+            for n, f in zip(missing, self._decode([indices[n] for n in missing], map_fn, farm)):
+                frames[n] = f
+                self.cache.keep_host(indices[n], f)
         draws = [self._draw(*f.shape[:2]) for f in frames]
-        return frames, draws, numpy.array([self._pairs[i][1] for i in indices], numpy.int32)
+        labels = numpy.array([self._pairs[i][1] for i in indices], numpy.int32)
+        if self.cache is None:
+            return frames, draws, labels
+        return frames, draws, labels, indices, len(indices) - len(missing)
 
     def finish_batch(self, decoded, device, map_fn=map):
         """Device half.  Host cores are the scarce resource: per frame ONE contiguous copy -- rows y0 .. y0 + h at full width --
@@ -100,6 +126,8 @@ class ClassificationImageDataset(_CropDraws):
         frames, one launch; the kernel gets x0 and the pitch."""
         from .resample import _staging
         device = torch.device(device)
+        if len(decoded) > 3:
+            return self._finish_cached(decoded, device, map_fn)
         frames, draws, labels = decoded
         jobs, spans, off = [], [], 0
         for f, ((y0, x0, h, w), flip) in zip(frames, draws):
@@ -125,6 +153,89 @@ class ClassificationImageDataset(_CropDraws):
         ring['events'][slot] = ev
         # (the labels are their own tensor: the upload buffer goes when the launch has read it)
         return crop_resize_device(dev_all[:off], jobs, self.image_size), dev_all[labels_at:total].view(torch.int32).clone()
+
+    def _finish_cached(self, decoded, device, map_fn):
+        """``finish_batch`` with a cache.  Three kinds of frames, ONE launch over several sources: hits are read where they lie
+        in the cache's slabs; misses the cache admits are staged as WHOLE frames and uploaded, one asynchronous copy per
+        touched slab, straight into the space reserved for them (no device-to-device copy), and read there; the other misses
+        -- no room, an index that occurs twice in the batch before it is stored (a batch that runs over a shard's end), every miss in
+        host mode -- go up as before: crop rows only, with the labels, as the last source."""
+        from .resample import _staging
+        frames, draws, labels, indices, hits = decoded
+        cache = self.cache
+        cur = torch.cuda.current_stream(device)
+        missed = [n for n, f in enumerate(frames) if not isinstance(f, CachedFrame)]
+        plan = {}
+        if cache.where == 'device':
+            if cache.device.type != device.type or None not in (cache.device.index, device.index) and cache.device.index != device.index:
+                raise ValueError('the frame cache lives on %s, the batch is finished on %s' % (cache.device, device))
+            cache.wait_for_stores(cur)
+            times = {}
+            for n in missed:
+                times[indices[n]] = times.get(indices[n], 0) + 1
+            once = [n for n in missed if times[indices[n]] == 1]
+            plan = {n: loc for n, loc in zip(once, cache.reserve([(indices[n],) + frames[n].shape[:2] for n in once]))
+                    if loc is not None}
+        # the staging buffer: per touched slab the run of whole frames reserved in it, then the crop rows of the other misses,
+        # then the labels
+        runs = {}                                       # slab -> [first byte in the slab, bytes, offset in the staging buffer]
+        for n, (slab, at) in plan.items():
+            run = runs.setdefault(slab, [at, 0, 0])
+            run[1] = at + frames[n].nbytes - run[0]     # (reserved in batch order: offsets ascend)
+        off = 0
+        for run in runs.values():
+            run[2] = off
+            off += run[1]
+        rows_at = off = (off + 15) & ~15
+        sources, source_of = [], {}
+
+        def source(slab):
+            if slab not in source_of:
+                source_of[slab] = len(sources)
+                sources.append(cache.slabs[slab])
+            return source_of[slab]
+
+        jobs, spans = [], []
+        for n, (f, ((y0, x0, h, w), flip)) in enumerate(zip(frames, draws)):
+            H, W = f.shape[:2]
+            if isinstance(f, CachedFrame):
+                slab, at = cache.location(f.index)[:2]
+                jobs.append((at, 3 * W, H, W, (y0, x0, h, w), flip, source(slab)))
+            elif n in plan:
+                slab, at = plan[n]
+                jobs.append((at, 3 * W, H, W, (y0, x0, h, w), flip, source(slab)))
+                spans.append((runs[slab][2] + at - runs[slab][0], f, 0, H))
+            else:
+                jobs.append([off - rows_at, 3 * W, h, W, (0, x0, h, w), flip, None])
+                spans.append((off, f, y0, h))
+                off += h * W * 3
+        labels_at = (off + 3) & ~3
+        total = labels_at + 4 * len(frames)
+        ring, slot, host = _staging.get(total)
+        host_np = host.numpy()
+
+        def stage(span):
+            o, f, y0, h = span
+            W = f.shape[1]
+            numpy.copyto(host_np[o:o + h * W * 3].reshape(h, W, 3), f[y0:y0 + h])
+
+        list(map_fn(stage, spans))
+        host_np[labels_at:total].view(numpy.int32)[:] = labels
+        for slab, (first, nbytes, at) in runs.items():
+            cache.slabs[slab][first:first + nbytes].copy_(host[at:at + nbytes], non_blocking=True)
+        dev_rest = host[rows_at:total].to(device, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(cur)
+        ring['events'][slot] = ev
+        if plan:
+            cache.publish([indices[n] for n in plan], ev, cur)
+        if off > rows_at:
+            sources.append(dev_rest[:off - rows_at])
+            jobs = [tuple(j[:6]) + (len(sources) - 1,) if j[6] is None else j for j in jobs]
+        batch = FeedBatch((crop_resize_device_multi(sources, jobs, self.image_size),
+                           dev_rest[labels_at - rows_at:total - rows_at].view(torch.int32).clone()))
+        batch.cache_hits, batch.cache_misses = hits, len(frames) - hits
+        return batch
 
 
 class ResidentClassificationSource(_CropDraws):

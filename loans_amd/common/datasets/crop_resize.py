@@ -76,24 +76,49 @@ def crop_resize_host(frame_u8_hwc, box, out_hw, flip=False):
     return np.ascontiguousarray(np.asarray(image, dtype=np.float32).transpose(2, 0, 1) / 255, dtype=np.float32)
 
 
+def bilinear_window(in_size, out_size):
+    """``resample_coeffs(in_size, out_size, 'bilinear')[2]`` -- the width of the coefficient rows: the largest window of one
+    output coordinate -- by that function's own arithmetic, without building the table (1 ms of Python apiece, and a batch of
+    random-resized-crops from a cache has a few hundred distinct sizes: more than ``resample_coeffs`` memoises)"""
+    filterscale = (float(in_size) - 0.0) / out_size
+    if filterscale < 1.0:
+        filterscale = 1.0
+    return int(math.ceil(resample.BILINEAR_SUPPORT * filterscale)) * 2 + 1
+
+
 def check_jobs(nbytes, jobs, out_hw):
     """host-side validation of ``crop_resize_device``'s jobs against a source buffer of ``nbytes`` bytes: ValueError for a box
-    that leaves its frame, a frame that leaves the buffer, a window that exceeds the LDS capacity.  Touches no GPU."""
+    that leaves its frame, a frame that leaves the buffer, a window that exceeds the LDS capacity.  Touches no GPU.
+
+    The per-source form (``crop_resize_device_multi``): ``nbytes`` is the list of the sources' byte counts and a job carries
+    the index of its source as a seventh entry -- an index that names no source is a ValueError, and a frame has to lie inside
+    its OWN source."""
     oh, ow = int(out_hw[0]), int(out_hw[1])
     if oh <= 0 or ow <= 0:
         raise ValueError('output size must be positive, got %r' % (out_hw,))
     if not 0 < len(jobs) <= MAX_JOBS:
         raise ValueError('a launch takes 1 .. %d crops, got %d' % (MAX_JOBS, len(jobs)))
+    multi = not isinstance(nbytes, (int, np.integer))
+    sizes = [int(b) for b in nbytes] if multi else [int(nbytes)]
     cap = lds_row_capacity(ow)
-    for n, (off, pitch, H, W, (y0, x0, h, w), _) in enumerate(jobs):
+    windows = {}
+    for n, job in enumerate(jobs):
+        if len(job) != (7 if multi else 6):
+            raise ValueError('crop %d: a job of %d entries, %d expected' % (n, len(job), 7 if multi else 6))
+        off, pitch, H, W, (y0, x0, h, w), _ = job[:6]
+        s = job[6] if multi else 0
+        if not (isinstance(s, (int, np.integer)) and 0 <= s < len(sizes)):
+            raise ValueError('crop %d: source index %r of %d sources' % (n, s, len(sizes)))
         if H <= 0 or W <= 0 or pitch < 3 * W or pitch >= 1 << 31:
             raise ValueError('crop %d: a %d x %d frame with a row pitch of %d bytes' % (n, H, W, pitch))
-        if off < 0 or off + (H - 1) * pitch + 3 * W > nbytes:
-            raise ValueError('crop %d: the frame (offset %d, %d rows of pitch %d) does not lie inside the %d-byte buffer'
-                             % (n, off, H, pitch, nbytes))
+        if off < 0 or off + (H - 1) * pitch + 3 * W > sizes[s]:
+            raise ValueError('crop %d: the frame (offset %d, %d rows of pitch %d) does not lie inside the %d-byte buffer%s'
+                             % (n, off, H, pitch, sizes[s], ' of source %d' % s if multi else ''))
         if h < 1 or w < 1 or y0 < 0 or x0 < 0 or y0 + h > H or x0 + w > W:
             raise ValueError('crop %d: box (y0 %d, x0 %d, h %d, w %d) does not lie inside its %d x %d frame' % (n, y0, x0, h, w, H, W))
-        vks = resample_coeffs(h, oh, 'bilinear')[2]
+        vks = windows.get(h)
+        if vks is None:
+            vks = windows[h] = bilinear_window(h, oh)
         if vks > cap:
             raise ValueError('crop %d: %d rows to %d need a vertical window of %d rows, the kernel holds %d rows of %d pixels'
                              % (n, h, oh, vks, cap, ow))
@@ -132,4 +157,55 @@ def crop_resize_device(dev_all, jobs, out_hw, out=None):
     ring['events'][slot] = ev
     check(_lib.load().loans_crop_resize_u8_f32(_ptr(dev_all), _ptr(out), _ptr(jobs_d), len(jobs), _ptr(arena.buf),
                                                int(table['vks'].max()), oh, ow, _stream()), 'loans_crop_resize_u8_f32')
+    return out
+
+
+def crop_resize_device_multi(sources, jobs, out_hw, out=None):
+    """``crop_resize_device`` for frames that lie in SEVERAL device buffers (slabs of a frame cache, an upload of this moment):
+    ``sources`` is a list of contiguous uint8 device tensors on one device, a job is ``crop_resize_device``'s tuple plus the
+    index of the source its byte offset refers to.  Still ONE launch, and one pinned staging upload for the job table, the
+    index array and the table of the sources' addresses.  The sources have to stay alive until the launch has run: what the
+    kernel is given are their addresses."""
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    sources, jobs = list(sources), list(jobs)
+    if not sources:
+        raise ValueError('at least one source buffer is needed')
+    for s in sources:
+        if s.dtype != torch.uint8 or not s.is_contiguous():
+            raise ValueError('every source must be a contiguous uint8 buffer')
+    check_jobs([s.numel() for s in sources], jobs, (oh, ow))
+    dev = sources[0].device
+    if not all(s.is_cuda and s.device == dev for s in sources):
+        raise ValueError('the sources must be device buffers of one device')
+    if out is None:
+        out = torch.empty((len(jobs), 3, oh, ow), device=dev, dtype=torch.float32)
+    elif not (out.dtype == torch.float32 and out.device == dev and out.is_contiguous() and tuple(out.shape) == (len(jobs), 3, oh, ow)):
+        raise ValueError('out must be a contiguous float32 [%d][3][%d][%d] tensor on %s' % (len(jobs), oh, ow, dev))
+    akey = (dev, torch.cuda.current_stream(dev).cuda_stream)
+    arena = resample._arenas.get(akey)
+    if arena is None:
+        arena = resample._arenas[akey] = resample._TableArena(dev)
+    at = arena.ensure({(job[4][3], ow, 'bilinear') for job in jobs} | {(job[4][2], oh, 'bilinear') for job in jobs})
+    # [job table][index array][(padding to 8)][address table], staged and uploaded as one
+    n = len(jobs)
+    index_at = CROP_JOB.itemsize * n
+    srcs_at = (index_at + 4 * n + 7) & ~7
+    total = srcs_at + 8 * len(sources)
+    ring, slot, host = resample._staging.get(total, kind='jobs')
+    host_np = host[:total].numpy()
+    table, index = host_np[:index_at].view(CROP_JOB), host_np[index_at:index_at + 4 * n].view(np.int32)
+    max_vks = 0
+    for k, (off, pitch, _, _, (y0, x0, h, w), flip, s) in enumerate(jobs):
+        v = at[(h, oh, 'bilinear')]
+        table[k] = (off, pitch, y0, x0, h, w) + at[(w, ow, 'bilinear')] + v + (int(bool(flip)),)
+        index[k] = s
+        max_vks = max(max_vks, v[2])
+    host_np[srcs_at:total].view(np.int64)[:] = [s.data_ptr() for s in sources]
+    staged = host[:total].to(dev, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(dev))
+    ring['events'][slot] = ev
+    check(_lib.load().loans_crop_resize_srcs_u8_f32(_ptr(staged[srcs_at:]), _ptr(staged[index_at:]), len(sources), _ptr(out),
+                                                    _ptr(staged), n, _ptr(arena.buf), int(max_vks), oh, ow, _stream()),
+          'loans_crop_resize_srcs_u8_f32')
     return out

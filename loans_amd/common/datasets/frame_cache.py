@@ -14,6 +14,9 @@ resize would see:
   (The naive crop / flip branch -- ``use_imgaug=False`` -- hands strided VIEWS of a frame to the resize and always uses this form.)
 
 The bytes a batch is made of are the decoded arrays either way: ``device_batch == stack(get_example)`` holds as before.
+
+``RaggedFrameCache`` (below) is the same idea for the ImageNet pre-training feed, whose frames have thousands of sizes: whole
+frames packed back to back into slabs and cropped in place by the kernel of crop_resize.py.
 """
 import threading
 
@@ -149,3 +152,115 @@ class FrameCache:
                 out = torch.empty((len(frames), 3, int(out_hw[0]), int(out_hw[1])), device=device, dtype=torch.float32)
             out[torch.tensor(order, dtype=torch.int64).to(device, non_blocking=True)] = batch
         return out
+
+
+class RaggedFrameCache:
+    """Decode once for frames of ANY size (the ImageNet pre-training feed, classification_dataset.py: thousands of sizes, so
+    ``FrameCache``'s pools per size do not apply), read in place by the crop kernel (crop_resize_device_multi).
+
+    * ``where='device'``: frames packed back to back, at any byte offset, into uint8 slabs of ``max(64 MiB, budget / 32)``
+      bytes (chunks sized from the budget) on ``device``.  A slab is added only if ``allocated + slab <= budget``,
+      a frame never straddles two slabs, and only the last slab is filled: a frame that does not fit what is left of it -- and
+      for which no further slab is admitted -- stays uncached.  No eviction, nothing is ever copied to grow.  The dataset
+      ``reserve``s the space of a batch's misses, uploads the frames straight into it and ``publish``es them with the event of
+      that upload; a frame is served only once published.  (Space reserved for a batch that then fails is lost, not reused.)
+    * ``where='host'``: the decoded arrays in host memory within the budget; only the decode is skipped.
+
+    The lock guards lookups (decode thread) against stores (finish thread).  The cache keeps the event of the last store of
+    every stream that stored: a batch finished on another stream -- a second iterator over the same dataset -- waits for those
+    events before it reads (``wait_for_stores``).  ``device='cpu'`` gives the bookkeeping host tensors for slabs: tests without
+    a GPU."""
+
+    MIN_SLAB_BYTES = 64 << 20
+
+    def __init__(self, budget_bytes, where='device', device=None, slab_bytes=None):
+        if where not in ('device', 'host'):
+            raise ValueError("where must be 'device' or 'host', got %r" % (where,))
+        self.where, self.budget = where, int(budget_bytes)
+        self.device = torch.device('cuda' if device is None else device) if where == 'device' else None
+        self.slab_bytes = max(self.MIN_SLAB_BYTES, self.budget // 32) if slab_bytes is None else int(slab_bytes)
+        self.host = {}              # index -> uint8 HWC array                         (where == 'host')
+        self.slots = {}             # index -> (slab, byte offset, H, W), published    (where == 'device')
+        self._reserved = {}         # the same for frames whose upload has not been published yet
+        self.slabs, self._used = [], 0          # uint8 tensors [slab_bytes]; bytes handed out of the last one
+        self.bytes = self.allocated = 0         # bytes of the frames kept; bytes of all slabs: what the budget bounds
+        self.hits = self.misses = 0
+        self.lock = threading.Lock()
+        self._store_events = {}     # stream -> the event behind its last store
+
+    def __len__(self):
+        return len(self.host) + len(self.slots)
+
+    # ---- decode thread ----------------------------------------------------------------------------------------------------
+    def lookup(self, i):
+        """the cached form of frame i: a uint8 array (host), a CachedFrame (device) or None; counts a hit or a miss"""
+        with self.lock:
+            if self.where == 'host':
+                f = self.host.get(i)
+            else:
+                s = self.slots.get(i)
+                f = CachedFrame(i, (s[2], s[3], 3)) if s is not None else None
+            if f is None:
+                self.misses += 1
+            else:
+                self.hits += 1
+            return f
+
+    def keep_host(self, i, image):
+        """host mode: keep a freshly decoded frame (within the budget); a second store of an index is a no-op"""
+        if self.where != 'host' or not isinstance(image, np.ndarray):
+            return False
+        with self.lock:
+            if i in self.host or self.bytes + image.nbytes > self.budget:
+                return False
+            self.host[i] = image
+            self.bytes += image.nbytes
+            return True
+
+    # ---- finish thread (device mode) ------------------------------------------------------------------------------------------
+    def location(self, i):
+        """(slab, byte offset, H, W) of a published frame"""
+        with self.lock:
+            return self.slots[i]
+
+    def reserve(self, frames):
+        """``frames`` = [(index, H, W)] -> [(slab, byte offset) or None] in that order: space for each frame the cache admits,
+        handed out in one piece of work under the lock -- so what one call reserves in a slab is one contiguous run.  None:
+        the index is stored or reserved already, or the frame fits neither the last slab nor a further one."""
+        if self.where != 'device':
+            return [None] * len(frames)
+        out = []
+        with self.lock:
+            for i, H, W in frames:
+                n = int(H) * int(W) * 3
+                if i in self.slots or i in self._reserved or n <= 0 or n > self.slab_bytes:
+                    out.append(None)
+                    continue
+                if not self.slabs or self._used + n > self.slab_bytes:
+                    if self.allocated + self.slab_bytes > self.budget:
+                        out.append(None)
+                        continue
+                    self.slabs.append(torch.empty(self.slab_bytes, device=self.device, dtype=torch.uint8))
+                    self.allocated += self.slab_bytes
+                    self._used = 0
+                loc = (len(self.slabs) - 1, self._used)
+                self._reserved[i] = loc + (int(H), int(W))
+                self._used += n
+                out.append(loc)
+        return out
+
+    def publish(self, indices, event=None, stream=None):
+        """the reserved frames ``indices`` have been uploaded (``event``: recorded behind the copies on ``stream``)"""
+        with self.lock:
+            for i in indices:
+                s = self.slots[i] = self._reserved.pop(i)
+                self.bytes += s[2] * s[3] * 3
+            if event is not None:
+                self._store_events[stream] = event
+
+    def wait_for_stores(self, stream):
+        """make ``stream`` wait for the last store of every other stream"""
+        with self.lock:
+            events = [event for other, event in self._store_events.items() if other != stream]
+        for event in events:
+            stream.wait_event(event)

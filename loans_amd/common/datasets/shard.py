@@ -8,7 +8,8 @@ seen twice per epoch.  ``pad=False`` (validation): no example is repeated; shard
 so what is computed over them must be summed, not averaged per shard.
 
 Whatever the base offers of ``get_examples`` / ``decode_batch`` / ``finish_batch`` / ``device_batch`` / ``reseed`` the view offers
-too, with mapped indices -- and nothing the base does not have --, so ``MultithreadIterator(device=...)`` treats a shard exactly
+too, with mapped indices -- and nothing the base does not have --, and the base's frame ``cache``, which is keyed by base
+indices like everything a mapped call hands the base, so ``MultithreadIterator(device=...)`` treats a shard exactly
 like its base."""
 
 
@@ -16,6 +17,7 @@ class ShardedDataset:
 
     _INDEXED = ('get_examples', 'decode_batch', 'device_batch')       # first argument: a list of indices
     _PLAIN = ('finish_batch', 'reseed')
+    _ATTRIBUTES = ('cache',)
 
     def __init__(self, dataset, rank, world, pad):
         n = len(dataset)
@@ -43,9 +45,9 @@ class ShardedDataset:
 
     def __getattr__(self, name):
         # only reached for names the view itself does not define
-        if name in ShardedDataset._INDEXED or name in ShardedDataset._PLAIN:
+        if name in ShardedDataset._INDEXED or name in ShardedDataset._PLAIN or name in ShardedDataset._ATTRIBUTES:
             method = getattr(self.__dict__['dataset'], name)        # AttributeError where the base has none: hasattr() is False
-            if name in ShardedDataset._PLAIN:
+            if name not in ShardedDataset._INDEXED:
                 return method
             indices = self.__dict__['_indices']
             return lambda idx, *args, **kwargs: method([indices[int(i)] for i in idx], *args, **kwargs)

@@ -47,12 +47,23 @@ __device__ __forceinline__ uint32_t load_rgb(const uint8_t* a, int col) {
 constexpr int HROWS = 4;        // crop rows per thread in the horizontal pass: one coefficient load serves four pixels
 
 // VEC: outW % 4 == 0 and dst 16-byte aligned -- the vertical pass takes four pixels (12 LDS bytes, three dwords) per thread
-// and stores a float4 per plane.  LDS: bytes of the row image.
-template <bool VEC, int LDS>
+// and stores a float4 per plane.  LDS: bytes of the row image.  SRCS: the jobs' frames lie in several buffers -- job n's
+// src_off is relative to srcs[src_index[n]] (`src` is unused); without it the three trailing arguments are unused and the
+// instance is the single-source kernel.
+template <bool VEC, int LDS, bool SRCS>
 __global__ __launch_bounds__(THREADS) void crop_resize_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst,
                                                               const loans_crop_job* __restrict__ jobs,
-                                                              const int32_t* __restrict__ tables, int band, int outH, int outW) {
+                                                              const int32_t* __restrict__ tables, int band, int outH, int outW,
+                                                              const uint8_t* const* __restrict__ srcs,
+                                                              const int32_t* __restrict__ src_index, int nsrcs) {
     __shared__ __attribute__((aligned(16))) uint8_t rows[LDS];      // [crop rows of this fill][outW][3]
+    if (SRCS) {
+        // one index per job, read through blockIdx alone: the same for every thread of the block, so a block whose index
+        // names no source leaves as a whole, before any barrier and before it has read a job or a pixel
+        const int s = src_index[blockIdx.y];
+        if (s < 0 || s >= nsrcs) return;
+        src = srcs[s];
+    }
     const loans_crop_job j = jobs[blockIdx.y];
     const int32_t* hb = tables + j.hb_off;
     const int32_t* hk = tables + j.hk_off;
@@ -192,9 +203,30 @@ extern "C" int loans_crop_resize_u8_f32(const uint8_t* src, float* dst, const lo
     const dim3 grid((outH + band - 1) / band, njobs);
     const bool vec = outW % 4 == 0 && ((uintptr_t)dst & 15) == 0;
     const bool small = 2 * max_vks <= SMALL_LDS_BYTES / (outW * 3);     // (at its limit a fill is one output row: every crop row twice)
-    auto kern = small ? (vec ? crop_resize_kernel<true, SMALL_LDS_BYTES> : crop_resize_kernel<false, SMALL_LDS_BYTES>)
-                      : (vec ? crop_resize_kernel<true, LOANS_CROP_LDS_BYTES> : crop_resize_kernel<false, LOANS_CROP_LDS_BYTES>);
-    hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, as_stream(stream), src, dst, jobs, tables, band, outH, outW);
+    auto kern = small ? (vec ? crop_resize_kernel<true, SMALL_LDS_BYTES, false> : crop_resize_kernel<false, SMALL_LDS_BYTES, false>)
+                      : (vec ? crop_resize_kernel<true, LOANS_CROP_LDS_BYTES, false> : crop_resize_kernel<false, LOANS_CROP_LDS_BYTES, false>);
+    hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, as_stream(stream), src, dst, jobs, tables, band, outH, outW,
+                       (const uint8_t* const*)nullptr, (const int32_t*)nullptr, 0);
+    LOANS_LAUNCH_CHECK();
+    return LOANS_OK;
+}
+
+extern "C" int loans_crop_resize_srcs_u8_f32(const uint8_t* const* srcs, const int32_t* src_index, int32_t nsrcs, float* dst,
+                                             const loans_crop_job* jobs, int32_t njobs, const int32_t* tables, int32_t max_vks,
+                                             int32_t outH, int32_t outW, void* stream) {
+    if (!srcs || !src_index || nsrcs <= 0) return LOANS_EINVAL;
+    // from here on the checks and the choice of the form are those of the single-source entry
+    if (!dst || !jobs || !tables || njobs <= 0 || njobs > 65535 || max_vks <= 0 || outH <= 0 || outW <= 0) return LOANS_EINVAL;
+    if ((int64_t)outW * 3 > LOANS_CROP_LDS_BYTES || max_vks > LOANS_CROP_LDS_BYTES / (outW * 3)) return LOANS_EINVAL;
+    if ((int64_t)outH * outW >= ((int64_t)1 << 30)) return LOANS_ERANGE;
+    const int band = band_rows(outH, outW);
+    const dim3 grid((outH + band - 1) / band, njobs);
+    const bool vec = outW % 4 == 0 && ((uintptr_t)dst & 15) == 0;
+    const bool small = 2 * max_vks <= SMALL_LDS_BYTES / (outW * 3);
+    auto kern = small ? (vec ? crop_resize_kernel<true, SMALL_LDS_BYTES, true> : crop_resize_kernel<false, SMALL_LDS_BYTES, true>)
+                      : (vec ? crop_resize_kernel<true, LOANS_CROP_LDS_BYTES, true> : crop_resize_kernel<false, LOANS_CROP_LDS_BYTES, true>);
+    hipLaunchKernelGGL(kern, grid, dim3(THREADS), 0, as_stream(stream), (const uint8_t*)nullptr, dst, jobs, tables, band, outH,
+                       outW, srcs, src_index, nsrcs);
     LOANS_LAUNCH_CHECK();
     return LOANS_OK;
 }

@@ -39,7 +39,17 @@ the scheduled rate at the start to the scheduled rate at epoch E, the gradual wa
 running statistics went to every rank; its entries also carry ``validation/rows`` and ``validation/valid`` under ``--gpus N``.
 Rank 0 alone prints, logs and writes snapshots.
 
-Not built (follow-ups): ``--use-graph`` and cropping out of the decode-once frame cache.
+``--frame-cache-gb G`` (with ``--augment rrc`` on files; per rank) decodes every file once: the uint8 frames are kept -- whole,
+at any size, packed into slabs in HBM (``--frame-cache-where device``, the default) or as arrays in host memory (``host``) --
+and from the second epoch on a batch is cropped straight out of them, no decode and, in HBM, no upload
+(loans_amd/common/datasets/frame_cache.py, ``RaggedFrameCache``; no eviction: what does not fit is decoded every epoch, as
+before).  The training and the validation set have caches of their own, G split between them in proportion to their numbers
+of examples.  The first epoch uploads whole frames where it would have uploaded the crops' rows.  Logged entries then carry
+``feed/cache_frames`` and ``feed/cache_bytes`` (what the training cache holds) and ``feed/cache_hits`` / ``feed/cache_misses``
+(training examples served from it / decoded since the previous entry), and the same four under ``feed/val_cache_`` for the
+validation set.
+
+Not built (follow-ups): ``--use-graph``.
 """
 import os
 
@@ -101,8 +111,13 @@ class Arguments(argparse.Namespace):
     warmup_start_factor = 0.1
     validation_sums = False
 
+    # decode-once frame cache of --augment rrc on files
+    frame_cache_gb = 0.0
+    frame_cache_where = 'device'
+
     _PIPELINE = ('augment', 'rrc_scale', 'rrc_ratio', 'val_crop_pct', 'augment_seed')
     _PARALLEL = ('gpus', 'warmup_epochs', 'warmup_start_factor', 'validation_sums')
+    _CACHE = ('frame_cache_gb', 'frame_cache_where')
 
 
 def parse_args(argv=None):
@@ -149,7 +164,33 @@ def parse_args(argv=None):
     parser.add_argument("--warmup-epochs", type=float, default=argparse.SUPPRESS, help="ramp the rate linearly up to the scheduled one over this many epochs (default 0: off)")
     parser.add_argument("--warmup-start-factor", type=float, default=argparse.SUPPRESS, help="fraction of the scheduled rate the warm-up starts from (default 0.1)")
     parser.add_argument("--validation-sums", action='store_true', default=argparse.SUPPRESS, help="validate by summing loss and hits over all examples on the device (always on with --gpus N)")
-    return parser.parse_args(argv, namespace=Arguments())
+    # decode-once frame cache
+    parser.add_argument("--frame-cache-gb", type=float, default=argparse.SUPPRESS, help="with --augment rrc on files: keep up to this many GB of decoded frames per rank and crop later epochs out of them (default 0: off)")
+    parser.add_argument("--frame-cache-where", default=argparse.SUPPRESS, choices=['device', 'host'], help="keep the frames in HBM (default) or in host memory")
+    args = parser.parse_args(argv, namespace=Arguments())
+    try:
+        check_cache_arguments(args)
+    except ValueError as e:
+        parser.error(str(e))
+    return args
+
+
+def check_cache_arguments(args):
+    """ValueError where ``--frame-cache-gb`` is asked of a run that has nothing to cache"""
+    gb = args.frame_cache_gb
+    if gb < 0:
+        raise ValueError('--frame-cache-gb must not be negative, got %r' % gb)
+    if gb > 0 and args.augment != 'rrc':
+        raise ValueError('--frame-cache-gb caches the frames the GPU crops: it needs --augment rrc')
+    if gb > 0 and args.train_file == SYNTHETIC:
+        raise ValueError('--frame-cache-gb caches decoded files: the synthetic classes already lie in HBM, give a train_file')
+
+
+def cache_budgets(total_bytes, n_train, n_validation):
+    """(training, validation) bytes of the frame caches: the budget split in proportion to the sets' numbers of examples --
+    frames of one collection are of one size on average, so each set gets the same fraction of itself cached"""
+    train = int(total_bytes) * n_train // max(n_train + n_validation, 1)
+    return train, int(total_bytes) - train
 
 
 def scheduled_lr(base, epoch, drop_epochs, factor):
@@ -220,7 +261,16 @@ def build_crop_datasets(args, device, rank=0):
         return ClassificationImageDataset(path, os.path.dirname(path), train=train, **crops)
 
     train = dataset(args.train_file, args.dataset_size, 0, True)
-    return train, (dataset(args.val_file, args.validation_size, 1, False) if args.validation else None)
+    validation = dataset(args.val_file, args.validation_size, 1, False) if args.validation else None
+    if getattr(args, 'frame_cache_gb', 0) > 0:
+        # per rank: every rank keeps its own share of the sets (ShardedDataset hands it every N-th example)
+        from loans_amd.common.datasets.frame_cache import RaggedFrameCache
+        cached_validation = validation is not None and args.val_file != SYNTHETIC
+        budgets = cache_budgets(args.frame_cache_gb * 1e9, len(train), len(validation) if cached_validation else 0)
+        train.cache = RaggedFrameCache(budgets[0], args.frame_cache_where, device)
+        if cached_validation:
+            validation.cache = RaggedFrameCache(budgets[1], args.frame_cache_where, device)
+    return train, validation
 
 
 def converter(batch, device=None):
@@ -237,9 +287,10 @@ def run(args, log=print):
     elif args.gpu < 0:
         args.gpu = torch.cuda.current_device()
     torch.cuda.set_device(args.gpu)
-    for name in Arguments._PIPELINE + Arguments._PARALLEL:      # the values this run uses, logged with the other arguments
+    for name in Arguments._PIPELINE + Arguments._PARALLEL + Arguments._CACHE:      # the values this run uses, logged with the other arguments
         setattr(args, name, getattr(args, name, getattr(Arguments, name)))
     args.gpus = comm.size
+    check_cache_arguments(args)
     chief = comm.rank == 0                       # prints, logs and writes snapshots
 
     # --augment rrc: the iterators hand out (frames, labels) already resident on the device
@@ -249,6 +300,24 @@ def run(args, log=print):
         feed, batch_converter = {'device': args.gpu}, training.identity_converter
     else:
         train_dataset, validation_dataset = build_datasets(args)
+    # the frame caches' work is counted where a batch is consumed (the lookups run batches ahead): [hits, misses] since the last
+    # log entry, of the training and of the validation set
+    caches = {'feed/cache_': [getattr(train_dataset, 'cache', None), 0, 0],
+              'feed/val_cache_': [getattr(validation_dataset, 'cache', None), 0, 0]}
+    caches = {k: v for k, v in caches.items() if v[0] is not None}
+
+    def counting(prefix):
+        if prefix not in caches:
+            return batch_converter
+        tally = caches[prefix]
+
+        def convert(batch, device=None):
+            tally[1] += getattr(batch, 'cache_hits', 0)
+            tally[2] += getattr(batch, 'cache_misses', 0)
+            return batch_converter(batch, device)
+        return convert
+
+    train_converter, validation_converter = counting('feed/cache_'), counting('feed/val_cache_')
     # every rank built the same sets and takes every comm.size-th example: the training share padded by wrapping (all ranks make
     # the same iterations and epochs), the validation share not (every example is counted once; shares may differ by one)
     train_dataset = ShardedDataset(train_dataset, comm.rank, comm.size, pad=True)
@@ -271,7 +340,7 @@ def run(args, log=print):
     parallel.create_multi_node_optimizer(optimizer, comm)
     topk = 'accuracy_top%d' % model.topk if model.topk is not None else None
     train_keys = ('loss', 'accuracy') + ((topk,) if topk else ())
-    updater = training.StandardUpdater(train_iter, optimizer, converter=batch_converter, device=args.gpu, comm=comm)
+    updater = training.StandardUpdater(train_iter, optimizer, converter=train_converter, device=args.gpu, comm=comm)
 
     evaluator = validate = None
     summed = comm.size > 1 or args.validation_sums
@@ -287,7 +356,7 @@ def run(args, log=print):
                 result['validation/' + topk] = float(model.accuracy_topk.data)
             return result
 
-        evaluator = training.Evaluator(validation_iter, model, converter=batch_converter, device=args.gpu, eval_func=eval_func)
+        evaluator = training.Evaluator(validation_iter, model, converter=validation_converter, device=args.gpu, eval_func=eval_func)
         metrics = loans_amd.ClassificationMetrics(topk=model.topk, device=torch.device('cuda', args.gpu))
 
         def summed_validation():
@@ -298,7 +367,7 @@ def run(args, log=print):
             metrics.reset()
             validation_iter.reset()
             for batch in validation_iter:
-                x, t = batch_converter(batch, args.gpu)
+                x, t = validation_converter(batch, args.gpu)
                 model.evaluate(x, t, metrics)
             total = metrics.result(comm)
             result = {'validation/loss': total['loss'], 'validation/accuracy': total['accuracy']}
@@ -352,6 +421,10 @@ def run(args, log=print):
                 keep = {k: obs[k] for k in train_keys}
                 entry.update({k: v for k, v in validate().items() if k.startswith('validation/')})
                 loans_amd.report(keep)
+            for prefix, tally in caches.items():
+                entry.update({prefix + 'frames': len(tally[0]), prefix + 'bytes': tally[0].bytes,
+                              prefix + 'hits': tally[1], prefix + 'misses': tally[2]})
+                tally[1] = tally[2] = 0
             entry['elapsed_time'] = time.time() - t0
             top = '  top-%d %%.4f' % model.topk if topk else ''
             val = ''
