@@ -35,6 +35,13 @@ class _CropDraws:
     def reseed(self, seed):
         self._aug_rng = random.Random(seed)
 
+    def draw_state(self):
+        """where the draw stream stands (``random.Random.getstate()``): what a checkpoint keeps of this dataset"""
+        return self._aug_rng.getstate()
+
+    def set_draw_state(self, state):
+        self._aug_rng.setstate(state)
+
     def _draw(self, H, W):
         """(box, flip) of the next example, an H x W frame"""
         if not self.train:

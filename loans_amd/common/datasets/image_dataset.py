@@ -105,6 +105,14 @@ class ImageDataset:
     def reseed(self, seed):
         self._aug_rng = random.Random(seed)
 
+    def draw_state(self):
+        """where the stream of both augmentation branches stands (``random.Random.getstate()``): what a checkpoint keeps of
+        this dataset"""
+        return self._aug_rng.getstate()
+
+    def set_draw_state(self, state):
+        self._aug_rng.setstate(state)
+
     def enable_frame_cache(self, gigabytes, where='device'):
         """keep decoded frames for the next epochs (frame_cache.py).  The naive crop / flip branch hands strided views of a frame
         to the resize: it always caches on the host."""

@@ -7,7 +7,7 @@ entry ``j`` is base index ``(rank + j * world) % n`` --, so for a given batch si
 seen twice per epoch.  ``pad=False`` (validation): no example is repeated; shards may differ in length by one and may be empty,
 so what is computed over them must be summed, not averaged per shard.
 
-Whatever the base offers of ``get_examples`` / ``decode_batch`` / ``finish_batch`` / ``device_batch`` / ``reseed`` the view offers
+Whatever the base offers of ``get_examples`` / ``decode_batch`` / ``finish_batch`` / ``device_batch`` / ``reseed`` / ``draw_state`` / ``set_draw_state`` the view offers
 too, with mapped indices -- and nothing the base does not have --, and the base's frame ``cache``, which is keyed by base
 indices like everything a mapped call hands the base, so ``MultithreadIterator(device=...)`` treats a shard exactly
 like its base."""
@@ -16,7 +16,7 @@ like its base."""
 class ShardedDataset:
 
     _INDEXED = ('get_examples', 'decode_batch', 'device_batch')       # first argument: a list of indices
-    _PLAIN = ('finish_batch', 'reseed')
+    _PLAIN = ('finish_batch', 'reseed', 'draw_state', 'set_draw_state')
     _ATTRIBUTES = ('cache',)
 
     def __init__(self, dataset, rank, world, pad):

@@ -15,6 +15,7 @@ update of this optimiser has seen, with the gradients beyond the current graph z
 import math
 from types import SimpleNamespace
 
+import numpy as np
 import torch
 
 from .. import ops
@@ -188,6 +189,66 @@ class GradientMethod:
             self.t += 1
             self._lr_dev.fill_(self.lr)
 
+    # ---- checkpoints (runtime/checkpoint.py) --------------------------------------------------------------------------
+    def _state_names(self):
+        """names of the state buffers a step reads, in ``_new_state`` order"""
+        raise NotImplementedError
+
+    def state_dict(self):
+        """Everything a later ``update()`` depends on, independent of the arena's layout: ``class``, ``t``, ``hyperparam`` (a
+        dict), ``stepped_cold`` (None before the first step, else the cold links -- res6 / res7, fc6 -- the stepped prefix has
+        reached) and ``state``: every state buffer cut per parameter, in the parameter's Chainer layout, under
+        ``<param path>/<buffer name>`` with the paths ``state_dict_chainer()`` uses.  Full length: parameters behind the active
+        prefix are included."""
+        arena = self._ensure_state()
+        named = {id(p): k[1:] for k, p in self.target.namedparams()}
+        state = {}
+        for name, buf in zip(self._state_names(), self._state):
+            host = buf.detach().cpu().numpy()
+            for p, o in zip(arena.params, arena.offsets):
+                state['%s/%s' % (named[id(p)], name)] = np.ascontiguousarray(p._to_logical(host[o:o + p.size].reshape(p.physical_shape)))
+        stepped = getattr(self, '_stepped_numel', 0)
+        return {'class': type(self).__name__, 't': int(self.t), 'hyperparam': dict(vars(self.hyperparam)),
+                'stepped_cold': None if stepped == 0 else [n for n, o in arena.cold_offsets.items() if o < stepped],
+                'state': state}
+
+    def load_state_dict(self, sd):
+        """Restore ``state_dict()``'s record into this optimiser (set up on a model of the same architecture).  ValueError
+        naming the first offending field or key where the class, ``amsgrad``, the parameter paths or a shape differ; nothing is
+        changed then.  The buffers are written in place, so a captured step keeps reading them, and the device copy of the rate
+        a captured step reads is republished for the restored ``t``."""
+        if sd['class'] != type(self).__name__:
+            raise ValueError('class: the checkpoint holds %s, this optimiser is %s' % (sd['class'], type(self).__name__))
+        hp = dict(sd['hyperparam'])
+        if bool(hp.get('amsgrad', False)) != bool(getattr(self.hyperparam, 'amsgrad', False)):
+            raise ValueError('amsgrad: the checkpoint has %r, this optimiser %r' % (hp.get('amsgrad'), self.hyperparam.amsgrad))
+        arena = self._ensure_state()
+        named = {id(p): k[1:] for k, p in self.target.namedparams()}
+        names = self._state_names()
+        want = {'%s/%s' % (named[id(p)], n): p for p in arena.params for n in names}
+        state = sd['state']
+        odd = sorted(set(want) ^ set(state))
+        if odd:
+            raise ValueError('%s: %s' % (odd[0], 'not in the checkpoint' if odd[0] in want else 'no such parameter state in this model'))
+        for key, p in want.items():
+            if tuple(np.shape(state[key])) != p.logical_shape:
+                raise ValueError('%s: shape %s in the checkpoint, %s in this model' % (key, tuple(np.shape(state[key])), p.logical_shape))
+        for name, buf in zip(names, self._state):
+            host = np.zeros(arena.numel, np.float32)
+            for p, o in zip(arena.params, arena.offsets):
+                host[o:o + p.size] = p._from_logical(np.asarray(state['%s/%s' % (named[id(p)], name)], dtype=np.float32)).ravel()
+            buf.copy_(torch.from_numpy(host))
+        for k, v in hp.items():
+            setattr(self.hyperparam, k, v)
+        self.t = int(sd['t'])
+        stepped = sd['stepped_cold']
+        if stepped is None:
+            self._stepped_numel = 0
+        else:       # the cold links lie behind the hot parameters in `cold_links` order: the prefix ends at the first one not stepped
+            self._stepped_numel = min([o for n, o in arena.cold_offsets.items() if n not in stepped] + [arena.numel])
+        if getattr(self, '_lr_dev', None) is not None and self.t > 0:
+            self._lr_dev.fill_(self.lr)
+
 
 class Adam(GradientMethod):
 
@@ -216,6 +277,9 @@ class Adam(GradientMethod):
     def _new_state(self, zeros):
         return zeros(), zeros(), zeros()        # m, v, vhat
 
+    def _state_names(self):
+        return ('m', 'v', 'vhat') if self.hyperparam.amsgrad else ('m', 'v')
+
     def _step(self, arena, n, state, lr, grad_scale):
         hp = self.hyperparam
         m, v, vhat = state
@@ -243,6 +307,9 @@ class MomentumSGD(GradientMethod):
 
     def _new_state(self, zeros):
         return (zeros(),)
+
+    def _state_names(self):
+        return ('v',)
 
     def _step(self, arena, n, state, lr, grad_scale):
         hp = self.hyperparam

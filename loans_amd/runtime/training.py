@@ -80,6 +80,40 @@ class SerialIterator:
     def epoch_detail(self):
         return self.epoch + self._pos / max(len(self.dataset), 1)
 
+    # ---- checkpoints (runtime/checkpoint.py) --------------------------------------------------------------------------
+    def _snapshot(self, epoch, is_new_epoch):
+        """where the iteration stands now: the shuffle stream, the current order and the position in it, the epoch values of
+        the batch handed out last, and the dataset's draw stream where it has one (``draw_state``)"""
+        draw = getattr(self.dataset, 'draw_state', None)
+        return {'rng': self._rng.get_state(), 'order': self._order, 'pos': int(self._pos), 'epoch': int(epoch),
+                'is_new_epoch': bool(is_new_epoch), 'draw': draw() if draw is not None else None}
+
+    def state_dict(self):
+        """The state after the last batch this iterator handed out (the initial one before the first)."""
+        return self._snapshot(self.epoch, self.is_new_epoch)
+
+    def load_state_dict(self, state):
+        """Continue where ``state_dict()`` was taken: the next batches, and the ``epoch`` / ``is_new_epoch`` / ``epoch_detail``
+        they are handed out with, are those of an iterator that was never interrupted."""
+        order = np.asarray(state['order']).astype(np.int64).reshape(-1)
+        if len(order) != len(self.dataset):
+            raise ValueError('order: %d entries in the checkpoint, the dataset has %d examples' % (len(order), len(self.dataset)))
+        draw = getattr(self.dataset, 'set_draw_state', None)
+        if (state.get('draw') is None) != (draw is None):
+            raise ValueError('draw: the checkpoint %s a draw stream, the dataset %s' % (
+                'has no' if state.get('draw') is None else 'has', 'has one' if draw is not None else 'has none'))
+        rng = state['rng']
+        self._rng.set_state((rng[0], np.asarray(rng[1], dtype=np.uint32)) + tuple(rng[2:]))
+        self._order, self._pos = order, int(state['pos'])
+        self.epoch, self.is_new_epoch = int(state['epoch']), bool(state['is_new_epoch'])
+        if draw is not None:
+            draw(_as_draw_state(state['draw']))
+
+
+def _as_draw_state(state):
+    """``random.Random.setstate`` wants tuples; a state that went through a file comes back as lists"""
+    return tuple(_as_draw_state(s) for s in state) if isinstance(state, (list, tuple)) else state
+
 
 class MultithreadIterator(SerialIterator):
     """``chainer.iterators.MultithreadIterator(dataset, batch_size, repeat, shuffle, n_threads)`` in the role the reference
@@ -97,7 +131,11 @@ class MultithreadIterator(SerialIterator):
     Random draws of the datasets (augmentation) are taken on the producer thread in index order, each ``ImageDataset`` from a
     stream of its own (``augment_seed`` / ``reseed``; both augmentation branches), so a run is reproducible for a given seed
     whatever the pool size and however the producer threads of several iterators interleave.  Datasets without
-    ``get_examples`` (``LabeledImageDataset``: no random draws in ``get_example``) go through ``pool.map(ds.__getitem__)``."""
+    ``get_examples`` (``LabeledImageDataset``: no random draws in ``get_example``) go through ``pool.map(ds.__getitem__)``.
+
+    ``state_dict()`` is the state as of the last batch handed OUT: the producer is ``n_prefetch`` batches and more ahead (it may
+    have reshuffled for the next epoch and has taken the draws of batches nobody consumed yet), so it sends the state behind
+    each batch along with the batch, and ``__next__`` keeps the one it returns."""
 
     def __init__(self, dataset, batch_size, repeat=True, shuffle=True, n_threads=4, seed=0, device=None, n_prefetch=2,
                  device_stage='producer', n_processes=0):
@@ -113,6 +151,7 @@ class MultithreadIterator(SerialIterator):
         self._pool = self._pool2 = self._thread = self._thread2 = self._queue = self._mid = self._stream = None
         self._generation = 0
         self._host_state = (self.epoch, self.is_new_epoch, self._pos)
+        self._consumed = None               # state_dict()'s record of the batch handed out last (None: none since start / reset)
 
     # ---- producer side ----------------------------------------------------------------------------------------------
     def _indices(self):
@@ -177,7 +216,10 @@ class MultithreadIterator(SerialIterator):
                     self._put(generation, q_mid, (generation, StopIteration, None))
                     return
                 idx, state = nxt
-                if not self._put(generation, q_mid, (generation, self._decode(idx), state)):
+                item = self._decode(idx)
+                # the state AFTER this batch was produced -- its draws are taken in _decode, on this thread -- travels with the
+                # batch: this thread runs n_prefetch batches ahead of the consumer and may have reshuffled for the next epoch
+                if not self._put(generation, q_mid, (generation, item, state + (self._snapshot(state[0], state[1]),))):
                     return
         except BaseException as e:          # handed to the consumer: a failing decode must fail the training loop
             self._put(generation, q_mid, (generation, e, None))
@@ -213,6 +255,8 @@ class MultithreadIterator(SerialIterator):
         if self._pool2 is None:
             self._pool2 = ThreadPoolExecutor(max_workers=min(self.n_threads, 8), thread_name_prefix='loans-stage')
         self._p_epoch = self.epoch
+        if self._consumed is None:
+            self._consumed = self._snapshot(self.epoch, self.is_new_epoch)     # before any batch: the initial state
         self._queue, self._mid = queue.Queue(maxsize=self.n_prefetch), queue.Queue(maxsize=1)
         args = (self._generation, self._queue, self._mid)
         self._thread = threading.Thread(target=self._produce, args=args, daemon=True, name='loans-feed-decode')
@@ -235,6 +279,7 @@ class MultithreadIterator(SerialIterator):
     def reset(self):
         self._stop()
         super().reset()
+        self._consumed = None
 
     def finalize(self):
         self._stop()
@@ -258,6 +303,7 @@ class MultithreadIterator(SerialIterator):
             self._stop()
             raise item
         self.epoch, self.is_new_epoch, self._host_pos = state[0], state[1], state[2]
+        self._consumed = state[3]
         kind = item[0]
         if kind == 'host':
             return item[1]
@@ -275,6 +321,20 @@ class MultithreadIterator(SerialIterator):
     @property
     def epoch_detail(self):
         return self.epoch + getattr(self, '_host_pos', 0) / max(len(self.dataset), 1)
+
+    def state_dict(self):
+        """The state as of the last batch handed to the consumer -- not the producer thread's, which is ahead of it."""
+        if self._consumed is not None:
+            return self._consumed
+        return self._snapshot(self.epoch, self.is_new_epoch)
+
+    def load_state_dict(self, state):
+        """Only before the threads start, or after ``reset()`` / ``finalize()``: the producer owns the state while it runs."""
+        if self._thread is not None:
+            raise RuntimeError('load_state_dict() while the producer threads run: reset() or finalize() first')
+        super().load_state_dict(state)
+        self._host_pos = self._pos
+        self._consumed = None
 
 
 class DeviceBatchIterator:

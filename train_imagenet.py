@@ -49,6 +49,24 @@ of examples.  The first epoch uploads whole frames where it would have uploaded 
 (training examples served from it / decoded since the previous entry), and the same four under ``feed/val_cache_`` for the
 validation set.
 
+``--checkpoint-interval N`` writes a full-state checkpoint, ``checkpoint_<iteration>.npz`` in the log directory, after every
+N-th iteration and after the last one (default 0: none; ``--checkpoint-keep K``, default 2, keeps the newest K): the model with
+its BN statistics, the optimiser's buffers and step count, the training iterator as of the batch the step consumed (shuffle
+stream, order, position, the crop / mirror draw stream), NumPy's global stream and the run's arguments
+(loans_amd/runtime/checkpoint.py; under ``--gpus N`` one small record per rank beside rank 0's file, which is written last).
+``--resume PATH`` -- a checkpoint file, or a log directory, whose newest complete checkpoint is taken -- continues that run in
+its log directory: the ``log`` file is read back and appended to, ``elapsed_time`` and the snapshot names count on.  Fixed on
+resume (one error lists every one that differs): the architecture, ``--dtype``, ``--optimizer``, ``-b``, ``--gpus``,
+``--image-size``, the dataset files or the synthetic sizes, classes and ``--data-seed``, ``--no-shuffle``, ``--augment`` /
+``--rrc-*`` / ``--val-crop-pct`` / ``--augment-seed``, ``--seed``.  Taken from the new command line (each one that differs is
+printed once): ``--num-epoch``, ``--iterations``, the log, snapshot and checkpoint intervals, ``--loader-threads``, the frame
+cache options, ``--lr``, ``--weight-decay``, ``--momentum``, ``--lr-drop-*``, ``--warmup-*``, ``--label-smoothing``, ``--topk``.  The
+frame caches start empty after a resume and refill during the first epoch.
+
+    python train_imagenet.py train.tsv val.tsv -b 256 --optimizer sgd --lr 0.1 --lr-drop-epochs 30 60 90 --checkpoint-interval 500
+    python train_imagenet.py train.tsv val.tsv -b 256 --optimizer sgd --lr 0.1 --lr-drop-epochs 30 60 90 --checkpoint-interval 500 \
+        --resume imagenet_logs/<time>_test
+
 Not built (follow-ups): ``--use-graph``.
 """
 import os
@@ -75,9 +93,13 @@ import loans_amd            # noqa: E402
 from loans_amd import parallel                                      # noqa: E402
 from loans_amd.common.datasets.shard import ShardedDataset          # noqa: E402
 from loans_amd.datasets import synthetic                            # noqa: E402
-from loans_amd.runtime import training                              # noqa: E402
+from loans_amd.runtime import checkpoint, training                  # noqa: E402
 
 SYNTHETIC = 'synthetic'
+# what --resume holds against the checkpoint's arguments: everything the data sequence and the model's shape depend on
+RESUME_FIXED = ('use_resnet_18', 'dtype', 'optimizer', 'batch_size', 'gpus', 'image_size', 'train_file', 'val_file', 'dataset_size',
+                'validation_size', 'synthetic_classes', 'data_seed', 'no_shuffle', 'augment', 'rrc_scale', 'rrc_ratio', 'val_crop_pct',
+                'augment_seed', 'seed')
 
 
 class SyntheticClasses:
@@ -114,6 +136,11 @@ class Arguments(argparse.Namespace):
     # decode-once frame cache of --augment rrc on files
     frame_cache_gb = 0.0
     frame_cache_where = 'device'
+
+    # full-state checkpoints (loans_amd/runtime/checkpoint.py: FLAGS); logged only where the command line gives them
+    checkpoint_interval = 0
+    checkpoint_keep = 2
+    resume = None
 
     _PIPELINE = ('augment', 'rrc_scale', 'rrc_ratio', 'val_crop_pct', 'augment_seed')
     _PARALLEL = ('gpus', 'warmup_epochs', 'warmup_start_factor', 'validation_sums')
@@ -167,9 +194,13 @@ def parse_args(argv=None):
     # decode-once frame cache
     parser.add_argument("--frame-cache-gb", type=float, default=argparse.SUPPRESS, help="with --augment rrc on files: keep up to this many GB of decoded frames per rank and crop later epochs out of them (default 0: off)")
     parser.add_argument("--frame-cache-where", default=argparse.SUPPRESS, choices=['device', 'host'], help="keep the frames in HBM (default) or in host memory")
+    checkpoint.add_arguments(parser, argparse.SUPPRESS)
     args = parser.parse_args(argv, namespace=Arguments())
     try:
         check_cache_arguments(args)
+        if args.resume is not None:
+            world = os.environ.get('WORLD_SIZE')        # a rank under a launcher: the group's size, whatever --gpus says
+            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world))
     except ValueError as e:
         parser.error(str(e))
     return args
@@ -379,7 +410,14 @@ def run(args, log=print):
 
         validate = summed_validation if summed else evaluator.evaluate
 
-    if not args.flat_log_dir:
+    resumed = None
+    if args.resume is not None:
+        # the run continues in the checkpoint's log directory: no new <time>_<name>
+        resumed, changed = checkpoint.resolve_resume(args, RESUME_FIXED, log if chief else (lambda line: None), world=comm.size)
+        args.log_dir = os.path.dirname(os.path.abspath(args.resume))
+        for line in changed if chief else ():
+            log(line)
+    elif not args.flat_log_dir:
         stamp = datetime.datetime.now().isoformat() if comm.size == 1 else os.environ.get('TORCHELASTIC_RUN_ID', 'dp') + \
             '_' + datetime.datetime.now().strftime('%Y-%m-%dT%H')
         args.log_dir = os.path.join(args.log_dir, "{}_{}".format(stamp, args.ln))
@@ -387,14 +425,28 @@ def run(args, log=print):
         os.makedirs(args.log_dir, exist_ok=True)
     data_to_log = {'log_dir': args.log_dir, 'image_size': list(args.image_size), 'localizer': [localizer.__class__.__name__, 'localizer.py']}
     for argument in filter(lambda x: not x.startswith('_'), dir(args)):
+        if argument in checkpoint.FLAGS and checkpoint.FLAGS[argument] == getattr(args, argument):
+            continue        # a run without the checkpoint options logs what it always logged
         data_to_log[argument] = getattr(args, argument)
     log_entries = []
+    state = dict(models={'model': model}, optimizers={'main': optimizer}, iterators={'main': train_iter}, comm=comm)
 
     def snapshot_path(it):
         return os.path.join(args.log_dir, '%s_%d.npz' % (localizer.__class__.__name__, it))
 
     t0 = time.time()
     it = 0
+    if resumed is not None:
+        # before the first step: model, optimiser, iterator and streams as they stood after iteration `resumed['iteration']`
+        checkpoint.load_checkpoint(args.resume, **state)
+        optimizer.hyperparam.weight_decay_rate = args.weight_decay      # the rates are the new command line's (--lr: set per step below)
+        if args.optimizer == 'sgd':
+            optimizer.hyperparam.momentum = args.momentum
+        it = updater.iteration = int(resumed['iteration'])
+        t0 -= float(resumed['elapsed_time'])
+        log_entries = checkpoint.read_log(args.log_dir, it)
+        if chief:
+            log('resumed %s: iteration %d, epoch %d' % (args.resume, it, updater.epoch))
     while updater.epoch < args.num_epoch and (args.iterations is None or it < args.iterations):
         lr = scheduled_lr(args.learning_rate, updater.epoch, args.lr_drop_epochs, args.lr_drop_factor) * \
             warmup_factor(updater.epoch_detail, args.warmup_epochs, args.warmup_start_factor)
@@ -443,6 +495,9 @@ def run(args, log=print):
                     json.dump(log_entries, f, indent=4, default=str)
         if chief and it % args.snapshot_interval == 0:
             loans_amd.save_npz(snapshot_path(it), localizer)
+        if checkpoint.due(it, args.checkpoint_interval, last):      # of `it` and the arguments alone: LOCK STEP holds (a barrier inside)
+            checkpoint.save_checkpoint(args.log_dir, it, keep=args.checkpoint_keep, meta={
+                'epoch': updater.epoch, 'elapsed_time': time.time() - t0, 'args': checkpoint.plain_arguments(args)}, **state)
     train_iter.finalize()
     if evaluator is not None:
         validation_iter.finalize()

@@ -22,6 +22,25 @@ default to it --, ``--iterations N`` (stop early), ``--gpus N`` (data parallel, 
 
     python train_sheep_localizer.py --use-resnet-18 -b 64 --iterations 20
     python train_sheep_localizer.py --gpus 8 --use-resnet-18 -b 128        (forks its own 8 ranks)
+
+``--checkpoint-interval N`` writes a full-state checkpoint, ``checkpoint_<iteration>.npz`` in the log directory, after every
+N-th iteration and after the last one (default 0: none; ``--checkpoint-keep K``, default 2, keeps the newest K): both models
+with their BN statistics, both AMSGrad optimisers (``m``, ``v``, ``vhat``, ``t``), the ``main`` and ``real`` iterators as of the
+batches the step consumed (shuffle streams, orders, positions, the augmentation draw stream), NumPy's global stream
+(``rotation_dropout`` draws from it) and the run's arguments (loans_amd/runtime/checkpoint.py; under ``--gpus N`` one small
+record per rank beside rank 0's file, which is written last).  ``--resume PATH`` -- a checkpoint file, or a log directory, whose
+newest complete checkpoint is taken -- continues that run in its log directory: the ``log`` file is read back and appended
+to, ``elapsed_time`` and the snapshot names count on.  Unlike ``--rd`` it freezes nothing: the assessor goes on training unless
+the checkpointed run itself had ``--rd``.  With ``--use-graph`` the state is restored before the step is captured.  Fixed on
+resume (one error lists every one that differs): the architecture, ``--dtype``, ``-b``, ``--gpus``, ``--image-size``,
+``--target-size``, the three dataset files or the synthetic sizes and ``--data-seed``, ``--no-shuffle``, ``--no-imgaug``,
+``--seed``, ``--rd``.  Taken from the new command line (each one that differs is printed once): ``--num-epoch``,
+``--iterations``, the log, snapshot and checkpoint intervals, the loader threads / processes, the frame cache options, ``--lr``,
+``--localizer-target``, ``--use-graph``.  The frame cache starts empty after a resume and refills during the first epoch.
+
+    python train_sheep_localizer.py train.txt val.csv reference/images.csv --use-resnet-18 -b 64 --checkpoint-interval 500
+    python train_sheep_localizer.py train.txt val.csv reference/images.csv --use-resnet-18 -b 64 --checkpoint-interval 500 \
+        --resume sheep_logs/<time>_test
 """
 import argparse
 import datetime
@@ -46,9 +65,14 @@ import torch                # noqa: E402
 import loans_amd            # noqa: E402
 from loans_amd import parallel                  # noqa: E402
 from loans_amd.datasets import synthetic        # noqa: E402
-from loans_amd.runtime import training          # noqa: E402
+from loans_amd.runtime import checkpoint, training      # noqa: E402
 
 SYNTHETIC = 'synthetic'
+# what --resume holds against the checkpoint's arguments: everything the data sequence and the models' shapes depend on, and
+# --rd, which freezes the assessor
+RESUME_FIXED = ('use_resnet_18', 'dtype', 'batch_size', 'gpus', 'image_size', 'target_size', 'train_file', 'val_file',
+                'reference_file', 'dataset_size', 'validation_size', 'data_seed', 'no_shuffle', 'use_imgaug', 'seed',
+                'resume_discriminator')
 
 
 class SyntheticFrames:
@@ -181,7 +205,15 @@ def parse_args(argv=None):
     parser.add_argument("--dtype", default='f32', choices=['f32', 'bf16'],
                         help="f32: the parity path; bf16: bf16 activations / gradients in HBM and bf16 MFMA, fp32 master "
                              "weights and gradient accumulation (not in the reference, which is fp32 only)")
-    return parser.parse_args(argv)
+    checkpoint.add_arguments(parser)
+    args = parser.parse_args(argv)
+    if args.resume is not None:
+        try:
+            world = os.environ.get('WORLD_SIZE')        # a rank under a launcher: the group's size, whatever --gpus says
+            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world))
+        except ValueError as e:
+            parser.error(str(e))
+    return args
 
 
 def build_models(args):
@@ -301,8 +333,17 @@ def run(args, log=print):
         sheep_evaluator = loans_amd.SheepMAPEvaluator(localizer, args.gpu)
         evaluator = training.Evaluator(validation_iter, localizer, device=args.gpu, eval_func=sheep_evaluator)
 
+    for name, default in checkpoint.FLAGS.items():
+        setattr(args, name, getattr(args, name, default))
+    resumed = None
+    if args.resume is not None:
+        # the run continues in the checkpoint's log directory: no new <time>_<name>
+        resumed, changed = checkpoint.resolve_resume(args, RESUME_FIXED, log if comm.rank == 0 else (lambda line: None), world=comm.size)
+        args.log_dir = os.path.dirname(os.path.abspath(args.resume))
+        for line in changed if comm.rank == 0 else ():
+            log(line)
     # reference :158-162: <log-dir>/<iso time>_<log name>
-    if not args.flat_log_dir:
+    elif not args.flat_log_dir:
         stamp = datetime.datetime.now().isoformat() if comm.size == 1 else os.environ.get('TORCHELASTIC_RUN_ID', 'dp') + \
             '_' + datetime.datetime.now().strftime('%Y-%m-%dT%H')
         args.log_dir = os.path.join(args.log_dir, "{}_{}".format(stamp, args.ln))
@@ -313,8 +354,13 @@ def run(args, log=print):
                    'discriminator': [discriminator.__class__.__name__, 'discriminator.py'], 'discriminator_output_dim': 1,
                    'localizer': [localizer.__class__.__name__, 'localizer.py']}
     for argument in filter(lambda x: not x.startswith('_'), dir(args)):
+        if argument in checkpoint.FLAGS and checkpoint.FLAGS[argument] == getattr(args, argument):
+            continue        # a run without the checkpoint options logs what it always logged
         data_to_log[argument] = getattr(args, argument)
     log_entries = []
+    state = dict(models={'localizer': localizer, 'discriminator': discriminator},
+                 optimizers={'opt_gen': localizer_optimizer, 'opt_dis': discriminator_optimizer},
+                 iterators={'main': data_iter, 'real': reference_iter}, comm=comm)
 
     def snapshot(it):
         for model in (localizer, discriminator):
@@ -326,6 +372,18 @@ def run(args, log=print):
     history = []
     t0 = time.time()
     it = 0
+    if resumed is not None:
+        # before the first step -- so before a capture --: models, optimisers, iterators and streams as they stood after
+        # iteration `resumed['iteration']`
+        checkpoint.load_checkpoint(args.resume, **state)
+        for optimizer in (localizer_optimizer, discriminator_optimizer):
+            optimizer.alpha = args.learning_rate        # the rate is the new command line's
+        it = updater.iteration = int(resumed['iteration'])
+        updater.graph_warmup += it                      # --use-graph: the eager iterations in front of the capture, again
+        t0 -= float(resumed['elapsed_time'])
+        if comm.rank == 0:
+            log_entries = checkpoint.read_log(args.log_dir, it)
+            log('resumed %s: iteration %d, epoch %d' % (args.resume, it, updater.epoch))
     while updater.epoch < args.num_epoch and (args.iterations is None or it < args.iterations):
         updater.update()
         it = updater.iteration
@@ -366,6 +424,9 @@ def run(args, log=print):
         # reference :182-186: a snapshot on every new epoch, or every snapshot_interval iterations
         if comm.rank == 0 and (updater.is_new_epoch if args.snapshot_every_epoch else it % args.snapshot_interval == 0):
             snapshot(it)
+        if checkpoint.due(it, args.checkpoint_interval, last):      # of `it` and the arguments alone, the same on every rank (a barrier inside)
+            checkpoint.save_checkpoint(args.log_dir, it, keep=args.checkpoint_keep, meta={
+                'epoch': updater.epoch, 'elapsed_time': time.time() - t0, 'args': checkpoint.plain_arguments(args)}, **state)
     for iterator in (data_iter, reference_iter):
         iterator.finalize()
     if comm.rank == 0:
