@@ -221,7 +221,9 @@ __global__ __launch_bounds__(256) void axpby_kernel(float a, const float* x, flo
 
 // ---- spatial transformer -------------------------------------------------------------------
 __device__ __forceinline__ float lin_coord(int i, int n) {
-    // numpy.linspace(-1, 1, n, dtype=float32): float64 arithmetic, last point exactly 1
+    // numpy.linspace(-1, 1, n, dtype=float32): float64 arithmetic, last point exactly 1.  The product rounds before the sum, as
+    // NumPy's does: fused, the centre point of an odd n (3 * fl(2 / 6) - 1) is 5.6e-17 and not 0
+#pragma clang fp contract(off)
     if (n == 1) return -1.f;
     if (i == n - 1) return 1.f;
     return (float)(-1.0 + (double)i * (2.0 / (double)(n - 1)));
@@ -266,10 +268,13 @@ struct Bilin {
 };
 
 __device__ __forceinline__ Bilin bilin_setup(float gx, float gy, int H, int W) {
+    // the coordinates decide floor() and the clip / mask comparisons: every operator below rounds on its own, as NumPy's
+    // float32 does (plain operators: the pragma does not reach into __fmul_rn and its kin)
+#pragma clang fp contract(off)
     Bilin s;
     // chainer spatial_transformer_sampler: (u + 1) * (W - 1) / 2 + 1 in float32
-    s.u = __fadd_rn(__fdiv_rn(__fmul_rn(__fadd_rn(gx, 1.f), (float)(W - 1)), 2.f), 1.f);
-    s.v = __fadd_rn(__fdiv_rn(__fmul_rn(__fadd_rn(gy, 1.f), (float)(H - 1)), 2.f), 1.f);
+    s.u = (gx + 1.f) * (float)(W - 1) / 2.f + 1.f;
+    s.v = (gy + 1.f) * (float)(H - 1) / 2.f + 1.f;
     const float uc = fminf(fmaxf(s.u, 0.f), (float)(W + 1));
     const float vc = fminf(fmaxf(s.v, 0.f), (float)(H + 1));
     s.u0 = min(max((int)floorf(uc), 0), W);
@@ -289,6 +294,10 @@ __device__ __forceinline__ float pad_fetch(const float* plane, int vp, int up, i
 
 __global__ __launch_bounds__(256) void st_sampler_fwd_kernel(const float* img, const float* grid, float* rois, int B,
                                                              int H, int W, int P) {
+    // unfused products and sums.  The pragma is what keeps the roundings apart, and it reaches only operators written
+    // in this function: HIP's __fmul_rn / __fadd_rn are a plain `*` / `+` inside a header function compiled under the default
+    // -ffp-contract=fast, and a pair of them still became one v_fmac_f32.
+#pragma clang fp contract(off)
     const int64_t total = (int64_t)B * P;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t b = i / P;
@@ -300,10 +309,10 @@ __global__ __launch_bounds__(256) void st_sampler_fwd_kernel(const float* img, c
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float* plane = img + (b * 3 + c) * (int64_t)H * W;
-            float y = __fmul_rn(w1, pad_fetch(plane, s.v0, s.u0, H, W));
-            y = __fadd_rn(y, __fmul_rn(w2, pad_fetch(plane, s.v0, s.u0 + 1, H, W)));
-            y = __fadd_rn(y, __fmul_rn(w3, pad_fetch(plane, s.v0 + 1, s.u0, H, W)));
-            y = __fadd_rn(y, __fmul_rn(w4, pad_fetch(plane, s.v0 + 1, s.u0 + 1, H, W)));
+            float y = w1 * pad_fetch(plane, s.v0, s.u0, H, W);
+            y = y + w2 * pad_fetch(plane, s.v0, s.u0 + 1, H, W);
+            y = y + w3 * pad_fetch(plane, s.v0 + 1, s.u0, H, W);
+            y = y + w4 * pad_fetch(plane, s.v0 + 1, s.u0 + 1, H, W);
             o[c] = y;
         }
         f32x4 v = {o[0], o[1], o[2], 0.f};
@@ -363,6 +372,8 @@ __global__ __launch_bounds__(256) void mse_bwd_kernel(const float* y, const floa
 // corner points of sample b: TL = (0,0), TR = (0,tw-1), BL = (th-1,0)
 __global__ __launch_bounds__(256) void grid_loss_fwd_kernel(const float* grid, float* loss, int kind, float imgH,
                                                             float imgW, float oob_scale, int B, int th, int tw) {
+    // the sign of `a * H - b * H` decides a tie: a product fused into the subtraction would see the unrounded a * H
+#pragma clang fp contract(off)
     __shared__ float sh[4];
     const int P = th * tw;
     float acc = 0.f;
@@ -388,6 +399,7 @@ __global__ __launch_bounds__(256) void grid_loss_fwd_kernel(const float* grid, f
 __global__ __launch_bounds__(256) void grid_loss_bwd_kernel(const float* grid, const float* gloss, float* ggrid,
                                                             int kind, float imgH, float imgW, float oob_scale, int B,
                                                             int th, int tw) {
+#pragma clang fp contract(off)        // as in grid_loss_fwd_kernel: the tie comparisons see rounded products
     const int P = th * tw;
     const float gl = gloss[0];
     for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < B; b += gridDim.x * blockDim.x) {

@@ -9,19 +9,9 @@ import loans_amd
 from oracle import chainer_ops as C
 from oracle import model as M
 from tests.gpu_util import build_pair, dev, inputs, oracle_params
+from tests.misc_kernels.cases import ones_deconv as _ones_deconv
 
 pytestmark = pytest.mark.gpu
-
-
-def _ones_deconv(f, H, W, s, p):
-    """F.deconvolution_2d(f, ones(1, 1, kh, kw), stride s, pad p, outsize (H, W)), kh = H + 2p - s (fh - 1)  (visual_backprop.py:29-37)"""
-    B, fh, fw = f.shape
-    kh, kw = H + 2 * p - s * (fh - 1), W + 2 * p - s * (fw - 1)
-    full = np.zeros((B, s * (fh - 1) + kh, s * (fw - 1) + kw))
-    for i in range(fh):
-        for j in range(fw):
-            full[:, s * i:s * i + kh, s * j:s * j + kw] += f[:, i:i + 1, j:j + 1]
-    return full[:, p:p + H, p:p + W]
 
 
 def _oracle_visual_backprop(lp, frames, crop):

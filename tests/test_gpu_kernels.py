@@ -648,7 +648,8 @@ def test_spatial_transformer_forward_backward():
     np.testing.assert_allclose(grid.cpu().numpy(), grid_ref, atol=2e-7)
     rois_ref = C.st_sampler_fwd(img, grid_ref)
     rois = ops.st_sampler_fwd(dev(img), dev(grid_ref))
-    np.testing.assert_allclose(rois.cpu().numpy()[..., :3].transpose(0, 3, 1, 2), rois_ref, atol=1e-6)
+    # unfused products and sums: the float32 oracle's bits; tests/misc_kernels holds the case grid
+    np.testing.assert_array_equal(rois.cpu().numpy()[..., :3].transpose(0, 3, 1, 2), rois_ref)
     gy = rng.standard_normal(rois_ref.shape).astype(np.float32)
     gg_ref = C.st_sampler_bwd_grid(img, grid_ref, gy)
     gg = ops.st_sampler_bwd_grid(dev(img), dev(grid_ref), dev(_nhwc(gy, 4)))
