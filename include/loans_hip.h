@@ -577,6 +577,16 @@ int loans_softmax_xent_fwd_f32(const float* z, const int32_t* t, float* gz, floa
 int loans_softmax_xent_ls_fwd_f32(const float* z, const int32_t* t, float* gz, float* row_loss, float* row_hit,
                                   float* row_hitk, float* out /* [3] */, int32_t B, int32_t N, double eps, int32_t k,
                                   void* stream);
+/* The same against a TWO-LABEL target (a mixup / CutMix batch): with w = lam onehot(ta) + oml onehot(tb) (ta == tb: lam + oml on
+ * that class), q = (1 - eps) w + eps / N, row_loss = lse - (1 - eps) (lam z_ta + oml z_tb) - eps mean(z), gz = (softmax(z) - q) / count.
+ * The weights are taken as they are (the caller makes them sum to one).  A row counts when BOTH labels lie in [0, N); any other
+ * row has loss 0, gz 0 and no hit.  row_hit / row_hitk are taken against the dominant label, ta if lam >= oml, else tb, by the
+ * rules above.  out as above.  The weights (1, 0) run loans_softmax_xent_ls_fwd_f32 on (z, ta), the weights (0, 1) on (z, tb):
+ * every output carries that entry's bits and the label of weight zero is not read (it does not decide whether a row counts).
+ * Limits as above; LOANS_EINVAL also for a non-finite weight. */
+int loans_softmax_xent_mix_fwd_f32(const float* z, const int32_t* ta, const int32_t* tb, float lam, float oml,
+                                   float* gz, float* row_loss, float* row_hit, float* row_hitk, float* out /* [3] */,
+                                   int32_t B, int32_t N, double eps, int32_t k, void* stream);
 /* Evaluation: the plain loss (eps = 0), the top-1 and the top-k hit of every row as defined above, summed into running totals;
  * no gradient is written.  rows: 3 * B floats of scratch (row loss, hit, top-k hit).  acc[5], doubles, read-modify-write:
  * acc[0] += sum of row losses, acc[1] += top-1 hits, acc[2] += top-k hits, acc[3] += rows not ignored, acc[4] += B.  The five sums
@@ -733,6 +743,20 @@ int loans_crop_resize_srcs_u8_f32(const uint8_t* const* srcs, const int32_t* src
                                   int32_t outH, int32_t outW, void* stream);
 /* output rows per block of that launch (host arithmetic only; <= 0 for non-positive sizes) */
 int loans_crop_band_rows(int32_t outH, int32_t outW);
+
+/* ---- mixup / CutMix of a device batch with a shifted copy of itself (csrc/mix.hip).  x, out: contiguous [B][C][H][W] fp32;
+ *      row b's partner is row p = (b - shift) mod B.  Per element of row b
+ *        inside the box y0 <= y < y1, x0 <= x < x1      out = x[p]                          (a bit copy)
+ *        outside, oml == 0                              out = x[b]                          (a bit copy; the partner is not read)
+ *        outside, otherwise                             out = fma(lam, x[b], oml * x[p])    (fp32: two roundings)
+ *      mixup: an empty box and (lam, 1 - lam); CutMix: a box and (1, 0); no mixing: an empty box and (1, 0).  One streaming
+ *      launch, 16-byte accesses where W % 4 == 0 and both pointers are 16-byte aligned; no atomics: two launches, the same bits.
+ *      LOANS_EINVAL -- before any launch -- for a null pointer, out == x (partners are read after they would be written),
+ *      non-positive sizes, shift outside [0, B), a box that is not 0 <= y0 <= y1 <= H, 0 <= x0 <= x1 <= W, a non-finite
+ *      weight; LOANS_ERANGE for C * H * W >= 2^30 (the batch itself is indexed in 64 bits). ---- */
+int loans_batch_mix_f32(const float* x, float* out, int32_t B, int32_t C, int32_t H, int32_t W,
+                        int32_t shift, float lam, float oml,
+                        int32_t y0, int32_t x0, int32_t y1, int32_t x1, void* stream);
 
 /* library / build identification */
 const char* loans_hip_version(void);

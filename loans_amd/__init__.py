@@ -15,6 +15,7 @@ from .sheep.sheep_updater import SheepAssessor, SheepUpdater  # noqa: F401
 from .sheep.sheep_evaluator import SheepMAPEvaluator  # noqa: F401
 from .common.net import ResnetAssessor  # noqa: F401
 from .classifier import Classifier, ClassificationMetrics  # noqa: F401
+from .mixed_labels import MixedLabels  # noqa: F401
 from .common.utils import Size, DirectionLossCalculator, OutOfImageLossCalculator  # noqa: F401
 from .functions.rotation_dropout import rotation_dropout, RotationDropout  # noqa: F401
 

@@ -123,6 +123,7 @@ SIGNATURES = {
     'loans_crop_resize_u8_f32': [_p, _p, _p, _i32, _p, _i32, _i32, _i32, _p],
     'loans_crop_resize_srcs_u8_f32': [_p, _p, _i32, _p, _p, _i32, _p, _i32, _i32, _i32, _p],
     'loans_crop_band_rows': [_i32, _i32],
+    'loans_batch_mix_f32': [_p, _p, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _i32, _i32, _i32, _p],
     'loans_prep_images_f32': [_p, _p, _i32, _i32, _i32, _p],
     'loans_prep_images_dense_f32': [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p],
     'loans_prep_images_dense_bf16': [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p],
@@ -154,6 +155,7 @@ SIGNATURES = {
     'loans_linear_wide_bwd_f32': [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p],
     'loans_softmax_xent_fwd_f32': [_p, _p, _p, _p, _p, _p, _i32, _i32, _p],
     'loans_softmax_xent_ls_fwd_f32': [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _f64, _i32, _p],
+    'loans_softmax_xent_mix_fwd_f32': [_p, _p, _p, _f32, _f32, _p, _p, _p, _p, _p, _i32, _i32, _f64, _i32, _p],
     'loans_softmax_xent_eval_f32': [_p, _p, _p, _p, _i32, _i32, _i32, _p],
     'loans_scale_by_scalar_f32': [_p, _p, _p, _i64, _p],
     'loans_mul_f32': [_p, _p, _p, _i64, _p],

@@ -6,7 +6,9 @@ runs), ``topk=k`` also reports ``accuracy_top<k>``; with neither, the loss funct
 import torch
 
 from . import ops
-from .functions.ops_small import _as_labels, softmax_cross_entropy_with_accuracy, softmax_cross_entropy_with_topk_accuracy
+from .functions.ops_small import (_as_labels, softmax_cross_entropy_mixed, softmax_cross_entropy_with_accuracy,
+                                  softmax_cross_entropy_with_topk_accuracy)
+from .mixed_labels import MixedLabels
 from .runtime.core import Chain, Variable, config, report, using_config
 
 
@@ -55,6 +57,13 @@ class Classifier(Chain):
     def __call__(self, *args):
         *xs, t = args
         self._predict(*xs)
+        if isinstance(t, MixedLabels):          # a mixup / CutMix batch: the same keys, the accuracies against the dominant label
+            self.loss, self.accuracy, self.accuracy_topk = softmax_cross_entropy_mixed(
+                self.y, t, self.label_smoothing if config.train else 0.0, self.topk or 1)
+            report({'loss': self.loss, 'accuracy': self.accuracy}, self)
+            if self.topk is not None:
+                report({'accuracy_top%d' % self.topk: self.accuracy_topk}, self)
+            return self.loss
         if self.label_smoothing == 0.0 and self.topk is None:
             self.loss, self.accuracy = softmax_cross_entropy_with_accuracy(self.y, t)
             report({'loss': self.loss, 'accuracy': self.accuracy}, self)

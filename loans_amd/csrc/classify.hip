@@ -1,6 +1,7 @@
 // The ImageNet classification head: a wide Linear layer (9 .. 2^16 outputs) in three directions on the fp32 matrix cores
 // (v_mfma_f32_32x32x2_f32), and softmax cross-entropy with top-1 accuracy in one pass over the logits (and its label-smoothed
-// form with a top-k hit), and the evaluation form that writes no gradient and adds the batch to running sums in double.
+// form with a top-k hit, and the two-label form of a mixup / CutMix batch), and the evaluation form that writes no gradient and
+// adds the batch to running sums in double.
 // No atomics anywhere in this file: every output element is owned by one lane (GEMM) or one block (loss rows) and is summed
 // in an order that depends on the shape alone, so two launches on the same inputs give the same bits.
 #include "common.h"
@@ -288,6 +289,85 @@ __global__ __launch_bounds__(256) void softmax_xent_ls_reduce_kernel(const float
     if (tid == 0) { out[0] = L / (float)count; out[1] = A / (float)B; out[2] = AK / (float)B; }
 }
 
+// The two-label form (loans_softmax_xent_mix_fwd_f32: the target of a mixup / CutMix batch).  With w_i = lam [i == ta] + oml [i == tb]
+// (ta == tb: the sum of the two weights on that class)
+//   q = (1 - eps) w + eps / N,   loss = lse - (1 - eps) (lam z_ta + oml z_tb) - eps mean(z),   gz = (softmax(z) - q) / count
+// A row counts when BOTH labels lie in [0, N); hit and rank are taken against the dominant label (ta if lam >= oml, else tb).
+// The products are plain C++: the compiler may contract a multiply-add, which removes a rounding and adds none.  This kernel
+// never sees the weights (1, 0) or (0, 1): the launcher hands those to softmax_xent_ls_rows_kernel on the one label that counts.
+struct XentMix { XentLs ls; float lam, oml; };
+
+__global__ __launch_bounds__(256) void softmax_xent_mix_rows_kernel(const float* __restrict__ z, const int* __restrict__ ta,
+                                                                    const int* __restrict__ tb, float* __restrict__ gz,
+                                                                    float* __restrict__ row_loss, float* __restrict__ row_hit,
+                                                                    float* __restrict__ row_hitk, int B, int N, XentMix mx) {
+    extern __shared__ __attribute__((aligned(16))) float row[];
+    __shared__ float shf[4];
+    __shared__ int shi[4];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const float* zr = z + (int64_t)b * N;
+    float* gr = gz + (int64_t)b * N;
+
+    int valid = 0;
+    for (int i = tid; i < B; i += 256) valid += ((unsigned)ta[i] < (unsigned)N) & ((unsigned)tb[i] < (unsigned)N);
+    const int count = max(block_count_256(valid, shi), 1);
+
+    float m;
+    int am;
+    row_stage_argmax(zr, row, N, shf, shi, m, am);
+
+    const int la = ta[b], lb = tb[b];
+    if ((unsigned)la >= (unsigned)N || (unsigned)lb >= (unsigned)N) {       // ignored row (uniform per block)
+        for (int i = tid; i < N; i += 256) gr[i] = 0.f;
+        if (tid == 0) { row_loss[b] = 0.f; row_hit[b] = 0.f; row_hitk[b] = 0.f; }
+        return;
+    }
+    const int label = mx.lam >= mx.oml ? la : lb;
+    if (tid == 0) row_hit[b] = (am == label) ? 1.f : 0.f;
+    const int rank = row_rank(row, N, label, row[label], shi);
+    if (tid == 0) row_hitk[b] = (rank < mx.ls.k) ? 1.f : 0.f;
+
+    const float zmix = mx.lam * row[la] + mx.oml * row[lb];
+    const float S = row_sum_exp(row, N, m, shf);
+    const float fc = (float)count;
+    if (mx.ls.eps == 0.f) {
+        if (tid == 0) row_loss[b] = (m + logf(S)) - zmix;
+    } else {
+        float zs = 0.f;
+        for (int i = tid; i < N; i += 256) zs += row[i];
+        const float mean = block_sum_256(zs, shf) / (float)N;
+        if (tid == 0) row_loss[b] = ((m + logf(S)) - mx.ls.omeps * zmix) - mx.ls.eps * mean;
+    }
+    // (eps == 0: omeps = 1 and q_off = 0, so q is w itself)
+    for (int i = tid; i < N; i += 256) {
+        const float p = expf(row[i] - m) / S;
+        const float w = (i == la ? mx.lam : 0.f) + (i == lb ? mx.oml : 0.f);
+        gr[i] = (p - (mx.ls.omeps * w + mx.ls.q_off)) / fc;
+    }
+}
+
+// softmax_xent_ls_reduce_kernel with the two-label count
+__global__ __launch_bounds__(256) void softmax_xent_mix_reduce_kernel(const float* __restrict__ row_loss, const float* __restrict__ row_hit,
+                                                                      const float* __restrict__ row_hitk, const int* __restrict__ ta,
+                                                                      const int* __restrict__ tb, float* __restrict__ out, int B, int N) {
+    __shared__ float shf[4];
+    __shared__ int shi[4];
+    const int tid = threadIdx.x;
+    int valid = 0;
+    float l = 0.f, a = 0.f, ak = 0.f;
+    for (int i = tid; i < B; i += 256) {
+        valid += ((unsigned)ta[i] < (unsigned)N) & ((unsigned)tb[i] < (unsigned)N);
+        l += row_loss[i];
+        a += row_hit[i];
+        ak += row_hitk[i];
+    }
+    const int count = max(block_count_256(valid, shi), 1);
+    const float L = block_sum_256(l, shf);
+    const float A = block_sum_256(a, shf);
+    const float AK = block_sum_256(ak, shf);
+    if (tid == 0) { out[0] = L / (float)count; out[1] = A / (float)B; out[2] = AK / (float)B; }
+}
+
 // Evaluation (loans_softmax_xent_eval_f32): the plain loss, the top-1 and the top-k hit of every row -- the eps == 0 expressions
 // of softmax_xent_ls_rows_kernel on the same row code -- and no gradient.  rows: [0, B) loss, [B, 2B) hit, [2B, 3B) top-k hit.
 __global__ __launch_bounds__(256) void softmax_xent_eval_rows_kernel(const float* __restrict__ z, const int* __restrict__ t,
@@ -427,6 +507,28 @@ extern "C" int loans_softmax_xent_ls_fwd_f32(const float* z, const int32_t* t, f
                        row_hitk, B, N, ls);
     LOANS_LAUNCH_CHECK();
     hipLaunchKernelGGL(softmax_xent_ls_reduce_kernel, dim3(1), dim3(256), 0, st, row_loss, row_hit, row_hitk, t, out, B, N);
+    LOANS_LAUNCH_CHECK();
+    return LOANS_OK;
+}
+
+extern "C" int loans_softmax_xent_mix_fwd_f32(const float* z, const int32_t* ta, const int32_t* tb, float lam, float oml,
+                                              float* gz, float* row_loss, float* row_hit, float* row_hitk, float* out,
+                                              int32_t B, int32_t N, double eps, int32_t k, void* stream) {
+    if (!z || !ta || !tb || !gz || !row_loss || !row_hit || !row_hitk || !out || B <= 0 || N <= 0) return LOANS_EINVAL;
+    if (!(eps >= 0.0 && eps < 1.0) || k < 1 || !__builtin_isfinite(lam) || !__builtin_isfinite(oml)) return LOANS_EINVAL;
+    // one label per row: the label-smoothed kernels themselves on the label that carries the whole weight -- their bits; the
+    // other label is not read
+    if (lam == 1.f && oml == 0.f) return loans_softmax_xent_ls_fwd_f32(z, ta, gz, row_loss, row_hit, row_hitk, out, B, N, eps, k, stream);
+    if (lam == 0.f && oml == 1.f) return loans_softmax_xent_ls_fwd_f32(z, tb, gz, row_loss, row_hit, row_hitk, out, B, N, eps, k, stream);
+    if (N > XENT_MAX_N || B > XENT_MAX_B) return LOANS_ERANGE;
+    XentMix mx;
+    mx.ls.eps = (float)eps; mx.ls.omeps = (float)(1.0 - eps); mx.ls.q_off = (float)(eps / N); mx.ls.q_on = mx.ls.omeps + mx.ls.q_off;
+    mx.ls.k = k; mx.lam = lam; mx.oml = oml;
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(softmax_xent_mix_rows_kernel, dim3(B), dim3(256), (size_t)N * sizeof(float), st, z, ta, tb, gz, row_loss,
+                       row_hit, row_hitk, B, N, mx);
+    LOANS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(softmax_xent_mix_reduce_kernel, dim3(1), dim3(256), 0, st, row_loss, row_hit, row_hitk, ta, tb, out, B, N);
     LOANS_LAUNCH_CHECK();
     return LOANS_OK;
 }

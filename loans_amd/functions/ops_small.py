@@ -162,6 +162,21 @@ class SoftmaxCrossEntropyTopK(SoftmaxCrossEntropy):
         return out[0], out[1], out[2]
 
 
+class SoftmaxCrossEntropyMixed(SoftmaxCrossEntropyTopK):
+    """The same against the target of a mixed batch, ``lam q(t_a) + oml q(t_b)`` with ``q`` the label-smoothed one-label target:
+    inputs (x, t_a, t_b), outputs (loss, accuracy, accuracy_topk), the accuracies against the label of the larger weight.  The
+    weights (1, 0) give ``SoftmaxCrossEntropyTopK``'s bits on (x, t_a).  The backward is the parent's."""
+
+    def __init__(self, lam32, oml32, label_smoothing, topk):
+        super().__init__(label_smoothing, topk)
+        self.lam32, self.oml32 = float(lam32), float(oml32)
+
+    def forward(self, inputs):
+        x, ta, tb = (a.contiguous() for a in inputs)
+        out, self.gz, _, _, _ = ops.softmax_xent_mix_fwd(x, ta, tb, self.lam32, self.oml32, self.label_smoothing, self.topk)
+        return out[0], out[1], out[2]
+
+
 def _as_labels(x, t):
     import numpy as np
     if isinstance(t, Variable):
@@ -183,6 +198,13 @@ def softmax_cross_entropy_with_topk_accuracy(x, t, label_smoothing=0.0, topk=1, 
     if ignore_label != -1:
         raise ValueError('only ignore_label=-1 (Chainer\'s default) is built')
     return SoftmaxCrossEntropyTopK(label_smoothing, topk)(x, _as_labels(x, t))
+
+
+def softmax_cross_entropy_mixed(x, labels, label_smoothing=0.0, topk=1):
+    """(loss, accuracy, accuracy_topk) of the logits ``x`` against ``labels``, a ``MixedLabels``: the loss of a mixup / CutMix
+    batch.  The accuracies are against each row's dominant label."""
+    return SoftmaxCrossEntropyMixed(labels.lam32, labels.oml32, label_smoothing, topk)(
+        x, _as_labels(x, labels.t_a.reshape(-1)), _as_labels(x, labels.t_b.reshape(-1)))
 
 
 def softmax_cross_entropy(x, t, ignore_label=-1):

@@ -2470,6 +2470,44 @@ def softmax_xent_ls_fwd(z, t, eps, k):
     return out, gz, row_loss, row_hit, row_hitk
 
 
+def softmax_xent_mix_fwd(z, ta, tb, lam, oml, eps, k):
+    """softmax_xent_ls_fwd against the two-label target lam q(ta) + oml q(tb) of a mixed batch, q(t) = (1 - eps) onehot(t) + eps / N
+    -> (out, gz, row_loss, row_hit, row_hitk); the hits are taken against the label of the larger weight.  lam, oml: the two
+    fp32 weights.  (1, 0) gives softmax_xent_ls_fwd(z, ta, eps, k)'s bits.  No host synchronisation."""
+    assert z.dtype == torch.float32 and z.dim() == 2 and z.is_contiguous(), 'logits must be a contiguous (B, N) fp32 array'
+    for t in (ta, tb):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == z.shape[0] and t.device == z.device, \
+            'labels must be int32, one per row, on the logits\' device'
+    B, N = z.shape
+    gz = _empty_like(z)
+    row_loss = _empty((B,), device=z.device, dtype=torch.float32)
+    row_hit = _empty((B,), device=z.device, dtype=torch.float32)
+    row_hitk = _empty((B,), device=z.device, dtype=torch.float32)
+    out = _empty((3,), device=z.device, dtype=torch.float32)
+    if CLASS_COUNT is not None: _acct('heads', 0, _nbytes(z), _nbytes(gz))
+    check(_lib.load().loans_softmax_xent_mix_fwd_f32(_ptr(z), _ptr(ta), _ptr(tb), float(lam), float(oml), _ptr(gz), _ptr(row_loss),
+                                                     _ptr(row_hit), _ptr(row_hitk), _ptr(out), B, N, float(eps), int(k), _stream()),
+          'loans_softmax_xent_mix_fwd_f32')
+    return out, gz, row_loss, row_hit, row_hitk
+
+
+def batch_mix(x, shift, lam, oml, box=(0, 0, 0, 0), out=None):
+    """mixup / CutMix of the device batch x [B][C][H][W] fp32 with itself shifted by ``shift`` rows, one launch on the current
+    stream: inside ``box`` = (y0, x0, y1, x1) row b is row (b - shift) % B, outside it lam * x[b] + oml * x[partner] (oml == 0: x[b]
+    itself, bit for bit).  Returns a fresh tensor (or ``out``, which must not be x): the batch outlives the step that made it."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()):
+        raise ValueError('the batch must be a contiguous float32 [B][C][H][W] device tensor')
+    if out is None:
+        out = torch.empty_like(x)
+    elif not (out.dtype == x.dtype and out.device == x.device and out.is_contiguous() and out.shape == x.shape):
+        raise ValueError('out must be a contiguous float32 tensor of the batch\'s shape on its device')
+    B, C, H, W = x.shape
+    y0, x0, y1, x1 = (int(v) for v in box)
+    check(_lib.load().loans_batch_mix_f32(_ptr(x), _ptr(out), B, C, H, W, int(shift), float(lam), float(oml), y0, x0, y1, x1,
+                                          _stream()), 'loans_batch_mix_f32')
+    return out
+
+
 def softmax_xent_eval(z, t, acc, k=1):
     """Evaluation: add the batch's plain loss sum, top-1 hits, top-k hits, valid rows and rows to ``acc`` (5 float64 on the
     device, read-modify-write).  No gradient is written.  No host synchronisation."""

@@ -246,10 +246,13 @@ def _plain(value):
     return json.loads(json.dumps(value, default=str))
 
 
-def check_arguments(saved, args, fixed, silent=()):
+def check_arguments(saved, args, fixed, silent=(), defaults=None):
     """``saved``: the arguments in a checkpoint's meta; ``args``: this run's namespace.  ValueError listing EVERY argument of
     ``fixed`` that differs, with both values; returns one line per other argument that differs (``silent`` ones left out):
-    those are taken from the new command line."""
+    those are taken from the new command line.  ``defaults``: values for arguments ``saved`` does not hold -- options that did
+    not exist when the checkpoint was written, which ran at their defaults."""
+    if defaults:
+        saved = dict(_plain(dict(defaults)), **saved)
     now = {k: _plain(getattr(args, k)) for k in dir(args) if not k.startswith('_')}
     wrong = ['%s: %r in the checkpoint, %r now' % (k, saved.get(k), now.get(k)) for k in fixed if saved.get(k) != now.get(k)]
     if wrong:
@@ -273,9 +276,9 @@ def add_arguments(parser, defaults=FLAGS):
                         help="continue the run of this checkpoint file, or of the newest complete checkpoint in this log directory, in its log directory")
 
 
-def resolve_resume(args, fixed, log=print, world=None):
+def resolve_resume(args, fixed, log=print, world=None, defaults=None):
     """``args.resume`` -> the common file it means (``resolve``), its arguments checked against ``args`` (``check_arguments``;
-    ``world``: the world size to hold against the checkpoint's where it is not ``args.gpus``).  Returns (meta, the lines of
+    ``world``: the world size to hold against the checkpoint's where it is not ``args.gpus``; ``defaults``: see there).  Returns (meta, the lines of
     the arguments that changed); ValueError for a path that is no checkpoint and for arguments that must not change."""
     args.resume = resolve(args.resume, log)
     meta = read_meta(args.resume)
@@ -283,7 +286,7 @@ def resolve_resume(args, fixed, log=print, world=None):
         raise ValueError(world_size_message(meta['world_size'], world))
     if 'gpus' in fixed and world is None and int(meta['world_size']) != int(getattr(args, 'gpus', 1)):
         raise ValueError(world_size_message(meta['world_size'], getattr(args, 'gpus', 1)))
-    return meta, check_arguments(meta['args'], args, [k for k in fixed if k != 'gpus'], SILENT + ('gpus',))
+    return meta, check_arguments(meta['args'], args, [k for k in fixed if k != 'gpus'], SILENT + ('gpus',), defaults)
 
 
 def due(iteration, interval, last):

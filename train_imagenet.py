@@ -49,16 +49,31 @@ of examples.  The first epoch uploads whole frames where it would have uploaded 
 (training examples served from it / decoded since the previous entry), and the same four under ``feed/val_cache_`` for the
 validation set.
 
+``--mixup-alpha A`` and ``--cutmix-alpha A`` (with ``--augment rrc``; default 0: off) add the two batch-mixing regularisers on
+top of label smoothing.  One draw per batch, from a stream of its own (``--mix-seed``; the crops do not depend on it): with
+probability ``--mix-prob`` (default 1) the batch is mixed, by CutMix with probability ``--mix-switch-prob`` (default 0.5) where
+both alphas are given, else by mixup.  Every row is mixed with the row before it (row 0 with the last one): mixup blends the two
+frames with a weight drawn from Beta(A, A), CutMix pastes a box of the partner whose share of the frame is one minus such a
+weight -- one streaming launch behind the crop on the iterator's stream (loans_amd/common/datasets/batch_mix.py, csrc/mix.hip) --
+and the loss is taken against the two labels with the same weight (``MixedLabels``; csrc/classify.hip,
+``loans_softmax_xent_mix_fwd_f32``).  Under ``--gpus N`` every rank mixes inside its own batch, with the draws of
+``--mix-seed`` + 7919 r.  The logged ``accuracy`` (and top-k accuracy) of a mixed run is against each row's dominant label; the
+validation entries are the plain loss on unmixed frames.  A batch that is not mixed runs the one-label loss bit for bit.
+
+    python train_imagenet.py train.tsv val.tsv -b 256 --optimizer sgd --lr 0.1 --augment rrc --label-smoothing 0.1 \
+        --mixup-alpha 0.2 --cutmix-alpha 1.0
+
 ``--checkpoint-interval N`` writes a full-state checkpoint, ``checkpoint_<iteration>.npz`` in the log directory, after every
 N-th iteration and after the last one (default 0: none; ``--checkpoint-keep K``, default 2, keeps the newest K): the model with
 its BN statistics, the optimiser's buffers and step count, the training iterator as of the batch the step consumed (shuffle
-stream, order, position, the crop / mirror draw stream), NumPy's global stream and the run's arguments
+stream, order, position, the crop / mirror draw stream and the mix draw stream), NumPy's global stream and the run's arguments
 (loans_amd/runtime/checkpoint.py; under ``--gpus N`` one small record per rank beside rank 0's file, which is written last).
 ``--resume PATH`` -- a checkpoint file, or a log directory, whose newest complete checkpoint is taken -- continues that run in
 its log directory: the ``log`` file is read back and appended to, ``elapsed_time`` and the snapshot names count on.  Fixed on
 resume (one error lists every one that differs): the architecture, ``--dtype``, ``--optimizer``, ``-b``, ``--gpus``,
 ``--image-size``, the dataset files or the synthetic sizes, classes and ``--data-seed``, ``--no-shuffle``, ``--augment`` /
-``--rrc-*`` / ``--val-crop-pct`` / ``--augment-seed``, ``--seed``.  Taken from the new command line (each one that differs is
+``--rrc-*`` / ``--val-crop-pct`` / ``--augment-seed``, ``--mixup-alpha`` / ``--cutmix-alpha`` / ``--mix-*`` (a checkpoint from
+before these options existed ran at their defaults), ``--seed``.  Taken from the new command line (each one that differs is
 printed once): ``--num-epoch``, ``--iterations``, the log, snapshot and checkpoint intervals, ``--loader-threads``, the frame
 cache options, ``--lr``, ``--weight-decay``, ``--momentum``, ``--lr-drop-*``, ``--warmup-*``, ``--label-smoothing``, ``--topk``.  The
 frame caches start empty after a resume and refill during the first epoch.
@@ -99,7 +114,7 @@ SYNTHETIC = 'synthetic'
 # what --resume holds against the checkpoint's arguments: everything the data sequence and the model's shape depend on
 RESUME_FIXED = ('use_resnet_18', 'dtype', 'optimizer', 'batch_size', 'gpus', 'image_size', 'train_file', 'val_file', 'dataset_size',
                 'validation_size', 'synthetic_classes', 'data_seed', 'no_shuffle', 'augment', 'rrc_scale', 'rrc_ratio', 'val_crop_pct',
-                'augment_seed', 'seed')
+                'augment_seed', 'seed', 'mixup_alpha', 'cutmix_alpha', 'mix_prob', 'mix_switch_prob', 'mix_seed')
 
 
 class SyntheticClasses:
@@ -142,9 +157,17 @@ class Arguments(argparse.Namespace):
     checkpoint_keep = 2
     resume = None
 
+    # mixup / CutMix of the --augment rrc feed (loans_amd/common/datasets/batch_mix.py); both alphas 0: off
+    mixup_alpha = 0.0
+    cutmix_alpha = 0.0
+    mix_prob = 1.0
+    mix_switch_prob = 0.5
+    mix_seed = None
+
     _PIPELINE = ('augment', 'rrc_scale', 'rrc_ratio', 'val_crop_pct', 'augment_seed')
     _PARALLEL = ('gpus', 'warmup_epochs', 'warmup_start_factor', 'validation_sums')
     _CACHE = ('frame_cache_gb', 'frame_cache_where')
+    _MIX = ('mixup_alpha', 'cutmix_alpha', 'mix_prob', 'mix_switch_prob', 'mix_seed')
 
 
 def parse_args(argv=None):
@@ -194,13 +217,20 @@ def parse_args(argv=None):
     # decode-once frame cache
     parser.add_argument("--frame-cache-gb", type=float, default=argparse.SUPPRESS, help="with --augment rrc on files: keep up to this many GB of decoded frames per rank and crop later epochs out of them (default 0: off)")
     parser.add_argument("--frame-cache-where", default=argparse.SUPPRESS, choices=['device', 'host'], help="keep the frames in HBM (default) or in host memory")
+    # mixup / CutMix
+    parser.add_argument("--mixup-alpha", type=float, default=argparse.SUPPRESS, help="with --augment rrc: mixup, the weight of a batch drawn from Beta(A, A) (default 0: off)")
+    parser.add_argument("--cutmix-alpha", type=float, default=argparse.SUPPRESS, help="with --augment rrc: CutMix, the kept share of the frame drawn from Beta(A, A) (default 0: off)")
+    parser.add_argument("--mix-prob", type=float, default=argparse.SUPPRESS, help="probability that a batch is mixed at all (default 1)")
+    parser.add_argument("--mix-switch-prob", type=float, default=argparse.SUPPRESS, help="with both alphas: probability that a mixed batch takes CutMix, not mixup (default 0.5)")
+    parser.add_argument("--mix-seed", type=int, default=argparse.SUPPRESS, help="seed of the mix draws (a stream of their own)")
     checkpoint.add_arguments(parser, argparse.SUPPRESS)
     args = parser.parse_args(argv, namespace=Arguments())
     try:
         check_cache_arguments(args)
+        check_mix_arguments(args)
         if args.resume is not None:
             world = os.environ.get('WORLD_SIZE')        # a rank under a launcher: the group's size, whatever --gpus says
-            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world))
+            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS)
     except ValueError as e:
         parser.error(str(e))
     return args
@@ -215,6 +245,22 @@ def check_cache_arguments(args):
         raise ValueError('--frame-cache-gb caches the frames the GPU crops: it needs --augment rrc')
     if gb > 0 and args.train_file == SYNTHETIC:
         raise ValueError('--frame-cache-gb caches decoded files: the synthetic classes already lie in HBM, give a train_file')
+
+
+def check_mix_arguments(args):
+    """ValueError for mix options that name no distribution, and where mixing is asked of a feed that is not on the device"""
+    for name in ('mixup_alpha', 'cutmix_alpha'):
+        if not getattr(args, name) >= 0:
+            raise ValueError('--%s must not be negative, got %r' % (name.replace('_', '-'), getattr(args, name)))
+    for name in ('mix_prob', 'mix_switch_prob'):
+        if not 0.0 <= getattr(args, name) <= 1.0:
+            raise ValueError('--%s is a probability: it must lie in [0, 1], got %r' % (name.replace('_', '-'), getattr(args, name)))
+    if (args.mixup_alpha > 0 or args.cutmix_alpha > 0) and args.augment != 'rrc':
+        raise ValueError('--mixup-alpha / --cutmix-alpha mix the batches the GPU crops: they need --augment rrc')
+
+
+# what a checkpoint written before an option existed is taken to have run with: the option's default
+RESUME_DEFAULTS = {name: getattr(Arguments, name) for name in Arguments._MIX}
 
 
 def cache_budgets(total_bytes, n_train, n_validation):
@@ -318,10 +364,11 @@ def run(args, log=print):
     elif args.gpu < 0:
         args.gpu = torch.cuda.current_device()
     torch.cuda.set_device(args.gpu)
-    for name in Arguments._PIPELINE + Arguments._PARALLEL + Arguments._CACHE:      # the values this run uses, logged with the other arguments
+    for name in Arguments._PIPELINE + Arguments._PARALLEL + Arguments._CACHE + Arguments._MIX:      # the values this run uses, logged with the other arguments
         setattr(args, name, getattr(args, name, getattr(Arguments, name)))
     args.gpus = comm.size
     check_cache_arguments(args)
+    check_mix_arguments(args)
     chief = comm.rank == 0                       # prints, logs and writes snapshots
 
     # --augment rrc: the iterators hand out (frames, labels) already resident on the device
@@ -352,6 +399,12 @@ def run(args, log=print):
     # every rank built the same sets and takes every comm.size-th example: the training share padded by wrapping (all ranks make
     # the same iterations and epochs), the validation share not (every example is counted once; shares may differ by one)
     train_dataset = ShardedDataset(train_dataset, comm.rank, comm.size, pad=True)
+    if args.mixup_alpha > 0 or args.cutmix_alpha > 0:
+        # every rank mixes inside its own batch, with draws of its own: the stream of --mix-seed + 7919 r, as for the crops
+        from loans_amd.common.datasets.batch_mix import MixedBatches, MixPolicy
+        policy = MixPolicy(args.mixup_alpha, args.cutmix_alpha, args.mix_prob, args.mix_switch_prob,
+                           None if args.mix_seed is None else args.mix_seed + 7919 * comm.rank)
+        train_dataset = MixedBatches(train_dataset, policy, tuple(args.image_size))
     if validation_dataset is not None:
         validation_dataset = ShardedDataset(validation_dataset, comm.rank, comm.size, pad=False)
     train_iter = training.MultithreadIterator(train_dataset, args.batch_size, shuffle=not args.no_shuffle, n_threads=args.loader_threads, **feed)
@@ -413,7 +466,8 @@ def run(args, log=print):
     resumed = None
     if args.resume is not None:
         # the run continues in the checkpoint's log directory: no new <time>_<name>
-        resumed, changed = checkpoint.resolve_resume(args, RESUME_FIXED, log if chief else (lambda line: None), world=comm.size)
+        resumed, changed = checkpoint.resolve_resume(args, RESUME_FIXED, log if chief else (lambda line: None), world=comm.size,
+                                                     defaults=RESUME_DEFAULTS)
         args.log_dir = os.path.dirname(os.path.abspath(args.resume))
         for line in changed if chief else ():
             log(line)
