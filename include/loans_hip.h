@@ -679,6 +679,39 @@ int loans_adam_f32(float* p, const float* g, float* m, float* v, int64_t n, doub
 int loans_momentum_sgd_f32(float* p, const float* g, float* v, int64_t n, double lr, const float* lr_dev, double momentum,
                            double weight_decay_rate, double grad_scale, void* stream);
 
+/* The same with the weight decay switched off inside marked ranges of the flat buffer (BN scales / shifts, biases).  The ranges
+ * are `nseg` segments that tile [0, n): seg_end[s] is segment s's exclusive end -- ascending, no empty segment, every end but the
+ * last a multiple of 4 (a float4 never straddles a boundary), the last equal to n --, bit 0 of seg_flags[s] says "exempt from
+ * decay".  Inside an exempt segment weight_decay_rate counts as 0, everything else is loans_momentum_sgd_f32's arithmetic bit for
+ * bit.  seg_end_dev / seg_flags_dev: the table in DEVICE memory (caller-owned, alive until the launch has run; read into LDS, so
+ * nseg <= loans_momentum_sgd_max_segments() = 1024); seg_end_host: the same ends in host memory, checked on every call --
+ * LOANS_EINVAL, and no launch, for a table that breaks a rule above, a null pointer or p / g / v off a 16-byte boundary. */
+int loans_momentum_sgd_seg_f32(float* p, const float* g, float* v, int64_t n, double lr, const float* lr_dev, double momentum,
+                               double weight_decay_rate, double grad_scale, const int64_t* seg_end_dev,
+                               const uint8_t* seg_flags_dev, const int64_t* seg_end_host, int32_t nseg, void* stream);
+int loans_momentum_sgd_max_segments(void);
+
+/* A table of streaming jobs over float ranges in ONE launch: the exponential moving average of a model's weights
+ * (loans_amd/runtime/average.py) -- job 0 the whole parameter arena, the others the ~100 small BN statistics tensors.
+ *   LOANS_AVG_UPDATE:  dst += omd * (src - dst)      (omd = 1 - decay; exactly nothing where dst == src)
+ *   LOANS_AVG_SWAP:    dst <-> src, bit for bit
+ * Work is cut into units of LOANS_AVG_UNIT floats: first_unit = the sum of ceil(n / LOANS_AVG_UNIT) over the jobs before it, `units`
+ * that sum over all jobs; n need not be a multiple of 4.  dst is streamed (non-temporal), src stays cacheable.  jobs_dev: the table
+ * in DEVICE memory (caller-owned, alive until the launch has run); jobs_host: the same table in host memory, checked on every call
+ * -- LOANS_EINVAL, and no launch, for a null or not 16-byte aligned dst / src, n <= 0, a first_unit or `units` that is not the sum
+ * above, njobs <= 0, a null table or an unknown mode.  Ranges must not overlap. */
+#define LOANS_AVG_UNIT 4096
+#define LOANS_AVG_UPDATE 0
+#define LOANS_AVG_SWAP 1
+typedef struct loans_avg_job {
+    void* dst;
+    void* src;
+    int64_t n;
+    int64_t first_unit;
+} loans_avg_job;
+int loans_average_jobs_f32(const loans_avg_job* jobs_dev, const loans_avg_job* jobs_host, int32_t njobs, int64_t units, int32_t mode,
+                           float omd, void* stream);
+
 /* ---- input contract on the GPU (common/datasets/image_dataset.py:16-28 `resize_image` -> Pillow
  *      Image.resize(LANCZOS); :98 `image / 255`).  Bit-exact restatement of Pillow's 8-bit two-pass resampler
  *      (libImaging/Resample.c): per output coordinate a window bounds[2*i] = first input index, bounds[2*i+1] = taps, and

@@ -47,6 +47,14 @@ class PwPackJob(C.Structure):
     _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p)] + [(n, C.c_int32) for n in ('Cout', 'Cin', 'first_unit', 'reserved')]
 
 
+class AvgJob(C.Structure):
+    """Mirror of ``loans_avg_job``."""
+    _fields_ = [('dst', C.c_void_p), ('src', C.c_void_p), ('n', C.c_int64), ('first_unit', C.c_int64)]
+
+
+AVG_UNIT, AVG_UPDATE, AVG_SWAP = 4096, 0, 1
+
+
 class SmallConv(C.Structure):
     """Mirror of ``loans_small_conv``."""
     _fields_ = [(n, C.c_int32) for n in ('k', 'stride', 'pad', 'outH', 'outW')]
@@ -172,10 +180,13 @@ SIGNATURES = {
     'loans_adam_amsgrad_devlr_f32': [_p, _p, _p, _p, _p, _i64, _p, _f64, _f64, _f64, _f64, _f64, _f64, _p],
     'loans_adam_f32': [_p, _p, _p, _p, _i64, _f64, _p, _f64, _f64, _f64, _f64, _f64, _f64, _p],
     'loans_momentum_sgd_f32': [_p, _p, _p, _i64, _f64, _p, _f64, _f64, _f64, _p],
+    'loans_momentum_sgd_seg_f32': [_p, _p, _p, _i64, _f64, _p, _f64, _f64, _f64, _p, _p, _p, _i32, _p],
+    'loans_momentum_sgd_max_segments': [],
+    'loans_average_jobs_f32': [_p, _p, _i32, _i64, _i32, _f32, _p],
 }
 
 # every entry point returns int (0 / LOANS_E* / hipError_t) except:
-RESTYPES = {'loans_wgrad_bf16s_ws_floats': C.c_int64, 'loans_crop_band_rows': C.c_int}      # (sizes / counts, not a status)
+RESTYPES = {'loans_wgrad_bf16s_ws_floats': C.c_int64, 'loans_crop_band_rows': C.c_int, 'loans_momentum_sgd_max_segments': C.c_int}      # (sizes / counts, not a status)
 
 _lib = None
 

@@ -1,5 +1,6 @@
 // Small kernels around the conv stacks: preprocessing, GAP, Linear heads, rotation-dropout
-// multiply, spatial transformer (grid + bilinear sampler), losses, the fused Adam-AMSGrad and momentum SGD.
+// multiply, spatial transformer (grid + bilinear sampler), losses, the fused Adam-AMSGrad and momentum SGD (plain and with
+// per-segment weight decay), the job-table streaming kernel of the weight average.
 // None of them is GEMM-shaped; they are coalesced streaming / wave-shuffle reduction kernels.
 #include "common.h"
 
@@ -503,6 +504,134 @@ __global__ __launch_bounds__(256) void momentum_sgd_kernel(float* p, const float
     }
 }
 
+// ---- momentum SGD with per-segment weight decay ---------------------------------------------------------------------------------
+// momentum_sgd_kernel with h.wd replaced by 0 inside the segments whose flag has bit 0 set (BN gamma / beta, biases).  The table --
+// exclusive ends, ascending, every end but the last a multiple of 4, so that no float4 straddles a boundary -- is copied into LDS once
+// per block; a thread bisects it once for its first float4 and from there carries a cursor along the grid-stride loop: the indices
+// only grow, so the cursor only moves forward -- at most SGD_MAX_SEGMENTS LDS reads per thread over the whole launch, none of them
+// on the path of the loads: a trip's loads are issued before the lookup of the trip in front of it is used.
+constexpr int SGD_MAX_SEGMENTS = 1024;      // 8 KB of ends + 1 KB of flags in LDS
+
+__global__ __launch_bounds__(256) void momentum_sgd_seg_kernel(float* p, const float* g, float* v, int64_t n, SgdHyper h,
+                                                               const float* lr_dev, const int64_t* __restrict__ seg_end,
+                                                               const uint8_t* __restrict__ seg_flags, int nseg) {
+    __shared__ int64_t ends[SGD_MAX_SEGMENTS];
+    __shared__ uint8_t flags[SGD_MAX_SEGMENTS];
+    const int64_t n4 = n >> 2, stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    // the first trip's loads go out BEFORE the table is fetched: the grid is one wave of blocks, so a prologue of a global load, a
+    // barrier and a bisection in front of every block's first load is time the plain kernel does not spend (1.3 us of 79 at the
+    // ResNet-50 arena, profiles/imagenet_ema.txt)
+    f32x4 pp = {0.f, 0.f, 0.f, 0.f}, gg = pp, vv = pp;
+    if (i < n4) { pp = ld4(p + i * 4); gg = ldnt4(g + i * 4); vv = ldnt4(v + i * 4); }
+    for (int s = threadIdx.x; s < nseg; s += 256) { ends[s] = seg_end[s]; flags[s] = seg_flags[s]; }
+    if (lr_dev) h.lr = *lr_dev;
+    __syncthreads();
+    const float wd = h.wd;
+    int seg = 0;
+    if (i < n4) {           // the first segment whose end lies behind float i * 4
+        int lo = 0, hi = nseg - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (ends[mid] > i * 4) hi = mid; else lo = mid + 1;
+        }
+        seg = lo;
+    }
+    while (i < n4) {
+        while (seg < nseg - 1 && ends[seg] <= i * 4) ++seg;         // (the last end is n > i * 4)
+        h.wd = (flags[seg] & 1) ? 0.f : wd;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float a = pp[e], b = vv[e];
+            sgd1(a, gg[e], b, h);
+            pp[e] = a; vv[e] = b;
+        }
+        st4(p + i * 4, pp); stnt4(v + i * 4, vv);
+        i += stride;
+        if (i < n4) { pp = ld4(p + i * 4); gg = ldnt4(g + i * 4); vv = ldnt4(v + i * 4); }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {         // the last segment's ragged end
+        const int64_t t = n4 * 4 + threadIdx.x;
+        h.wd = (flags[nseg - 1] & 1) ? 0.f : wd;
+        sgd1(p[t], g[t], v[t], h);
+    }
+}
+
+// ---- weight average: a table of (dst, src, n) jobs in one launch ------------------------------------------------------------------
+// Work is cut into units of AVG_UNIT floats; unit u belongs to the job with the largest first_unit <= u (bisection over the table: u
+// is the same for the whole block, so the table is read with scalar loads).  A full unit is four float4 per thread, all loads issued
+// before the first store; a job's last, short unit takes float4 while they fit and single floats for the remaining n & 3.
+// dst (the average) is read once and written once per step: non-temporal, like adam_kernel's moments.  src (the live parameters)
+// stays cacheable in UPDATE: the next step's bf16 cast and re-packs read it.
+constexpr int AVG_UNIT = LOANS_AVG_UNIT;
+
+__device__ __forceinline__ void avg_update4(float* d, const float* s, float omd) {
+    f32x4 dd = ldnt4(d);
+    const f32x4 ss = ld4(s);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) dd[e] += omd * (ss[e] - dd[e]);
+    stnt4(d, dd);
+}
+
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void avg_swap4(float* d, float* s) {     // integer lanes: no bit of a NaN or a denormal is touched
+    const u32x4_t dd = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(d));
+    const u32x4_t ss = *reinterpret_cast<const u32x4_t*>(s);
+    __builtin_nontemporal_store(ss, reinterpret_cast<u32x4_t*>(d));
+    *reinterpret_cast<u32x4_t*>(s) = dd;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void average_jobs_kernel(const loans_avg_job* __restrict__ jobs, int njobs, int64_t units, float omd) {
+    for (int64_t u = blockIdx.x; u < units; u += gridDim.x) {
+        int lo = 0, hi = njobs - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (jobs[mid].first_unit <= u) lo = mid; else hi = mid - 1;
+        }
+        const loans_avg_job j = jobs[lo];
+        const int64_t off = (u - j.first_unit) * AVG_UNIT;
+        const int64_t left = j.n - off;
+        if (left <= 0) continue;            // (a table whose first_unit leaves a gap: nothing to do)
+        float* d = static_cast<float*>(j.dst) + off;
+        float* s = static_cast<float*>(j.src) + off;
+        if (left >= AVG_UNIT) {
+            if (MODE == LOANS_AVG_UPDATE) {
+                f32x4 dd[4], ss[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { dd[k] = ldnt4(d + (k * 256 + threadIdx.x) * 4); ss[k] = ld4(s + (k * 256 + threadIdx.x) * 4); }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dd[k][e] += omd * (ss[k][e] - dd[k][e]);
+                    stnt4(d + (k * 256 + threadIdx.x) * 4, dd[k]);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) avg_swap4(d + (k * 256 + threadIdx.x) * 4, s + (k * 256 + threadIdx.x) * 4);
+            }
+        } else {
+            const int m = (int)left, m4 = m & ~3;
+            for (int k = threadIdx.x * 4; k < m4; k += 1024) {
+                if (MODE == LOANS_AVG_UPDATE) avg_update4(d + k, s + k, omd); else avg_swap4(d + k, s + k);
+            }
+            if ((int)threadIdx.x < (m & 3)) {
+                const int k = m4 + threadIdx.x;
+                if (MODE == LOANS_AVG_UPDATE) {
+                    d[k] += omd * (s[k] - d[k]);
+                } else {
+                    uint32_t* di = reinterpret_cast<uint32_t*>(d) + k;
+                    uint32_t* si = reinterpret_cast<uint32_t*>(s) + k;
+                    const uint32_t t = *di;
+                    *di = *si;
+                    *si = t;
+                }
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int loans_prep_images_f32(const float* images_nchw, float* out_nhwc4, int32_t B, int32_t H, int32_t W, void* stream) {
@@ -754,6 +883,50 @@ extern "C" int loans_momentum_sgd_f32(float* p, const float* g, float* v, int64_
     SgdHyper h;
     h.lr = (float)lr; h.momentum = (float)momentum; h.wd = (float)weight_decay_rate; h.gscale = (float)grad_scale;
     hipLaunchKernelGGL(momentum_sgd_kernel, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, as_stream(stream), p, g, v, n, h, lr_dev);
+    LOANS_LAUNCH_CHECK();
+    return LOANS_OK;
+}
+
+extern "C" int loans_momentum_sgd_seg_f32(float* p, const float* g, float* v, int64_t n, double lr, const float* lr_dev, double momentum,
+                                          double weight_decay_rate, double grad_scale, const int64_t* seg_end_dev,
+                                          const uint8_t* seg_flags_dev, const int64_t* seg_end_host, int32_t nseg, void* stream) {
+    if (!p || !g || !v || n <= 0 || !seg_end_dev || !seg_flags_dev || !seg_end_host) return LOANS_EINVAL;
+    if (nseg <= 0 || nseg > SGD_MAX_SEGMENTS) return LOANS_EINVAL;
+    if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)v) & 15) || ((uintptr_t)seg_end_dev & 7)) return LOANS_EINVAL;
+    int64_t prev = 0;
+    for (int s = 0; s < nseg; ++s) {        // ascending, no empty segment, float4-aligned boundaries, the last one at n
+        const int64_t e = seg_end_host[s];
+        if (e <= prev || (s < nseg - 1 && (e & 3))) return LOANS_EINVAL;
+        prev = e;
+    }
+    if (prev != n) return LOANS_EINVAL;
+    SgdHyper h;
+    h.lr = (float)lr; h.momentum = (float)momentum; h.wd = (float)weight_decay_rate; h.gscale = (float)grad_scale;
+    hipLaunchKernelGGL(momentum_sgd_seg_kernel, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, as_stream(stream), p, g, v, n, h, lr_dev,
+                       seg_end_dev, seg_flags_dev, nseg);
+    LOANS_LAUNCH_CHECK();
+    return LOANS_OK;
+}
+
+extern "C" int loans_momentum_sgd_max_segments(void) { return SGD_MAX_SEGMENTS; }
+
+extern "C" int loans_average_jobs_f32(const loans_avg_job* jobs_dev, const loans_avg_job* jobs_host, int32_t njobs, int64_t units,
+                                      int32_t mode, float omd, void* stream) {
+    if (!jobs_dev || !jobs_host || njobs <= 0 || ((uintptr_t)jobs_dev & 7)) return LOANS_EINVAL;
+    if (mode != LOANS_AVG_UPDATE && mode != LOANS_AVG_SWAP) return LOANS_EINVAL;
+    int64_t unit = 0;
+    for (int j = 0; j < njobs; ++j) {
+        const loans_avg_job& job = jobs_host[j];
+        if (!job.dst || !job.src || (((uintptr_t)job.dst | (uintptr_t)job.src) & 15)) return LOANS_EINVAL;
+        if (job.n <= 0 || job.first_unit != unit) return LOANS_EINVAL;
+        unit += (job.n + AVG_UNIT - 1) / AVG_UNIT;
+    }
+    if (units != unit) return LOANS_EINVAL;
+    const int grid = grid_for(units, 1);
+    if (mode == LOANS_AVG_UPDATE)
+        hipLaunchKernelGGL(average_jobs_kernel<LOANS_AVG_UPDATE>, dim3(grid), dim3(256), 0, as_stream(stream), jobs_dev, njobs, units, omd);
+    else
+        hipLaunchKernelGGL(average_jobs_kernel<LOANS_AVG_SWAP>, dim3(grid), dim3(256), 0, as_stream(stream), jobs_dev, njobs, units, omd);
     LOANS_LAUNCH_CHECK();
     return LOANS_OK;
 }

@@ -2708,3 +2708,86 @@ def momentum_sgd(p, g, v, lr, momentum, weight_decay_rate, grad_scale=1.0):
         assert lr.dtype == torch.float32 and lr.numel() == 1 and lr.is_cuda
     check(_lib.load().loans_momentum_sgd_f32(_ptr(p), _ptr(g), _ptr(v), p.numel(), 0.0 if dev_lr else lr, _ptr(lr) if dev_lr else 0,
                                              momentum, weight_decay_rate, grad_scale, _stream()), 'loans_momentum_sgd_f32')
+
+
+SGD_MAX_SEGMENTS = 1024     # loans_momentum_sgd_max_segments(): the segment table of loans_momentum_sgd_seg_f32 lives in LDS
+
+
+class SegmentTable:
+    """The decay segments of ``momentum_sgd_seg`` on the device and, for the entry's checks, on the host: ``ends`` exclusive,
+    ascending, every one but the last a multiple of 4; ``flags`` one byte each, bit 0 = exempt from weight decay.  Uploaded once."""
+
+    def __init__(self, ends, flags, device):
+        self.ends_host = np.ascontiguousarray(ends, dtype=np.int64)
+        self.flags_host = np.ascontiguousarray(flags, dtype=np.uint8)
+        if self.ends_host.ndim != 1 or self.ends_host.shape != self.flags_host.shape:
+            raise ValueError('a segment table is one end and one flag byte per segment')
+        self.ends = torch.from_numpy(self.ends_host).to(device)
+        self.flags = torch.from_numpy(self.flags_host).to(device)
+
+    def __len__(self):
+        return len(self.ends_host)
+
+    def prefix(self, n):
+        """the table of the first ``n`` floats -- ``n`` a segment end, or a multiple of 8 inside a segment (the arena's cold
+        offsets are both) --, sharing this table's device memory: the segments in front of ``n``, the one it cuts ending at it"""
+        if n == int(self.ends_host[-1]):
+            return self
+        k = int(np.searchsorted(self.ends_host, n, side='left')) + 1
+        cut = SegmentTable.__new__(SegmentTable)
+        cut.ends_host, cut.flags_host = self.ends_host[:k].copy(), self.flags_host[:k]
+        cut.ends_host[-1] = n
+        cut.flags = self.flags[:k]
+        cut.ends = self.ends[:k] if int(self.ends_host[k - 1]) == n else torch.from_numpy(cut.ends_host).to(self.ends.device)
+        return cut
+
+
+def momentum_sgd_seg(p, g, v, lr, momentum, weight_decay_rate, table, grad_scale=1.0):
+    """``momentum_sgd`` with ``weight_decay_rate`` counted as 0 inside the segments of ``table`` (a ``SegmentTable`` over exactly
+    ``p.numel()`` floats) whose flag says so."""
+    if CLASS_COUNT is not None: _acct('optimizer', 0, _nbytes(p, g, v), _nbytes(p, v))
+    dev_lr = torch.is_tensor(lr)
+    if dev_lr:
+        assert lr.dtype == torch.float32 and lr.numel() == 1 and lr.is_cuda
+    check(_lib.load().loans_momentum_sgd_seg_f32(_ptr(p), _ptr(g), _ptr(v), p.numel(), 0.0 if dev_lr else lr, _ptr(lr) if dev_lr else 0,
+                                                 momentum, weight_decay_rate, grad_scale, _ptr(table.ends), _ptr(table.flags),
+                                                 table.ends_host.ctypes.data, len(table), _stream()), 'loans_momentum_sgd_seg_f32')
+
+
+class AverageJobs:
+    """The job table of ``average_jobs``: pairs of float32 device tensors ``(dst, src)`` of equal size, kept alive here; the
+    table is built and uploaded once."""
+
+    def __init__(self, pairs):
+        pairs = list(pairs)
+        if not pairs:
+            raise ValueError('an average needs at least one (dst, src) pair')
+        self.pairs = pairs
+        self.host = (_lib.AvgJob * len(pairs))()
+        unit = 0
+        for i, (dst, src) in enumerate(pairs):
+            _chk(dst, 'dst'); _chk(src, 'src')
+            if dst.numel() != src.numel() or dst.device != src.device:
+                raise ValueError('dst and src of job %d differ in size or device' % i)
+            self.host[i].dst, self.host[i].src, self.host[i].n, self.host[i].first_unit = dst.data_ptr(), src.data_ptr(), dst.numel(), unit
+            unit += (dst.numel() + _lib.AVG_UNIT - 1) // _lib.AVG_UNIT
+        self.units, self.njobs = unit, len(pairs)
+        self.dev = torch.from_numpy(np.frombuffer(bytes(self.host), dtype=np.uint8).copy()).to(pairs[0][0].device)
+
+
+def average_jobs(jobs, mode, omd=0.0):
+    """one launch over every job of ``jobs`` (``AverageJobs``): ``mode`` 'update' -- dst += omd * (src - dst) -- or 'swap'"""
+    if CLASS_COUNT is not None:
+        n = sum(_nbytes(d) for d, _ in jobs.pairs)
+        _acct('optimizer', 0, 2 * n, n if mode == 'update' else 2 * n)
+    check(_lib.load().loans_average_jobs_f32(_ptr(jobs.dev), C.addressof(jobs.host), jobs.njobs, jobs.units,
+                                             {'update': _lib.AVG_UPDATE, 'swap': _lib.AVG_SWAP}[mode], omd, _stream()),
+          'loans_average_jobs_f32')
+
+
+def in_step(device):
+    """whether a training step is live on ``device``: between ``begin_step`` and ``end_step`` derived weight buffers (bf16 shadow,
+    fragment-order packs, data-gradient re-packs) are trusted, so the masters must not change under them"""
+    idx = device.index if isinstance(device, torch.device) else device
+    wp = _weight_preps.get(idx)
+    return wp is not None and wp.live

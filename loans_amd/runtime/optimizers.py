@@ -287,15 +287,60 @@ class Adam(GradientMethod):
                          hp.eps, hp.eta, hp.weight_decay_rate, grad_scale)
 
 
+def decay_segments(sizes, offsets, exempt, numel):
+    """The segment table of ``ops.momentum_sgd_seg`` for parameters of ``sizes`` floats at ``offsets`` of a flat buffer of
+    ``numel`` floats (ascending, every offset a multiple of 4, the first one 0; ``ParamArena`` pads to 8), ``exempt[i]`` true where
+    parameter i takes no weight decay: ``(ends, flags)`` -- exclusive ends as int64 and one flag byte per segment, bit 0 = exempt.
+    A parameter's segment runs to the next parameter's offset (the padding behind it is zero and has a zero gradient: it does not
+    move either way), the last one to ``numel``; neighbours with equal flags are one segment.  A pure function of its arguments."""
+    sizes, offsets = [int(s) for s in sizes], [int(o) for o in offsets]
+    if not sizes or len(sizes) != len(offsets) or len(sizes) != len(exempt):
+        raise ValueError('one size, one offset and one flag per parameter, and at least one parameter')
+    if offsets[0] != 0:
+        raise ValueError('the first parameter starts at offset %d, not 0' % offsets[0])
+    stops = offsets[1:] + [int(numel)]
+    ends, flags = [], []
+    for size, start, stop, flag in zip(sizes, offsets, stops, exempt):
+        if start % 4 or size <= 0 or start + size > stop:
+            raise ValueError('a parameter of %d floats at offset %d does not fit in front of %d on a float4 boundary' % (size, start, stop))
+        if flags and flags[-1] == int(bool(flag)):
+            ends[-1] = stop
+        else:
+            ends.append(stop)
+            flags.append(int(bool(flag)))
+    return np.asarray(ends, np.int64), np.asarray(flags, np.uint8)
+
+
 class MomentumSGD(GradientMethod):
     """``chainer.optimizers.MomentumSGD(lr, momentum)`` with ``chainer.optimizer.WeightDecay(weight_decay_rate)`` applied to the
     gradient first: ``g' = g + rate * p; v = momentum * v - lr * g'; p += v``.  State: one ``v`` the size of the arena.  The
     prefix rule of the module docstring holds as it stands: v = 0 and g = 0 make the step of a never-used parameter a no-op,
-    and a parameter that was stepped before keeps moving by its decaying ``v``."""
+    and a parameter that was stepped before keeps moving by its decaying ``v``.
 
-    def __init__(self, lr=0.01, momentum=0.9, weight_decay_rate=0.0):
+    ``decay_exempt_1d=True``: parameters whose Chainer shape has at most one dimension -- BN ``gamma`` / ``beta``, biases -- take
+    no weight decay (``decay_segments`` over the arena, ``ops.momentum_sgd_seg``: still one launch)."""
+
+    def __init__(self, lr=0.01, momentum=0.9, weight_decay_rate=0.0, decay_exempt_1d=False):
         super().__init__()
-        self.hyperparam = SimpleNamespace(lr=lr, momentum=momentum, weight_decay_rate=weight_decay_rate)
+        self.hyperparam = SimpleNamespace(lr=lr, momentum=momentum, weight_decay_rate=weight_decay_rate,
+                                          decay_exempt_1d=bool(decay_exempt_1d))
+        self._segments, self._segment_cuts = None, {}
+
+    def _segment_table(self, arena, n):
+        """the decay segments of the first ``n`` floats of ``arena``: the arena's table is built and uploaded once, and cut once
+        per stepped prefix -- that ends at a cold link's offset, so there are at most a few"""
+        if self._segments is None or self._segments[0] is not arena:
+            if arena.data.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('the decay segment table is uploaded once, outside a captured step: step once before capturing')
+            ends, flags = decay_segments([p.size for p in arena.params], arena.offsets,
+                                         [len(p.logical_shape) <= 1 for p in arena.params], arena.numel)
+            if len(ends) > ops.SGD_MAX_SEGMENTS:
+                raise ValueError('%d decay segments: the kernel takes %d' % (len(ends), ops.SGD_MAX_SEGMENTS))
+            self._segments, self._segment_cuts = (arena, ops.SegmentTable(ends, flags, arena.device)), {}
+        table = self._segment_cuts.get(n)
+        if table is None:
+            table = self._segment_cuts[n] = self._segments[1].prefix(n)
+        return table
 
     @property
     def lr(self):
@@ -313,4 +358,8 @@ class MomentumSGD(GradientMethod):
 
     def _step(self, arena, n, state, lr, grad_scale):
         hp = self.hyperparam
+        if getattr(hp, 'decay_exempt_1d', False):
+            ops.momentum_sgd_seg(arena.data[:n], arena.grad[:n], state[0][:n], lr, hp.momentum, hp.weight_decay_rate,
+                                 self._segment_table(arena, n), grad_scale)
+            return
         ops.momentum_sgd(arena.data[:n], arena.grad[:n], state[0][:n], lr, hp.momentum, hp.weight_decay_rate, grad_scale)

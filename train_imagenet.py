@@ -63,6 +63,20 @@ validation entries are the plain loss on unmixed frames.  A batch that is not mi
     python train_imagenet.py train.tsv val.tsv -b 256 --optimizer sgd --lr 0.1 --augment rrc --label-smoothing 0.1 \
         --mixup-alpha 0.2 --cutmix-alpha 1.0
 
+``--ema-decay D`` (default 0: off) keeps an exponential moving average of the weights and the BN statistics
+(loans_amd/runtime/average.py, ``WeightAverage``: one launch per step behind the optimiser's; update t uses the decay
+``min(D, (1 + t) / (10 + t))``).  When validation runs it runs twice -- the live model first, as always, then the averaged one, whose
+entries are ``validation/ema/loss``, ``validation/ema/accuracy`` and ``validation/ema/accuracy_top<k>`` -- and beside every
+``<LocalizerClass>_<it>.npz`` the averaged model is written as ``<LocalizerClass>_ema_<it>.npz`` with the same keys: the model to
+hand to ``train_sheep_localizer.py --rl`` after a long run.  The average is part of the checkpoints; a checkpoint written without
+the option is not resumed with it, nor the reverse.  ``--lr-schedule cosine`` (default ``step``) takes the rate from ``--lr`` at the
+end of the warm-up down half a cosine to ``--lr-min`` (default 0) at ``--num-epoch``; ``--lr-drop-epochs`` belongs to ``step``.
+``--no-decay-1d`` (with ``--optimizer sgd``) exempts BN scales / shifts and biases from ``--weight-decay``.  The schedule and the
+exemption may change on resume, like ``--weight-decay``.
+
+    python train_imagenet.py train.tsv val.tsv -b 256 --optimizer sgd --lr 0.1 --weight-decay 5e-5 --no-decay-1d \
+        --lr-schedule cosine --lr-min 1e-5 --warmup-epochs 5 --num-epoch 300 --ema-decay 0.9999
+
 ``--checkpoint-interval N`` writes a full-state checkpoint, ``checkpoint_<iteration>.npz`` in the log directory, after every
 N-th iteration and after the last one (default 0: none; ``--checkpoint-keep K``, default 2, keeps the newest K): the model with
 its BN statistics, the optimiser's buffers and step count, the training iterator as of the batch the step consumed (shuffle
@@ -72,10 +86,10 @@ stream, order, position, the crop / mirror draw stream and the mix draw stream),
 its log directory: the ``log`` file is read back and appended to, ``elapsed_time`` and the snapshot names count on.  Fixed on
 resume (one error lists every one that differs): the architecture, ``--dtype``, ``--optimizer``, ``-b``, ``--gpus``,
 ``--image-size``, the dataset files or the synthetic sizes, classes and ``--data-seed``, ``--no-shuffle``, ``--augment`` /
-``--rrc-*`` / ``--val-crop-pct`` / ``--augment-seed``, ``--mixup-alpha`` / ``--cutmix-alpha`` / ``--mix-*`` (a checkpoint from
+``--rrc-*`` / ``--val-crop-pct`` / ``--augment-seed``, ``--mixup-alpha`` / ``--cutmix-alpha`` / ``--mix-*``, ``--ema-decay`` (a checkpoint from
 before these options existed ran at their defaults), ``--seed``.  Taken from the new command line (each one that differs is
 printed once): ``--num-epoch``, ``--iterations``, the log, snapshot and checkpoint intervals, ``--loader-threads``, the frame
-cache options, ``--lr``, ``--weight-decay``, ``--momentum``, ``--lr-drop-*``, ``--warmup-*``, ``--label-smoothing``, ``--topk``.  The
+cache options, ``--lr``, ``--weight-decay``, ``--momentum``, ``--lr-drop-*``, ``--lr-schedule``, ``--lr-min``, ``--no-decay-1d``, ``--warmup-*``, ``--label-smoothing``, ``--topk``.  The
 frame caches start empty after a resume and refill during the first epoch.
 
     python train_imagenet.py train.tsv val.tsv -b 256 --optimizer sgd --lr 0.1 --lr-drop-epochs 30 60 90 --checkpoint-interval 500
@@ -99,6 +113,7 @@ if __name__ == "__main__":
 import argparse             # noqa: E402
 import datetime             # noqa: E402
 import json                 # noqa: E402
+import math                 # noqa: E402
 import time                 # noqa: E402
 
 import numpy as np          # noqa: E402
@@ -114,7 +129,7 @@ SYNTHETIC = 'synthetic'
 # what --resume holds against the checkpoint's arguments: everything the data sequence and the model's shape depend on
 RESUME_FIXED = ('use_resnet_18', 'dtype', 'optimizer', 'batch_size', 'gpus', 'image_size', 'train_file', 'val_file', 'dataset_size',
                 'validation_size', 'synthetic_classes', 'data_seed', 'no_shuffle', 'augment', 'rrc_scale', 'rrc_ratio', 'val_crop_pct',
-                'augment_seed', 'seed', 'mixup_alpha', 'cutmix_alpha', 'mix_prob', 'mix_switch_prob', 'mix_seed')
+                'augment_seed', 'seed', 'mixup_alpha', 'cutmix_alpha', 'mix_prob', 'mix_switch_prob', 'mix_seed', 'ema_decay')
 
 
 class SyntheticClasses:
@@ -167,7 +182,14 @@ class Arguments(argparse.Namespace):
     _PIPELINE = ('augment', 'rrc_scale', 'rrc_ratio', 'val_crop_pct', 'augment_seed')
     _PARALLEL = ('gpus', 'warmup_epochs', 'warmup_start_factor', 'validation_sums')
     _CACHE = ('frame_cache_gb', 'frame_cache_where')
+    # weight average, cosine rate, decay-free 1-d parameters (loans_amd/runtime/average.py, optimizers.py); all off by default
+    ema_decay = 0.0
+    lr_schedule = 'step'
+    lr_min = 0.0
+    no_decay_1d = False
+
     _MIX = ('mixup_alpha', 'cutmix_alpha', 'mix_prob', 'mix_switch_prob', 'mix_seed')
+    _AVERAGE = ('ema_decay', 'lr_schedule', 'lr_min', 'no_decay_1d')
 
 
 def parse_args(argv=None):
@@ -223,14 +245,21 @@ def parse_args(argv=None):
     parser.add_argument("--mix-prob", type=float, default=argparse.SUPPRESS, help="probability that a batch is mixed at all (default 1)")
     parser.add_argument("--mix-switch-prob", type=float, default=argparse.SUPPRESS, help="with both alphas: probability that a mixed batch takes CutMix, not mixup (default 0.5)")
     parser.add_argument("--mix-seed", type=int, default=argparse.SUPPRESS, help="seed of the mix draws (a stream of their own)")
+    # weight average, cosine rate, decay-free 1-d parameters
+    parser.add_argument("--ema-decay", type=float, default=argparse.SUPPRESS, help="keep an exponential moving average of the weights with this decay (warmed up as (1 + t) / (10 + t)); validated and snapshotted beside the live model (default 0: off)")
+    parser.add_argument("--lr-schedule", default=argparse.SUPPRESS, choices=['step', 'cosine'], help="step: --lr-drop-epochs; cosine: half a cosine from --lr down to --lr-min over --num-epoch, behind the warm-up (default step)")
+    parser.add_argument("--lr-min", type=float, default=argparse.SUPPRESS, help="the rate --lr-schedule cosine ends at (default 0)")
+    parser.add_argument("--no-decay-1d", action='store_true', default=argparse.SUPPRESS, help="with --optimizer sgd: no weight decay on BN scales / shifts and on biases")
     checkpoint.add_arguments(parser, argparse.SUPPRESS)
     args = parser.parse_args(argv, namespace=Arguments())
     try:
         check_cache_arguments(args)
         check_mix_arguments(args)
+        check_average_arguments(args)
         if args.resume is not None:
+            check_average_resume(args)
             world = os.environ.get('WORLD_SIZE')        # a rank under a launcher: the group's size, whatever --gpus says
-            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS)
+            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=ALL_RESUME_DEFAULTS)
     except ValueError as e:
         parser.error(str(e))
     return args
@@ -259,8 +288,34 @@ def check_mix_arguments(args):
         raise ValueError('--mixup-alpha / --cutmix-alpha mix the batches the GPU crops: they need --augment rrc')
 
 
+def check_average_arguments(args):
+    """ValueError for an --ema-decay that is no decay, and for options that contradict each other"""
+    if not 0.0 <= args.ema_decay < 1.0:
+        raise ValueError('--ema-decay is a decay: it must lie in [0, 1), got %r' % args.ema_decay)
+    if args.lr_schedule == 'cosine' and len(args.lr_drop_epochs) > 0:
+        raise ValueError('--lr-drop-epochs belongs to --lr-schedule step: the cosine rate has no steps')
+    if args.lr_min < 0:
+        raise ValueError('--lr-min must not be negative, got %r' % args.lr_min)
+    if args.no_decay_1d and args.optimizer != 'sgd':
+        raise ValueError('--no-decay-1d is built for --optimizer sgd: Adam\'s kernel applies one weight decay to every parameter')
+
+
+AVERAGE_RESUME = {False: '--resume: the checkpoint was written without --ema-decay and holds no weight average: resume it without the option',
+                  True: '--resume: the checkpoint was written with --ema-decay %g and holds a weight average: resume it with the option'}
+
+
+def check_average_resume(args):
+    """ValueError, a sentence, where a run with a weight average is to continue a checkpoint without one, or the reverse"""
+    saved = float(checkpoint.read_meta(checkpoint.resolve(args.resume, log=lambda line: None))['args'].get('ema_decay', 0.0))
+    if (saved > 0) != (args.ema_decay > 0):
+        raise ValueError(AVERAGE_RESUME[True] % saved if saved > 0 else AVERAGE_RESUME[False])
+
+
 # what a checkpoint written before an option existed is taken to have run with: the option's default
 RESUME_DEFAULTS = {name: getattr(Arguments, name) for name in Arguments._MIX}
+# ... and the same for the weight average, the cosine rate and --no-decay-1d (a table of its own: RESUME_DEFAULTS is the mix options')
+RESUME_DEFAULTS_AVERAGE = {name: getattr(Arguments, name) for name in Arguments._AVERAGE}
+ALL_RESUME_DEFAULTS = dict(RESUME_DEFAULTS, **RESUME_DEFAULTS_AVERAGE)
 
 
 def cache_budgets(total_bytes, n_train, n_validation):
@@ -274,6 +329,15 @@ def scheduled_lr(base, epoch, drop_epochs, factor):
     """the stepped rate of ``epoch``: ``base`` times ``factor`` once per listed epoch that has begun -- a pure function, so a
     resumed run and a fresh one agree"""
     return base * factor ** sum(1 for e in set(drop_epochs) if e <= epoch)
+
+
+def cosine_lr(base, epoch_detail, num_epoch, warmup_epochs, lr_min):
+    """the cosine rate at ``epoch_detail`` (epochs done, fractional): ``base`` until the warm-up ends, then half a cosine down to
+    ``lr_min`` at ``num_epoch`` and ``lr_min`` from there on -- a pure function, like ``scheduled_lr``, whose place it takes;
+    ``warmup_factor`` multiplies it the same way"""
+    span = num_epoch - warmup_epochs
+    progress = min(max((epoch_detail - warmup_epochs) / span, 0.0), 1.0) if span > 0 else 1.0
+    return lr_min + (base - lr_min) * (1.0 + math.cos(math.pi * progress)) / 2.0
 
 
 def warmup_factor(epoch_detail, warmup_epochs, start_factor):
@@ -366,9 +430,12 @@ def run(args, log=print):
     torch.cuda.set_device(args.gpu)
     for name in Arguments._PIPELINE + Arguments._PARALLEL + Arguments._CACHE + Arguments._MIX:      # the values this run uses, logged with the other arguments
         setattr(args, name, getattr(args, name, getattr(Arguments, name)))
+    # the _AVERAGE options are logged where one of them is given: a run without them logs what it always logged
+    averaging = any(getattr(args, name) != getattr(Arguments, name) for name in Arguments._AVERAGE)
     args.gpus = comm.size
     check_cache_arguments(args)
     check_mix_arguments(args)
+    check_average_arguments(args)
     chief = comm.rank == 0                       # prints, logs and writes snapshots
 
     # --augment rrc: the iterators hand out (frames, labels) already resident on the device
@@ -417,7 +484,8 @@ def run(args, log=print):
     comm.bcast_data(model)
 
     if args.optimizer == 'sgd':
-        optimizer, rate_name = loans_amd.MomentumSGD(lr=args.learning_rate, momentum=args.momentum, weight_decay_rate=args.weight_decay), 'lr'
+        exempt = {'decay_exempt_1d': True} if args.no_decay_1d else {}
+        optimizer, rate_name = loans_amd.MomentumSGD(lr=args.learning_rate, momentum=args.momentum, weight_decay_rate=args.weight_decay, **exempt), 'lr'
     else:
         optimizer, rate_name = loans_amd.Adam(alpha=args.learning_rate, weight_decay_rate=args.weight_decay), 'alpha'
     optimizer.setup(model)
@@ -425,6 +493,8 @@ def run(args, log=print):
     topk = 'accuracy_top%d' % model.topk if model.topk is not None else None
     train_keys = ('loss', 'accuracy') + ((topk,) if topk else ())
     updater = training.StandardUpdater(train_iter, optimizer, converter=train_converter, device=args.gpu, comm=comm)
+    # every rank keeps its own average: the parameters agree on all ranks (built after bcast_data), the BN statistics are local
+    average = loans_amd.WeightAverage(model, args.ema_decay) if args.ema_decay > 0 else None
 
     evaluator = validate = None
     summed = comm.size > 1 or args.validation_sums
@@ -466,8 +536,9 @@ def run(args, log=print):
     resumed = None
     if args.resume is not None:
         # the run continues in the checkpoint's log directory: no new <time>_<name>
+        check_average_resume(args)
         resumed, changed = checkpoint.resolve_resume(args, RESUME_FIXED, log if chief else (lambda line: None), world=comm.size,
-                                                     defaults=RESUME_DEFAULTS)
+                                                     defaults=ALL_RESUME_DEFAULTS)
         args.log_dir = os.path.dirname(os.path.abspath(args.resume))
         for line in changed if chief else ():
             log(line)
@@ -481,12 +552,22 @@ def run(args, log=print):
     for argument in filter(lambda x: not x.startswith('_'), dir(args)):
         if argument in checkpoint.FLAGS and checkpoint.FLAGS[argument] == getattr(args, argument):
             continue        # a run without the checkpoint options logs what it always logged
+        if argument in Arguments._AVERAGE and not averaging:
+            continue
         data_to_log[argument] = getattr(args, argument)
     log_entries = []
     state = dict(models={'model': model}, optimizers={'main': optimizer}, iterators={'main': train_iter}, comm=comm)
+    if average is not None:
+        state['optimizers']['ema'] = average    # the shape of an optimiser's record: class, t, hyperparam, state
 
-    def snapshot_path(it):
-        return os.path.join(args.log_dir, '%s_%d.npz' % (localizer.__class__.__name__, it))
+    def snapshot_path(it, tag=''):
+        return os.path.join(args.log_dir, '%s_%s%d.npz' % (localizer.__class__.__name__, tag, it))
+
+    def save_snapshots(it):
+        loans_amd.save_npz(snapshot_path(it), localizer)
+        if average is not None:     # the same keys, the averaged values: train_sheep_localizer.py --rl takes it as it is
+            with average.applied():
+                loans_amd.save_npz(snapshot_path(it, 'ema_'), localizer)
 
     t0 = time.time()
     it = 0
@@ -495,6 +576,8 @@ def run(args, log=print):
         checkpoint.load_checkpoint(args.resume, **state)
         optimizer.hyperparam.weight_decay_rate = args.weight_decay      # the rates are the new command line's (--lr: set per step below)
         if args.optimizer == 'sgd':
+            optimizer.hyperparam.decay_exempt_1d = bool(args.no_decay_1d)
+        if args.optimizer == 'sgd':
             optimizer.hyperparam.momentum = args.momentum
         it = updater.iteration = int(resumed['iteration'])
         t0 -= float(resumed['elapsed_time'])
@@ -502,10 +585,15 @@ def run(args, log=print):
         if chief:
             log('resumed %s: iteration %d, epoch %d' % (args.resume, it, updater.epoch))
     while updater.epoch < args.num_epoch and (args.iterations is None or it < args.iterations):
-        lr = scheduled_lr(args.learning_rate, updater.epoch, args.lr_drop_epochs, args.lr_drop_factor) * \
-            warmup_factor(updater.epoch_detail, args.warmup_epochs, args.warmup_start_factor)
+        if args.lr_schedule == 'cosine':
+            lr = cosine_lr(args.learning_rate, updater.epoch_detail, args.num_epoch, args.warmup_epochs, args.lr_min)
+        else:
+            lr = scheduled_lr(args.learning_rate, updater.epoch, args.lr_drop_epochs, args.lr_drop_factor)
+        lr *= warmup_factor(updater.epoch_detail, args.warmup_epochs, args.warmup_start_factor)
         setattr(optimizer, rate_name, lr)
         updater.update()
+        if average is not None:
+            average.update()
         it = updater.iteration
         last = (args.iterations is not None and it == args.iterations) or updater.epoch >= args.num_epoch
         # LOCK STEP.  Everything below that holds a collective -- the mean of the training metrics, the validation pass -- and the
@@ -526,6 +614,11 @@ def run(args, log=print):
             if validate is not None:
                 keep = {k: obs[k] for k in train_keys}
                 entry.update({k: v for k, v in validate().items() if k.startswith('validation/')})
+                if average is not None:
+                    # the second pass: the same set through the averaged model (LOCK STEP: `average` depends on the arguments alone)
+                    with average.applied():
+                        entry.update({'validation/ema/' + k[len('validation/'):]: v for k, v in validate().items()
+                                      if k in ('validation/loss', 'validation/accuracy', 'validation/' + str(topk))})
                 loans_amd.report(keep)
             for prefix, tally in caches.items():
                 entry.update({prefix + 'frames': len(tally[0]), prefix + 'bytes': tally[0].bytes,
@@ -538,6 +631,10 @@ def run(args, log=print):
                 val = '  validation loss %.5f accuracy %.4f' % (entry['validation/loss'], entry['validation/accuracy'])
                 if topk:
                     val += top % entry['validation/' + topk]
+            if 'validation/ema/loss' in entry:
+                val += '  ema loss %.5f accuracy %.4f' % (entry['validation/ema/loss'], entry['validation/ema/accuracy'])
+                if topk:
+                    val += top % entry['validation/ema/' + topk]
             if chief:
                 log('iteration %4d  epoch %d  lr %g  loss %.5f  accuracy %.4f%s%s  (%.1f s)' % (
                     it, updater.epoch, lr, entry['loss'], entry['accuracy'], top % entry[topk] if topk else '', val, entry['elapsed_time']))
@@ -548,7 +645,7 @@ def run(args, log=print):
                 with open(os.path.join(args.log_dir, 'log'), 'w') as f:
                     json.dump(log_entries, f, indent=4, default=str)
         if chief and it % args.snapshot_interval == 0:
-            loans_amd.save_npz(snapshot_path(it), localizer)
+            save_snapshots(it)
         if checkpoint.due(it, args.checkpoint_interval, last):      # of `it` and the arguments alone: LOCK STEP holds (a barrier inside)
             checkpoint.save_checkpoint(args.log_dir, it, keep=args.checkpoint_keep, meta={
                 'epoch': updater.epoch, 'elapsed_time': time.time() - t0, 'args': checkpoint.plain_arguments(args)}, **state)
@@ -557,7 +654,7 @@ def run(args, log=print):
         validation_iter.finalize()
     if chief:
         if not os.path.exists(snapshot_path(updater.iteration)):
-            loans_amd.save_npz(snapshot_path(updater.iteration), localizer)
+            save_snapshots(updater.iteration)
         log('snapshot: %s' % snapshot_path(updater.iteration))
     return log_entries, model
 
