@@ -691,6 +691,39 @@ int loans_momentum_sgd_seg_f32(float* p, const float* g, float* v, int64_t n, do
                                const uint8_t* seg_flags_dev, const int64_t* seg_end_host, int32_t nseg, void* stream);
 int loans_momentum_sgd_max_segments(void);
 
+/* LARS (You et al. 2017): momentum SGD whose rate is scaled per segment of the flat buffer by a trust ratio.  The segment table is
+ * loans_momentum_sgd_seg_f32's (same rules, same checks, nseg <= LOANS_LARS_MAX_SEGMENTS) with a second flag bit:
+ *   W_s  = sqrt(sum p_i^2)      G_s = |grad_scale| * sqrt(sum g_i^2)                  over segment s
+ *   wd_s = (flags[s] & 1) ? 0 : weight_decay_rate
+ *   r_s  = (flags[s] & 2) ? 1 : (W_s > 0 && G_s > 0 ? eta * W_s / (G_s + wd_s * W_s + eps) : 1)
+ *   g' = g * grad_scale + wd_s * p;   v = momentum * v - (lr * r_s) * g';   p = p + v
+ *
+ * loans_lars_ratios_f32: one pass over p and g (two launches: per-unit partial sums of squares, then a per-segment fold) leaves
+ * r_s, rounded to fp32 once, in ratios_dev[0 .. nseg) and, if norms_dev != NULL, W_s and G_s in norms_dev[2 s], norms_dev[2 s + 1].
+ * Every square and every sum is fp64, the order of the additions is fixed and no atomic is used: the same inputs give the same
+ * bits.  Work is cut per segment into units of LOANS_LARS_UNIT floats; seg_first_unit_dev[s] = the sum of
+ * ceil(length / LOANS_LARS_UNIT) over the segments before s, in device memory like the ends and flags.  workspace: device
+ * memory, 16-byte aligned, of at least loans_lars_workspace_bytes(seg_end_host, nseg) bytes (-1 for a table that breaks a
+ * rule); it need not be initialised.  Nothing is synchronised with the host.
+ *
+ * loans_lars_update_f32: loans_momentum_sgd_seg_f32 with the rate of segment s = fl(fl(lr) * ratios_dev[s]) -- one fp32 product
+ * of the rate as the kernel holds it (the argument rounded to fp32, or *lr_dev) --, everything else loans_momentum_sgd_f32's
+ * arithmetic bit for bit.
+ *
+ * LOANS_EINVAL, and no launch: a null pointer (norms_dev may be null), p / g / v / workspace off a 16-byte boundary, n <= 0,
+ * nseg outside [1, LOANS_LARS_MAX_SEGMENTS], ends not ascending, an inner end that is no multiple of 4, a last end != n, a
+ * workspace that is too small, eta <= 0, eps < 0. */
+#define LOANS_LARS_UNIT 4096
+#define LOANS_LARS_MAX_SEGMENTS 1024
+int64_t loans_lars_workspace_bytes(const int64_t* seg_end_host, int32_t nseg);
+int loans_lars_ratios_f32(const float* p, const float* g, int64_t n, double weight_decay_rate, double grad_scale, double eta,
+                          double eps, const int64_t* seg_end_dev, const uint8_t* seg_flags_dev, const int64_t* seg_first_unit_dev,
+                          const int64_t* seg_end_host, int32_t nseg, float* ratios_dev, double* norms_dev, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+int loans_lars_update_f32(float* p, const float* g, float* v, int64_t n, double lr, const float* lr_dev, double momentum,
+                          double weight_decay_rate, double grad_scale, const int64_t* seg_end_dev, const uint8_t* seg_flags_dev,
+                          const float* ratios_dev, const int64_t* seg_end_host, int32_t nseg, void* stream);
+
 /* A table of streaming jobs over float ranges in ONE launch: the exponential moving average of a model's weights
  * (loans_amd/runtime/average.py) -- job 0 the whole parameter arena, the others the ~100 small BN statistics tensors.
  *   LOANS_AVG_UPDATE:  dst += omd * (src - dst)      (omd = 1 - decay; exactly nothing where dst == src)

@@ -53,6 +53,7 @@ class AvgJob(C.Structure):
 
 
 AVG_UNIT, AVG_UPDATE, AVG_SWAP = 4096, 0, 1
+LARS_UNIT, LARS_MAX_SEGMENTS = 4096, 1024      # LOANS_LARS_UNIT, LOANS_LARS_MAX_SEGMENTS
 
 
 class SmallConv(C.Structure):
@@ -182,11 +183,15 @@ SIGNATURES = {
     'loans_momentum_sgd_f32': [_p, _p, _p, _i64, _f64, _p, _f64, _f64, _f64, _p],
     'loans_momentum_sgd_seg_f32': [_p, _p, _p, _i64, _f64, _p, _f64, _f64, _f64, _p, _p, _p, _i32, _p],
     'loans_momentum_sgd_max_segments': [],
+    'loans_lars_workspace_bytes': [_p, _i32],
+    'loans_lars_ratios_f32': [_p, _p, _i64, _f64, _f64, _f64, _f64, _p, _p, _p, _p, _i32, _p, _p, _p, _i64, _p],
+    'loans_lars_update_f32': [_p, _p, _p, _i64, _f64, _p, _f64, _f64, _f64, _p, _p, _p, _p, _i32, _p],
     'loans_average_jobs_f32': [_p, _p, _i32, _i64, _i32, _f32, _p],
 }
 
 # every entry point returns int (0 / LOANS_E* / hipError_t) except:
-RESTYPES = {'loans_wgrad_bf16s_ws_floats': C.c_int64, 'loans_crop_band_rows': C.c_int, 'loans_momentum_sgd_max_segments': C.c_int}      # (sizes / counts, not a status)
+RESTYPES = {'loans_wgrad_bf16s_ws_floats': C.c_int64, 'loans_crop_band_rows': C.c_int, 'loans_momentum_sgd_max_segments': C.c_int,
+            'loans_lars_workspace_bytes': C.c_int64}      # (sizes / counts, not a status)
 
 _lib = None
 

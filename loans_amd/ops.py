@@ -2754,6 +2754,63 @@ def momentum_sgd_seg(p, g, v, lr, momentum, weight_decay_rate, table, grad_scale
                                                  table.ends_host.ctypes.data, len(table), _stream()), 'loans_momentum_sgd_seg_f32')
 
 
+LARS_UNIT, LARS_MAX_SEGMENTS = _lib.LARS_UNIT, _lib.LARS_MAX_SEGMENTS
+
+
+def lars_first_units(ends):
+    """first unit of every segment and the number of units: a segment of L floats is ceil(L / LARS_UNIT) units of ``lars_ratios``"""
+    ends = np.asarray(ends, np.int64)
+    per = -(-np.diff(ends, prepend=0) // LARS_UNIT)
+    first = np.concatenate([[0], np.cumsum(per)[:-1]]).astype(np.int64)
+    return first, int(per.sum())
+
+
+class LarsTable(SegmentTable):
+    """``SegmentTable`` with what ``lars_ratios`` / ``lars_update`` need beside it, all allocated here, once: bit 1 of a flag byte
+    = no adaptation; ``first_unit`` per segment; ``ratios`` (one float per segment), ``norms`` (|p|, |g| * |grad_scale| per segment,
+    float64) and the workspace of the per-unit partial sums.  A ``prefix(n)`` shares every buffer with its table: its segments are
+    the table's first ones, and a segment's first unit does not depend on the segments behind it."""
+
+    def __init__(self, ends, flags, device):
+        super().__init__(ends, flags, device)
+        first, units = lars_first_units(self.ends_host)
+        self.first_unit = torch.from_numpy(first).to(device)
+        self.ratios = torch.ones(len(self), device=device, dtype=torch.float32)
+        self.norms = torch.zeros(2 * len(self), device=device, dtype=torch.float64)
+        self.workspace = torch.empty(2 * units, device=device, dtype=torch.float64)
+
+    def prefix(self, n):
+        cut = SegmentTable.prefix(self, n)
+        if cut is self:
+            return self
+        cut.__class__ = LarsTable
+        k = len(cut)
+        cut.first_unit, cut.ratios, cut.norms, cut.workspace = self.first_unit[:k], self.ratios[:k], self.norms[:2 * k], self.workspace
+        return cut
+
+
+def lars_ratios(p, g, weight_decay_rate, eta, eps, table, grad_scale=1.0):
+    """the trust ratio of every segment of ``table`` (a ``LarsTable`` over exactly ``p.numel()`` floats) into ``table.ratios``, the
+    two norms into ``table.norms``: two launches, nothing comes back to the host"""
+    if CLASS_COUNT is not None: _acct('optimizer', 0, _nbytes(p, g), _nbytes(table.ratios))
+    check(_lib.load().loans_lars_ratios_f32(_ptr(p), _ptr(g), p.numel(), weight_decay_rate, grad_scale, eta, eps, _ptr(table.ends),
+                                            _ptr(table.flags), _ptr(table.first_unit), table.ends_host.ctypes.data, len(table),
+                                            _ptr(table.ratios), _ptr(table.norms), _ptr(table.workspace),
+                                            table.workspace.numel() * 8, _stream()), 'loans_lars_ratios_f32')
+
+
+def lars_update(p, g, v, lr, momentum, weight_decay_rate, table, grad_scale=1.0):
+    """``momentum_sgd_seg`` with the rate of a segment = fl(fl(lr) * table.ratios[s]), one fp32 product"""
+    if CLASS_COUNT is not None: _acct('optimizer', 0, _nbytes(p, g, v), _nbytes(p, v))
+    dev_lr = torch.is_tensor(lr)
+    if dev_lr:
+        assert lr.dtype == torch.float32 and lr.numel() == 1 and lr.is_cuda
+    check(_lib.load().loans_lars_update_f32(_ptr(p), _ptr(g), _ptr(v), p.numel(), 0.0 if dev_lr else lr, _ptr(lr) if dev_lr else 0,
+                                            momentum, weight_decay_rate, grad_scale, _ptr(table.ends), _ptr(table.flags),
+                                            _ptr(table.ratios), table.ends_host.ctypes.data, len(table), _stream()),
+          'loans_lars_update_f32')
+
+
 class AverageJobs:
     """The job table of ``average_jobs``: pairs of float32 device tensors ``(dst, src)`` of equal size, kept alive here; the
     table is built and uploaded once."""

@@ -363,3 +363,96 @@ class MomentumSGD(GradientMethod):
                                  self._segment_table(arena, n), grad_scale)
             return
         ops.momentum_sgd(arena.data[:n], arena.grad[:n], state[0][:n], lr, hp.momentum, hp.weight_decay_rate, grad_scale)
+
+
+def lars_segments(sizes, offsets, exempt_decay, exempt_adapt, numel):
+    """The segment table of ``ops.lars_ratios`` / ``ops.lars_update`` for the parameters ``decay_segments`` describes: ``(ends,
+    flags)`` with bit 0 of a flag byte = no weight decay (``exempt_decay[i]``) and bit 1 = no adaptation (``exempt_adapt[i]``).  A
+    trust ratio belongs to ONE tensor, so a parameter that adapts is a segment of its own; neighbours are one segment only where
+    both have bit 1 set and their flags are equal.  A parameter's segment runs to the next parameter's offset: the padding behind
+    it is zero and has a zero gradient, it adds nothing to either norm.  A pure function of its arguments."""
+    sizes, offsets = [int(s) for s in sizes], [int(o) for o in offsets]
+    if not sizes or len(sizes) != len(offsets) or len(sizes) != len(exempt_decay) or len(sizes) != len(exempt_adapt):
+        raise ValueError('one size, one offset and two flags per parameter, and at least one parameter')
+    if offsets[0] != 0:
+        raise ValueError('the first parameter starts at offset %d, not 0' % offsets[0])
+    stops = offsets[1:] + [int(numel)]
+    ends, flags = [], []
+    for size, start, stop, nodecay, noadapt in zip(sizes, offsets, stops, exempt_decay, exempt_adapt):
+        if start % 4 or size <= 0 or start + size > stop:
+            raise ValueError('a parameter of %d floats at offset %d does not fit in front of %d on a float4 boundary' % (size, start, stop))
+        flag = int(bool(nodecay)) | int(bool(noadapt)) << 1
+        if flags and flag & 2 and flags[-1] == flag:
+            ends[-1] = stop
+        else:
+            ends.append(stop)
+            flags.append(flag)
+    return np.asarray(ends, np.int64), np.asarray(flags, np.uint8)
+
+
+class LARS(GradientMethod):
+    """Layer-wise adaptive rate scaling (You et al. 2017, the MLPerf ResNet-50 recipe) on ``MomentumSGD``'s rule: per parameter
+    ``r = eta * |p| / (|g| + wd * |p| + eps)`` (1 where either norm is zero), then ``g' = g + wd * p; v = momentum * v - lr * r * g';
+    p += v``.  Parameters whose Chainer shape has at most one dimension -- BN ``gamma`` / ``beta``, biases -- never adapt (r = 1) and,
+    with ``decay_exempt_1d=True``, take no weight decay.  Two passes over the arena: ``ops.lars_ratios`` (norms in float64, ratios
+    left on the device), ``ops.lars_update``.  State: one ``v`` the size of the arena; the prefix rule of the module docstring
+    holds as for ``MomentumSGD`` (a never-used parameter has zero norms: r = 1, and v = g = 0 make its step a no-op)."""
+
+    def __init__(self, lr=0.01, momentum=0.9, weight_decay_rate=0.0, eta=0.001, eps=1e-8, decay_exempt_1d=False):
+        super().__init__()
+        self.hyperparam = SimpleNamespace(lr=lr, momentum=momentum, weight_decay_rate=weight_decay_rate, eta=eta, eps=eps,
+                                          decay_exempt_1d=bool(decay_exempt_1d))
+        self._segments, self._segment_cuts, self._last_table = None, {}, None
+
+    def _segment_table(self, arena, n):
+        """the segments of the first ``n`` floats of ``arena``, with the ratio buffer and the workspace: built and allocated once
+        per arena and cut once per stepped prefix, as ``MomentumSGD._segment_table`` -- no device allocation in a step"""
+        exempt = bool(getattr(self.hyperparam, 'decay_exempt_1d', False))
+        if self._segments is None or self._segments[0] is not arena or self._segments[2] != exempt:
+            if arena.data.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('the decay segment table is uploaded once, outside a captured step: step once before capturing')
+            one_d = [len(p.logical_shape) <= 1 for p in arena.params]
+            ends, flags = lars_segments([p.size for p in arena.params], arena.offsets, [exempt and d for d in one_d], one_d, arena.numel)
+            if len(ends) > ops.LARS_MAX_SEGMENTS:
+                raise ValueError('%d LARS segments: the kernel takes %d' % (len(ends), ops.LARS_MAX_SEGMENTS))
+            self._segments, self._segment_cuts = (arena, ops.LarsTable(ends, flags, arena.device), exempt), {}
+        table = self._segment_cuts.get(n)
+        if table is None:
+            table = self._segment_cuts[n] = self._segments[1].prefix(n)
+        return table
+
+    @property
+    def lr(self):
+        return self.hyperparam.lr
+
+    @lr.setter
+    def lr(self, v):
+        self.hyperparam.lr = v
+
+    def _new_state(self, zeros):
+        return (zeros(),)
+
+    def _state_names(self):
+        return ('v',)
+
+    def _step(self, arena, n, state, lr, grad_scale):
+        hp = self.hyperparam
+        table = self._last_table = self._segment_table(arena, n)
+        ops.lars_ratios(arena.data[:n], arena.grad[:n], hp.weight_decay_rate, hp.eta, hp.eps, table, grad_scale)
+        ops.lars_update(arena.data[:n], arena.grad[:n], state[0][:n], lr, hp.momentum, hp.weight_decay_rate, table, grad_scale)
+
+    def trust_ratios(self):
+        """``{parameter path: ratio}`` of the last step, for the parameters it covered (1.0 for those that never adapt).
+        Synchronises with the device: for diagnostics and tests, not for a training loop."""
+        table = self._last_table
+        if table is None:
+            raise RuntimeError('no step has been taken yet')
+        arena = self._segments[0]
+        ratios = table.ratios.detach().cpu().numpy()
+        named = {id(p): k[1:] for k, p in self.target.namedparams()}
+        n = int(table.ends_host[-1])
+        out = {}
+        for p, o in zip(arena.params, arena.offsets):
+            if o < n:
+                out[named[id(p)]] = float(ratios[int(np.searchsorted(table.ends_host, o, side='right'))])
+        return out
