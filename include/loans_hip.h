@@ -824,6 +824,43 @@ int loans_batch_mix_f32(const float* x, float* out, int32_t B, int32_t C, int32_
                         int32_t shift, float lam, float oml,
                         int32_t y0, int32_t x0, int32_t y1, int32_t x1, void* stream);
 
+/* ---- photometric augmentation of a device batch (csrc/photo.hip): colour jitter, lighting noise, random erasing.  x, out:
+ *      contiguous [B][3][H][W] fp32; image n has the job jobs[n].  A pixel's three channels are worked on together, with
+ *        grey(r, g, b) = fma(0.299, r, fma(0.587, g, 0.114 * b))
+ *        brightness   x = clamp01(b * x)
+ *        saturation   x = clamp01(fma(s, x, oms * grey(pixel)))
+ *        contrast     x = clamp01(fma(c, x, omc * m)),  m = the image's mean grey as it stands when contrast is reached (after the
+ *                     operations that precede contrast in this image's order): fp32 greys summed in fp64 in a fixed order, divided
+ *                     by H W in fp64, rounded to fp32 once
+ *      in the order `order` names: 0 BCS, 1 BSC, 2 CBS, 3 CSB, 4 SBC, 5 SCB.  A factor that is exactly 1 skips its operation (no
+ *      clamp: a bit copy).  Then, if any addend is non-zero, x = x + add[channel], no clamp; last, every pixel inside the erase box
+ *      y0 <= y < y1, x0 <= x < x1 becomes fill[channel], a bit copy.  All factors 1, a zero addend, an empty box: the image leaves
+ *      bit for bit.  omc = fl32(1 - c) and oms = fl32(1 - s) are rounded once, by the caller.  Hue is not built.
+ *      loans_photo_grey_means_f32: for the images with c != 1, one fp64 partial sum per (image, block) into `workspace` (device
+ *      memory, 8-byte aligned, loans_photo_workspace_bytes(B, H, W) bytes at least; it need not be initialised), then a small
+ *      launch that folds each image's partials in ascending block order and leaves its fp32 mean behind the partials; no atomics;
+ *      no launch when no image has c != 1.  loans_photo_apply_f32: one streaming launch that reads those means from the same
+ *      workspace; out == x is allowed (every lane owns its pixels in all three planes); 16-byte accesses where
+ *      W % 4 == 0 and x and out are 16-byte aligned.  `workspace` may be null for it when no image has c != 1.  Two runs give the
+ *      same bits.  jobs_dev: the table in DEVICE memory; jobs_host: the same table in host memory, checked on every call.
+ *      LOANS_EINVAL -- before any launch -- for a null or misaligned pointer, non-positive sizes, C != 3, a workspace that is too
+ *      small, a non-finite factor, addend or fill, an order outside [0, 5], a box that is not 0 <= y0 <= y1 <= H, 0 <= x0 <= x1
+ *      <= W; LOANS_ERANGE for 3 * H * W >= 2^30 (the batch itself is indexed in 64 bits).  Nothing is synchronised with the host. ---- */
+typedef struct loans_photo_job {
+    float b, c, s;              /* the three factors */
+    float omc, oms;             /* fl32(1 - c), fl32(1 - s) */
+    int32_t order;              /* 0 .. 5: the permutation of (brightness, contrast, saturation) */
+    float add[3];               /* RGB addend (lighting noise) */
+    int32_t y0, x0, y1, x1;     /* the erase box; empty where y1 <= y0 or x1 <= x0 */
+    float fill[3];              /* what an erased pixel becomes */
+} loans_photo_job;
+int64_t loans_photo_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int loans_photo_grey_means_f32(const float* x, int32_t B, int32_t C, int32_t H, int32_t W, const loans_photo_job* jobs_dev,
+                               const loans_photo_job* jobs_host, void* workspace, int64_t workspace_bytes, void* stream);
+int loans_photo_apply_f32(const float* x, float* out, int32_t B, int32_t C, int32_t H, int32_t W,
+                          const loans_photo_job* jobs_dev, const loans_photo_job* jobs_host, const void* workspace,
+                          int64_t workspace_bytes, void* stream);
+
 /* library / build identification */
 const char* loans_hip_version(void);
 

@@ -2508,6 +2508,68 @@ def batch_mix(x, shift, lam, oml, box=(0, 0, 0, 0), out=None):
     return out
 
 
+# mirror of loans_photo_job (include/loans_hip.h)
+PHOTO_JOB = np.dtype([('b', '<f4'), ('c', '<f4'), ('s', '<f4'), ('omc', '<f4'), ('oms', '<f4'), ('order', '<i4'), ('add', '<f4', (3,)),
+                      ('y0', '<i4'), ('x0', '<i4'), ('y1', '<i4'), ('x1', '<i4'), ('fill', '<f4', (3,))])
+assert PHOTO_JOB.itemsize == 64
+_photo_workspaces = {}          # (device index, raw stream) -> float64 tensor: the grey pass's partial sums
+
+
+def photo_workspace(device, nbytes):
+    """the workspace of ``photometric`` on ``device`` for the current stream (the grey pass's float64 partial sums, the float32
+    means behind them), at least ``nbytes`` bytes: kept from call to call (it is never part of a step arena), grown when a larger
+    batch comes"""
+    key = (device.index, _stream())
+    ws = _photo_workspaces.get(key)
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = _photo_workspaces[key] = torch.empty(max((int(nbytes) + 7) // 8, 1), device=device, dtype=torch.float64)
+    return ws
+
+
+def photo_identity(jobs):
+    """which jobs of a ``PHOTO_JOB`` table change nothing: every factor 1, a zero addend, an empty box"""
+    return (jobs['b'] == 1) & (jobs['c'] == 1) & (jobs['s'] == 1) & ~jobs['add'].any(axis=1) & \
+        ((jobs['y1'] <= jobs['y0']) | (jobs['x1'] <= jobs['x0']))
+
+
+def photometric(x, jobs, out=None):
+    """colour jitter, lighting noise and random erasing of the device batch x [B][3][H][W] fp32 (csrc/photo.hip; the arithmetic
+    is stated in loans_amd/common/datasets/photometric.py): ``jobs`` is a NumPy record array of dtype ``PHOTO_JOB``, one job per
+    image.  The table goes up through the pinned staging ring; then, on the current stream, the grey-mean entry (partial sums and
+    their fold) where an image has a contrast factor other than 1 and the apply launch -- none at all where every job is the
+    identity and ``out`` is ``x``.
+    Returns a fresh tensor, or ``out``, which may be ``x`` itself: the stage is computable in place.  No host synchronisation."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()):
+        raise ValueError('the batch must be a contiguous float32 [B][3][H][W] device tensor')
+    if out is None:
+        out = torch.empty_like(x)
+    elif not (out.dtype == x.dtype and out.device == x.device and out.is_contiguous() and out.shape == x.shape):
+        raise ValueError('out must be a contiguous float32 tensor of the batch\'s shape on its device')
+    B, C, H, W = x.shape
+    if not (isinstance(jobs, np.ndarray) and jobs.dtype == PHOTO_JOB and jobs.shape == (B,)):
+        raise ValueError('jobs must be a PHOTO_JOB record array with one job per image of the batch')
+    jobs = np.ascontiguousarray(jobs)
+    if out.data_ptr() == x.data_ptr() and photo_identity(jobs).all():
+        return out
+    from .common.datasets import resample           # (imports this module)
+    lib = _lib.load()
+    ring, slot, host = resample._staging.get(jobs.nbytes, kind='photo')      # (a ring of its own: it waits for the copy of two batches ago)
+    host[:jobs.nbytes].numpy()[:] = jobs.view(np.uint8)
+    jobs_d = host[:jobs.nbytes].to(x.device, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(x.device))
+    ring['events'][slot] = ev
+    ws, ws_bytes = None, 0
+    if (jobs['c'] != 1).any():
+        ws_bytes = int(lib.loans_photo_workspace_bytes(B, H, W))
+        ws = photo_workspace(x.device, ws_bytes)
+        check(lib.loans_photo_grey_means_f32(_ptr(x), B, C, H, W, _ptr(jobs_d), jobs.ctypes.data, _ptr(ws), ws_bytes, _stream()),
+              'loans_photo_grey_means_f32')
+    check(lib.loans_photo_apply_f32(_ptr(x), _ptr(out), B, C, H, W, _ptr(jobs_d), jobs.ctypes.data, _ptr(ws), ws_bytes, _stream()),
+          'loans_photo_apply_f32')
+    return out
+
+
 def softmax_xent_eval(z, t, acc, k=1):
     """Evaluation: add the batch's plain loss sum, top-1 hits, top-k hits, valid rows and rows to ``acc`` (5 float64 on the
     device, read-modify-write).  No gradient is written.  No host synchronisation."""

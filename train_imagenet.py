@@ -63,6 +63,19 @@ validation entries are the plain loss on unmixed frames.  A batch that is not mi
     python train_imagenet.py train.tsv val.tsv -b 256 --optimizer sgd --lr 0.1 --augment rrc --label-smoothing 0.1 \
         --mixup-alpha 0.2 --cutmix-alpha 1.0
 
+``--color-jitter B C S``, ``--lighting-std`` and ``--random-erase-prob`` (with ``--augment rrc``; default 0: off) are the
+photometric half of the augmentation, on training batches only, between the crop and the mix: brightness, contrast and saturation
+factors drawn uniformly from ``[max(0, 1 - v), 1 + v]`` and applied in a random order per image (hue is not built), AlexNet-style
+PCA lighting noise of that standard deviation, and random erasing of one box per image with that probability (area fraction
+``--random-erase-scale``, aspect ratio ``--random-erase-ratio``, filled with ``--random-erase-value`` -- the ImageNet mean by
+default: the frames are not mean-subtracted).  The draws come from a stream of their own (``--photo-seed``, rank r from seed +
+7919 r; the crops and the mixes do not depend on it) on the host, the pixels are changed in place on the GPU: one small reduction
+for the contrast means and one streaming pass, on the iterator's stream (loans_amd/common/datasets/photometric.py, csrc/photo.hip).
+Validation frames are never touched.
+
+    python train_imagenet.py train.tsv val.tsv -b 256 --optimizer sgd --lr 0.1 --augment rrc --label-smoothing 0.1 \
+        --color-jitter 0.4 0.4 0.4 --lighting-std 0.1 --random-erase-prob 0.25
+
 ``--ema-decay D`` (default 0: off) keeps an exponential moving average of the weights and the BN statistics
 (loans_amd/runtime/average.py, ``WeightAverage``: one launch per step behind the optimiser's; update t uses the decay
 ``min(D, (1 + t) / (10 + t))``).  When validation runs it runs twice -- the live model first, as always, then the averaged one, whose
@@ -90,13 +103,13 @@ never adapt and, with ``--no-decay-1d``, take no weight decay.  ``--momentum``, 
 ``--checkpoint-interval N`` writes a full-state checkpoint, ``checkpoint_<iteration>.npz`` in the log directory, after every
 N-th iteration and after the last one (default 0: none; ``--checkpoint-keep K``, default 2, keeps the newest K): the model with
 its BN statistics, the optimiser's buffers and step count, the training iterator as of the batch the step consumed (shuffle
-stream, order, position, the crop / mirror draw stream and the mix draw stream), NumPy's global stream and the run's arguments
+stream, order, position, the crop / mirror draw stream, the photometric and the mix draw stream), NumPy's global stream and the run's arguments
 (loans_amd/runtime/checkpoint.py; under ``--gpus N`` one small record per rank beside rank 0's file, which is written last).
 ``--resume PATH`` -- a checkpoint file, or a log directory, whose newest complete checkpoint is taken -- continues that run in
 its log directory: the ``log`` file is read back and appended to, ``elapsed_time`` and the snapshot names count on.  Fixed on
 resume (one error lists every one that differs): the architecture, ``--dtype``, ``--optimizer``, ``-b``, ``--gpus``,
 ``--image-size``, the dataset files or the synthetic sizes, classes and ``--data-seed``, ``--no-shuffle``, ``--augment`` /
-``--rrc-*`` / ``--val-crop-pct`` / ``--augment-seed``, ``--mixup-alpha`` / ``--cutmix-alpha`` / ``--mix-*``, ``--ema-decay`` (a checkpoint from
+``--rrc-*`` / ``--val-crop-pct`` / ``--augment-seed``, ``--mixup-alpha`` / ``--cutmix-alpha`` / ``--mix-*``, ``--color-jitter`` / ``--lighting-std`` / ``--random-erase-*`` / ``--photo-seed``, ``--ema-decay`` (a checkpoint from
 before these options existed ran at their defaults), ``--seed``.  Taken from the new command line (each one that differs is
 printed once): ``--num-epoch``, ``--iterations``, the log, snapshot and checkpoint intervals, ``--loader-threads``, the frame
 cache options, ``--lr``, ``--weight-decay``, ``--momentum``, ``--lr-drop-*``, ``--lr-schedule``, ``--lr-min``, ``--no-decay-1d``, ``--lars-eta``, ``--lars-eps``, ``--warmup-*``, ``--label-smoothing``, ``--topk``.  The
@@ -139,7 +152,9 @@ SYNTHETIC = 'synthetic'
 # what --resume holds against the checkpoint's arguments: everything the data sequence and the model's shape depend on
 RESUME_FIXED = ('use_resnet_18', 'dtype', 'optimizer', 'batch_size', 'gpus', 'image_size', 'train_file', 'val_file', 'dataset_size',
                 'validation_size', 'synthetic_classes', 'data_seed', 'no_shuffle', 'augment', 'rrc_scale', 'rrc_ratio', 'val_crop_pct',
-                'augment_seed', 'seed', 'mixup_alpha', 'cutmix_alpha', 'mix_prob', 'mix_switch_prob', 'mix_seed', 'ema_decay')
+                'augment_seed', 'seed', 'mixup_alpha', 'cutmix_alpha', 'mix_prob', 'mix_switch_prob', 'mix_seed', 'ema_decay',
+                'color_jitter', 'lighting_std', 'random_erase_prob', 'random_erase_scale', 'random_erase_ratio', 'random_erase_value',
+                'photo_seed')
 
 
 class SyntheticClasses:
@@ -202,7 +217,19 @@ class Arguments(argparse.Namespace):
     lars_eta = 0.001
     lars_eps = 1e-8
 
+    # colour jitter, lighting noise, random erasing of the --augment rrc feed (loans_amd/common/datasets/photometric.py); all off by
+    # default, logged where one of them is given
+    color_jitter = (0.0, 0.0, 0.0)
+    lighting_std = 0.0
+    random_erase_prob = 0.0
+    random_erase_scale = (0.02, 0.33)
+    random_erase_ratio = (0.3, 3.3)
+    random_erase_value = (0.485, 0.456, 0.406)
+    photo_seed = None
+
     _MIX = ('mixup_alpha', 'cutmix_alpha', 'mix_prob', 'mix_switch_prob', 'mix_seed')
+    _PHOTO = ('color_jitter', 'lighting_std', 'random_erase_prob', 'random_erase_scale', 'random_erase_ratio', 'random_erase_value',
+              'photo_seed')
     _AVERAGE = ('ema_decay', 'lr_schedule', 'lr_min', 'no_decay_1d')
     _LARS = ('lars_eta', 'lars_eps')
 
@@ -260,6 +287,14 @@ def parse_args(argv=None):
     parser.add_argument("--mix-prob", type=float, default=argparse.SUPPRESS, help="probability that a batch is mixed at all (default 1)")
     parser.add_argument("--mix-switch-prob", type=float, default=argparse.SUPPRESS, help="with both alphas: probability that a mixed batch takes CutMix, not mixup (default 0.5)")
     parser.add_argument("--mix-seed", type=int, default=argparse.SUPPRESS, help="seed of the mix draws (a stream of their own)")
+    # colour jitter, lighting noise, random erasing
+    parser.add_argument("--color-jitter", type=float, nargs=3, default=argparse.SUPPRESS, metavar=('B', 'C', 'S'), help="with --augment rrc: brightness, contrast and saturation factors uniform in [max(0, 1 - v), 1 + v], applied in a random order per image; hue is not built (default 0 0 0: off)")
+    parser.add_argument("--lighting-std", type=float, default=argparse.SUPPRESS, help="with --augment rrc: standard deviation of the AlexNet-style PCA lighting noise (default 0: off)")
+    parser.add_argument("--random-erase-prob", type=float, default=argparse.SUPPRESS, help="with --augment rrc: probability that a training image has one box erased (default 0: off)")
+    parser.add_argument("--random-erase-scale", type=float, nargs=2, default=argparse.SUPPRESS, metavar=('LO', 'HI'), help="area fraction of the erased box (default 0.02 0.33)")
+    parser.add_argument("--random-erase-ratio", type=float, nargs=2, default=argparse.SUPPRESS, metavar=('LO', 'HI'), help="aspect ratio (height / width) of the erased box, log-uniform (default 0.3 3.3)")
+    parser.add_argument("--random-erase-value", type=float, nargs=3, default=argparse.SUPPRESS, metavar=('R', 'G', 'B'), help="what an erased pixel becomes (default 0.485 0.456 0.406, the ImageNet mean: the frames are not mean-subtracted)")
+    parser.add_argument("--photo-seed", type=int, default=argparse.SUPPRESS, help="seed of the colour jitter / lighting / erase draws (a stream of their own)")
     # weight average, cosine rate, decay-free 1-d parameters
     parser.add_argument("--ema-decay", type=float, default=argparse.SUPPRESS, help="keep an exponential moving average of the weights with this decay (warmed up as (1 + t) / (10 + t)); validated and snapshotted beside the live model (default 0: off)")
     parser.add_argument("--lr-schedule", default=argparse.SUPPRESS, choices=['step', 'cosine'], help="step: --lr-drop-epochs; cosine: half a cosine from --lr down to --lr-min over --num-epoch, behind the warm-up (default step)")
@@ -273,12 +308,13 @@ def parse_args(argv=None):
     try:
         check_cache_arguments(args)
         check_mix_arguments(args)
+        check_photo_arguments(args)
         check_average_arguments(args)
         check_lars_arguments(args)
         if args.resume is not None:
             check_average_resume(args)
             world = os.environ.get('WORLD_SIZE')        # a rank under a launcher: the group's size, whatever --gpus says
-            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS_WITH_LARS)
+            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS_WITH_PHOTO)
     except ValueError as e:
         parser.error(str(e))
     return args
@@ -305,6 +341,29 @@ def check_mix_arguments(args):
             raise ValueError('--%s is a probability: it must lie in [0, 1], got %r' % (name.replace('_', '-'), getattr(args, name)))
     if (args.mixup_alpha > 0 or args.cutmix_alpha > 0) and args.augment != 'rrc':
         raise ValueError('--mixup-alpha / --cutmix-alpha mix the batches the GPU crops: they need --augment rrc')
+
+
+def photo_enabled(args):
+    """whether any of the photometric stages is switched on"""
+    return any(v > 0 for v in args.color_jitter) or args.lighting_std > 0 or args.random_erase_prob > 0
+
+
+def check_photo_arguments(args):
+    """ValueError for photometric options that name no distribution, and where a stage is asked of a feed that is not on the device"""
+    if len(args.color_jitter) != 3 or not all(v >= 0 for v in args.color_jitter):
+        raise ValueError('--color-jitter takes three strengths that must not be negative, got %r' % (tuple(args.color_jitter),))
+    if not args.lighting_std >= 0:
+        raise ValueError('--lighting-std must not be negative, got %r' % args.lighting_std)
+    if not 0.0 <= args.random_erase_prob <= 1.0:
+        raise ValueError('--random-erase-prob is a probability: it must lie in [0, 1], got %r' % args.random_erase_prob)
+    for name in ('random_erase_scale', 'random_erase_ratio'):
+        pair = tuple(getattr(args, name))
+        if len(pair) != 2 or not 0 < pair[0] <= pair[1] < math.inf:
+            raise ValueError('--%s takes a positive, ordered range, got %r' % (name.replace('_', '-'), pair))
+    if len(args.random_erase_value) != 3 or not all(math.isfinite(v) for v in args.random_erase_value):
+        raise ValueError('--random-erase-value takes three finite numbers, got %r' % (tuple(args.random_erase_value),))
+    if photo_enabled(args) and args.augment != 'rrc':
+        raise ValueError('--color-jitter / --lighting-std / --random-erase-prob change the batches the GPU crops: they need --augment rrc')
 
 
 def check_average_arguments(args):
@@ -345,9 +404,12 @@ RESUME_DEFAULTS = {name: getattr(Arguments, name) for name in Arguments._MIX}
 # ... and the same for the weight average, the cosine rate and --no-decay-1d (a table of its own: RESUME_DEFAULTS is the mix options')
 RESUME_DEFAULTS_AVERAGE = {name: getattr(Arguments, name) for name in Arguments._AVERAGE}
 ALL_RESUME_DEFAULTS = dict(RESUME_DEFAULTS, **RESUME_DEFAULTS_AVERAGE)
-# ... and for --lars-eta / --lars-eps; this is the table --resume uses
+# ... and for --lars-eta / --lars-eps
 RESUME_DEFAULTS_LARS = {name: getattr(Arguments, name) for name in Arguments._LARS}
 RESUME_DEFAULTS_WITH_LARS = dict(ALL_RESUME_DEFAULTS, **RESUME_DEFAULTS_LARS)
+# ... and for the photometric options; this is the table --resume uses
+RESUME_DEFAULTS_PHOTO = {name: getattr(Arguments, name) for name in Arguments._PHOTO}
+RESUME_DEFAULTS_WITH_PHOTO = dict(RESUME_DEFAULTS_WITH_LARS, **RESUME_DEFAULTS_PHOTO)
 
 
 def cache_budgets(total_bytes, n_train, n_validation):
@@ -464,12 +526,16 @@ def run(args, log=print):
         setattr(args, name, getattr(args, name, getattr(Arguments, name)))
     # the _AVERAGE options are logged where one of them is given: a run without them logs what it always logged
     averaging = any(getattr(args, name) != getattr(Arguments, name) for name in Arguments._AVERAGE)
+    # ... and so are the _PHOTO options
+    photo_given = any((tuple(v) if isinstance(v, (list, tuple)) else v) != getattr(Arguments, name)
+                      for name, v in ((name, getattr(args, name)) for name in Arguments._PHOTO))
     args.gpus = comm.size
     check_cache_arguments(args)
     check_mix_arguments(args)
+    check_photo_arguments(args)
     check_average_arguments(args)
     check_lars_arguments(args)
-    chief = comm.rank == 0                       # prints, logs and writes snapshots
+    chief = comm.rank == 0                     # prints, logs and writes snapshots
 
     # --augment rrc: the iterators hand out (frames, labels) already resident on the device
     feed, batch_converter = {}, converter
@@ -499,6 +565,14 @@ def run(args, log=print):
     # every rank built the same sets and takes every comm.size-th example: the training share padded by wrapping (all ranks make
     # the same iterations and epochs), the validation share not (every example is counted once; shares may differ by one)
     train_dataset = ShardedDataset(train_dataset, comm.rank, comm.size, pad=True)
+    if photo_enabled(args):
+        # between the crop and the mix, with draws of its own: the stream of --photo-seed + 7919 r
+        from loans_amd.common.datasets.photometric import PhotometricBatches, PhotoPolicy
+        jitter = tuple(args.color_jitter)
+        photo_policy = PhotoPolicy(jitter[0], jitter[1], jitter[2], args.lighting_std, args.random_erase_prob,
+                                   tuple(args.random_erase_scale), tuple(args.random_erase_ratio), tuple(args.random_erase_value),
+                                   None if args.photo_seed is None else args.photo_seed + 7919 * comm.rank)
+        train_dataset = PhotometricBatches(train_dataset, photo_policy, tuple(args.image_size))
     if args.mixup_alpha > 0 or args.cutmix_alpha > 0:
         # every rank mixes inside its own batch, with draws of its own: the stream of --mix-seed + 7919 r, as for the crops
         from loans_amd.common.datasets.batch_mix import MixedBatches, MixPolicy
@@ -574,7 +648,7 @@ def run(args, log=print):
         # the run continues in the checkpoint's log directory: no new <time>_<name>
         check_average_resume(args)
         resumed, changed = checkpoint.resolve_resume(args, RESUME_FIXED, log if chief else (lambda line: None), world=comm.size,
-                                                     defaults=RESUME_DEFAULTS_WITH_LARS)
+                                                     defaults=RESUME_DEFAULTS_WITH_PHOTO)
         args.log_dir = os.path.dirname(os.path.abspath(args.resume))
         for line in changed if chief else ():
             log(line)
@@ -589,6 +663,8 @@ def run(args, log=print):
         if argument in checkpoint.FLAGS and checkpoint.FLAGS[argument] == getattr(args, argument):
             continue        # a run without the checkpoint options logs what it always logged
         if argument in Arguments._AVERAGE and not averaging:
+            continue
+        if argument in Arguments._PHOTO and not photo_given:
             continue
         if argument in Arguments._LARS and args.optimizer != 'lars':
             continue        # a run with another optimiser logs what it always logged
