@@ -724,6 +724,42 @@ int loans_lars_update_f32(float* p, const float* g, float* v, int64_t n, double 
                           double weight_decay_rate, double grad_scale, const int64_t* seg_end_dev, const uint8_t* seg_flags_dev,
                           const float* ratios_dev, const int64_t* seg_end_host, int32_t nseg, void* stream);
 
+/* LAMB (You et al. 2019, algorithm 2 with the identity for phi): Adam's direction with decoupled weight decay, its length set per
+ * segment of the flat buffer by the trust ratio.  The segment table is LARS's (same rules, same checks, same two flag bits,
+ * LOANS_LARS_UNIT, LOANS_LARS_MAX_SEGMENTS, loans_lars_workspace_bytes).  Step t (1-based):
+ *   g^ = g * grad_scale;   m' = m + (1 - beta1) (g^ - m);   v' = v + (1 - beta2) (g^ g^ - v)
+ *   a  = (m' c1) / (sqrt(v' c2) + eps)       c1 = 1 / (1 - beta1^t), c2 = 1 / (1 - beta2^t): the caller forms them in double
+ *   wd_s = (flags[s] & 1) ? 0 : weight_decay_rate;   u = a + wd_s p
+ *   W_s = sqrt(sum p_i^2)   U_s = sqrt(sum u_i^2)    over segment s
+ *   r_s = (flags[s] & 2) || W_s == 0 || U_s == 0 ? 1 : W_s / U_s
+ *   p' = p - (lr r_s) u
+ * fp32 per element with the order fixed by fmaf: m' = fmaf(omb1, g^ - m, m); v' = fmaf(omb2, fmaf(g^, g^, -v), v);
+ * u = fmaf(wd_s, p, a); p' = fmaf(-fl(fl(lr) * r_s), u, p); every scalar is rounded to fp32 once.  Squares and sums of the norms
+ * are fp64 in a fixed order, r_s is formed in double and rounded to fp32 once; no atomic is used: the same inputs give the same bits.
+ *
+ * Three launches per step, nothing is synchronised with the host:
+ * loans_lamb_moments_f32  reads p (not written), g, m, v; writes m', v' and, per unit of LOANS_LARS_UNIT floats, the sums of p^2
+ *                         and u^2 into the workspace (two doubles per unit; it need not be initialised);
+ * loans_lamb_ratios_f32   folds the workspace per segment in ascending unit order: r_s into ratios_dev[0 .. nseg) and, if
+ *                         norms_dev != NULL, W_s and U_s into norms_dev[2 s], norms_dev[2 s + 1];
+ * loans_lamb_update_f32   reads p, m', v', forms u again from them -- the same function, the same bits as the u whose square
+ *                         was summed -- and writes p'.  c1, c2, eps and weight_decay_rate must be those of the moments call.
+ *
+ * LOANS_EINVAL, and no launch: a null pointer (norms_dev may be null), p / g / m / v / workspace off a 16-byte boundary, the
+ * int64 tables off an 8-byte one, ratios_dev off a 4-byte one, n <= 0, nseg outside [1, LOANS_LARS_MAX_SEGMENTS], ends not
+ * ascending, an inner end that is no multiple of 4, a last end != n, a workspace that is too small, beta1 or beta2 outside
+ * [0, 1), c1 or c2 not >= 1, eps < 0. */
+int loans_lamb_moments_f32(const float* p, const float* g, float* m, float* v, int64_t n, double beta1, double beta2, double c1,
+                           double c2, double eps, double weight_decay_rate, double grad_scale, const int64_t* seg_end_dev,
+                           const uint8_t* seg_flags_dev, const int64_t* seg_first_unit_dev, const int64_t* seg_end_host,
+                           int32_t nseg, void* workspace, int64_t workspace_bytes, void* stream);
+int loans_lamb_ratios_f32(int64_t n, const int64_t* seg_end_dev, const uint8_t* seg_flags_dev, const int64_t* seg_first_unit_dev,
+                          const int64_t* seg_end_host, int32_t nseg, float* ratios_dev, double* norms_dev, const void* workspace,
+                          int64_t workspace_bytes, void* stream);
+int loans_lamb_update_f32(float* p, const float* m, const float* v, int64_t n, double lr, double c1, double c2, double eps,
+                          double weight_decay_rate, const int64_t* seg_end_dev, const uint8_t* seg_flags_dev,
+                          const float* ratios_dev, const int64_t* seg_end_host, int32_t nseg, void* stream);
+
 /* A table of streaming jobs over float ranges in ONE launch: the exponential moving average of a model's weights
  * (loans_amd/runtime/average.py) -- job 0 the whole parameter arena, the others the ~100 small BN statistics tensors.
  *   LOANS_AVG_UPDATE:  dst += omd * (src - dst)      (omd = 1 - decay; exactly nothing where dst == src)

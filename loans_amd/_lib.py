@@ -186,6 +186,9 @@ SIGNATURES = {
     'loans_lars_workspace_bytes': [_p, _i32],
     'loans_lars_ratios_f32': [_p, _p, _i64, _f64, _f64, _f64, _f64, _p, _p, _p, _p, _i32, _p, _p, _p, _i64, _p],
     'loans_lars_update_f32': [_p, _p, _p, _i64, _f64, _p, _f64, _f64, _f64, _p, _p, _p, _p, _i32, _p],
+    'loans_lamb_moments_f32': [_p, _p, _p, _p, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _f64, _p, _p, _p, _p, _i32, _p, _i64, _p],
+    'loans_lamb_ratios_f32': [_i64, _p, _p, _p, _p, _i32, _p, _p, _p, _i64, _p],
+    'loans_lamb_update_f32': [_p, _p, _p, _i64, _f64, _f64, _f64, _f64, _f64, _p, _p, _p, _p, _i32, _p],
     'loans_average_jobs_f32': [_p, _p, _i32, _i64, _i32, _f32, _p],
     'loans_photo_workspace_bytes': [_i32, _i32, _i32],
     'loans_photo_grey_means_f32': [_p, _i32, _i32, _i32, _i32, _p, _p, _p, _i64, _p],

@@ -2873,6 +2873,35 @@ def lars_update(p, g, v, lr, momentum, weight_decay_rate, table, grad_scale=1.0)
           'loans_lars_update_f32')
 
 
+def lamb_moments(p, g, m, v, beta1, beta2, c1, c2, eps, weight_decay_rate, table, grad_scale=1.0):
+    """LAMB, pass 1 over ``table`` (a ``LarsTable`` over exactly ``p.numel()`` floats): ``m``, ``v`` become the new moments and the
+    per-unit sums of ``p^2`` and ``u^2`` go to ``table.workspace``; ``p`` is only read.  ``c1 = 1 / (1 - beta1^t)``,
+    ``c2 = 1 / (1 - beta2^t)``, formed in double by the caller."""
+    if CLASS_COUNT is not None: _acct('optimizer', 0, _nbytes(p, g, m, v), _nbytes(m, v))
+    check(_lib.load().loans_lamb_moments_f32(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), beta1, beta2, c1, c2, eps, weight_decay_rate,
+                                             grad_scale, _ptr(table.ends), _ptr(table.flags), _ptr(table.first_unit),
+                                             table.ends_host.ctypes.data, len(table), _ptr(table.workspace),
+                                             table.workspace.numel() * 8, _stream()), 'loans_lamb_moments_f32')
+
+
+def lamb_ratios(table):
+    """LAMB, pass 2: ``table.workspace`` folded per segment into ``table.ratios`` (|p| / |u|, 1 where the segment does not adapt or
+    a norm is zero) and ``table.norms`` (|p|, |u|): one launch, nothing comes back to the host"""
+    if CLASS_COUNT is not None: _acct('optimizer', 0, _nbytes(table.workspace), _nbytes(table.ratios))
+    check(_lib.load().loans_lamb_ratios_f32(int(table.ends_host[-1]), _ptr(table.ends), _ptr(table.flags), _ptr(table.first_unit),
+                                            table.ends_host.ctypes.data, len(table), _ptr(table.ratios), _ptr(table.norms),
+                                            _ptr(table.workspace), table.workspace.numel() * 8, _stream()), 'loans_lamb_ratios_f32')
+
+
+def lamb_update(p, m, v, lr, c1, c2, eps, weight_decay_rate, table):
+    """LAMB, pass 3: ``p -= fl(fl(lr) * table.ratios[s]) * u`` with ``u`` formed again from ``p`` and the moments ``lamb_moments``
+    stored, by the same device function -- ``c1``, ``c2``, ``eps`` and the decay must be that call's"""
+    if CLASS_COUNT is not None: _acct('optimizer', 0, _nbytes(p, m, v), _nbytes(p))
+    check(_lib.load().loans_lamb_update_f32(_ptr(p), _ptr(m), _ptr(v), p.numel(), lr, c1, c2, eps, weight_decay_rate, _ptr(table.ends),
+                                            _ptr(table.flags), _ptr(table.ratios), table.ends_host.ctypes.data, len(table), _stream()),
+          'loans_lamb_update_f32')
+
+
 class AverageJobs:
     """The job table of ``average_jobs``: pairs of float32 device tensors ``(dst, src)`` of equal size, kept alive here; the
     table is built and uploaded once."""

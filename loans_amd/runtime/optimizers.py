@@ -456,3 +456,68 @@ class LARS(GradientMethod):
             if o < n:
                 out[named[id(p)]] = float(ratios[int(np.searchsorted(table.ends_host, o, side='right'))])
         return out
+
+
+class LAMB(GradientMethod):
+    """LAMB (You et al. 2019, "Large Batch Optimization for Deep Learning", algorithm 2 with the identity for phi): Adam's direction
+    with decoupled weight decay, its length set per parameter tensor by the trust ratio.  Step ``t`` (1-based), ``gs`` the gradient
+    scale of a data-parallel step; segment ``s`` of the arena has flag byte ``f``: bit 0 = no weight decay, bit 1 = no adaptation
+    (``lars_segments``' table)::
+
+        g^  = g * gs
+        m'  = m + (1 - beta1) (g^ - m)
+        v'  = v + (1 - beta2) (g^ g^ - v)
+        c1  = 1 / (1 - beta1^t)      c2 = 1 / (1 - beta2^t)
+        a   = (m' c1) / (sqrt(v' c2) + eps)
+        wd_s = (f & 1) ? 0 : wd
+        u   = a + wd_s p                 (decoupled decay, inside the trust ratio as in the paper)
+        W   = |p|_2 over the segment     U = |u|_2 over the segment
+        r   = (f & 2) or W == 0 or U == 0 ?  1  :  W / U
+        p'  = p - (lr r) u
+
+    ``c1`` and ``c2`` are formed in double here and rounded to fp32 once; ``W``, ``U`` and ``r`` are formed in double from fp64 sums
+    of the squares of the fp32 values, and ``r`` is rounded to fp32 once.  Parameters whose Chainer shape has at most one dimension
+    -- BN ``gamma`` / ``beta``, biases -- never adapt (r = 1) and, with ``decay_exempt_1d=True``, take no decay, as for ``LARS``.
+    There is no clamp on ``W`` and no gradient clipping.  Wherever a segment adapts, ``|p' - p|_2 = lr |p|_2`` at every step,
+    whatever the gradient.  ``v = g^2`` overflows fp32 beyond ``|g gs|`` ~ 1e19: Adam's own limit.
+
+    Three launches per step (``ops.lamb_moments``, ``ops.lamb_ratios``, ``ops.lamb_update``; ``csrc/lamb.hip``); the bias correction
+    travels as ``c1``, ``c2``, not inside the rate, so ``lr`` is the plain hyperparameter.  State: ``m`` and ``v``, each the size of
+    the arena.  The prefix rule of the module docstring holds: beyond the stepped prefix nothing is touched (inside it a
+    parameter with zero gradient and zero moments has u = wd_s p: with decay it shrinks by lr of its norm, without it stays)."""
+
+    def __init__(self, lr=0.001, beta1=0.9, beta2=0.999, eps=1e-6, weight_decay_rate=0.0, decay_exempt_1d=False):
+        super().__init__()
+        self.hyperparam = SimpleNamespace(lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay_rate=weight_decay_rate,
+                                          decay_exempt_1d=bool(decay_exempt_1d))
+        self._segments, self._segment_cuts, self._last_table = None, {}, None
+
+    _segment_table = LARS._segment_table        # built once per arena, cut once per stepped prefix: no device allocation in a step
+    trust_ratios = LARS.trust_ratios
+
+    @property
+    def lr(self):
+        return self.hyperparam.lr
+
+    @lr.setter
+    def lr(self, v):
+        self.hyperparam.lr = v
+
+    def _new_state(self, zeros):
+        return zeros(), zeros()
+
+    def _state_names(self):
+        return ('m', 'v')
+
+    def _step(self, arena, n, state, lr, grad_scale):
+        if torch.is_tensor(lr) or (arena.data.is_cuda and torch.cuda.is_current_stream_capturing()):
+            raise RuntimeError('LAMB is not built for a captured step: its bias corrections c1, c2 change with every step and '
+                               'travel as launch arguments')
+        hp = self.hyperparam
+        c1, c2 = 1.0 / (1.0 - math.pow(hp.beta1, self.t)), 1.0 / (1.0 - math.pow(hp.beta2, self.t))
+        table = self._last_table = self._segment_table(arena, n)
+        m, v = state
+        ops.lamb_moments(arena.data[:n], arena.grad[:n], m[:n], v[:n], hp.beta1, hp.beta2, c1, c2, hp.eps, hp.weight_decay_rate,
+                         table, grad_scale)
+        ops.lamb_ratios(table)
+        ops.lamb_update(arena.data[:n], m[:n], v[:n], lr, c1, c2, hp.eps, hp.weight_decay_rate, table)

@@ -84,7 +84,7 @@ entries are ``validation/ema/loss``, ``validation/ema/accuracy`` and ``validatio
 hand to ``train_sheep_localizer.py --rl`` after a long run.  The average is part of the checkpoints; a checkpoint written without
 the option is not resumed with it, nor the reverse.  ``--lr-schedule cosine`` (default ``step``) takes the rate from ``--lr`` at the
 end of the warm-up down half a cosine to ``--lr-min`` (default 0) at ``--num-epoch``; ``--lr-drop-epochs`` belongs to ``step``.
-``--no-decay-1d`` (with ``--optimizer sgd`` or ``lars``) exempts BN scales / shifts and biases from ``--weight-decay``.  The schedule and the
+``--no-decay-1d`` (with ``--optimizer sgd``, ``lars`` or ``lamb``) exempts BN scales / shifts and biases from ``--weight-decay``.  The schedule and the
 exemption may change on resume, like ``--weight-decay``.
 
     python train_imagenet.py train.tsv val.tsv -b 256 --optimizer sgd --lr 0.1 --weight-decay 5e-5 --no-decay-1d \
@@ -100,6 +100,18 @@ never adapt and, with ``--no-decay-1d``, take no weight decay.  ``--momentum``, 
     python train_imagenet.py train.tsv val.tsv --gpus 8 -b 512 --dtype bf16 --optimizer lars --lr 10 --weight-decay 5e-5 \
         --no-decay-1d --lr-schedule cosine --warmup-epochs 5 --num-epoch 90 --label-smoothing 0.1 --augment rrc
 
+``--optimizer lamb`` is the Adam-shaped large-batch optimiser (LAMB, You et al. 2019, algorithm 2: ``loans_amd.LAMB``): Adam's
+bias-corrected direction ``a = m^ / (sqrt(v^) + --lamb-eps)`` (``--lamb-beta1``, default 0.9; ``--lamb-beta2``, default 0.999;
+``--lamb-eps``, default 1e-6) plus the decoupled decay ``--weight-decay * w``, stepped per parameter tensor by ``--lr * |w| / |u|``, so
+that every adapting tensor moves by ``--lr`` of its own norm per step.  BN scales / shifts and biases never adapt and, with
+``--no-decay-1d``, take no weight decay.  ``--lr``, ``--weight-decay``, the warm-up, both schedules, ``--ema-decay``, ``--gpus N``
+and the checkpoints work as for ``lars``; the betas and ``--lamb-eps`` may change on resume, like ``--momentum``.  The recipe the
+augmentation options above were built for:
+
+    python train_imagenet.py train.tsv val.tsv --gpus 8 -b 256 --dtype bf16 --optimizer lamb --lr 5e-3 --weight-decay 0.02 \
+        --no-decay-1d --lr-schedule cosine --lr-min 1e-6 --warmup-epochs 5 --num-epoch 300 --augment rrc --mixup-alpha 0.2 \
+        --cutmix-alpha 1.0 --color-jitter 0.4 0.4 0.4 --random-erase-prob 0.25 --ema-decay 0.9999
+
 ``--checkpoint-interval N`` writes a full-state checkpoint, ``checkpoint_<iteration>.npz`` in the log directory, after every
 N-th iteration and after the last one (default 0: none; ``--checkpoint-keep K``, default 2, keeps the newest K): the model with
 its BN statistics, the optimiser's buffers and step count, the training iterator as of the batch the step consumed (shuffle
@@ -112,7 +124,7 @@ resume (one error lists every one that differs): the architecture, ``--dtype``, 
 ``--rrc-*`` / ``--val-crop-pct`` / ``--augment-seed``, ``--mixup-alpha`` / ``--cutmix-alpha`` / ``--mix-*``, ``--color-jitter`` / ``--lighting-std`` / ``--random-erase-*`` / ``--photo-seed``, ``--ema-decay`` (a checkpoint from
 before these options existed ran at their defaults), ``--seed``.  Taken from the new command line (each one that differs is
 printed once): ``--num-epoch``, ``--iterations``, the log, snapshot and checkpoint intervals, ``--loader-threads``, the frame
-cache options, ``--lr``, ``--weight-decay``, ``--momentum``, ``--lr-drop-*``, ``--lr-schedule``, ``--lr-min``, ``--no-decay-1d``, ``--lars-eta``, ``--lars-eps``, ``--warmup-*``, ``--label-smoothing``, ``--topk``.  The
+cache options, ``--lr``, ``--weight-decay``, ``--momentum``, ``--lr-drop-*``, ``--lr-schedule``, ``--lr-min``, ``--no-decay-1d``, ``--lars-eta``, ``--lars-eps``, ``--lamb-beta1``, ``--lamb-beta2``, ``--lamb-eps``, ``--warmup-*``, ``--label-smoothing``, ``--topk``.  The
 frame caches start empty after a resume and refill during the first epoch.
 
     python train_imagenet.py train.tsv val.tsv -b 256 --optimizer sgd --lr 0.1 --lr-drop-epochs 30 60 90 --checkpoint-interval 500
@@ -217,6 +229,11 @@ class Arguments(argparse.Namespace):
     lars_eta = 0.001
     lars_eps = 1e-8
 
+    # --optimizer lamb (loans_amd/runtime/optimizers.py: LAMB); logged with that optimiser only
+    lamb_beta1 = 0.9
+    lamb_beta2 = 0.999
+    lamb_eps = 1e-6
+
     # colour jitter, lighting noise, random erasing of the --augment rrc feed (loans_amd/common/datasets/photometric.py); all off by
     # default, logged where one of them is given
     color_jitter = (0.0, 0.0, 0.0)
@@ -232,6 +249,7 @@ class Arguments(argparse.Namespace):
               'photo_seed')
     _AVERAGE = ('ema_decay', 'lr_schedule', 'lr_min', 'no_decay_1d')
     _LARS = ('lars_eta', 'lars_eps')
+    _LAMB = ('lamb_beta1', 'lamb_beta2', 'lamb_eps')
 
 
 def parse_args(argv=None):
@@ -241,14 +259,14 @@ def parse_args(argv=None):
     parser.add_argument("--use-resnet-18", action='store_true', default=False, help="SheepLocalizer (ResNet-18 variant) instead of the ResNet-50 one")
     parser.add_argument("-b", "--batch-size", type=int, default=32, help="batch size")
     parser.add_argument("-g", "--gpu", type=int, default=-1, help="gpu id to use (-1: the current device)")
-    parser.add_argument("--lr", "--learning-rate", dest="learning_rate", type=float, default=0.001, help="Adam's alpha / momentum SGD's and LARS's lr")
+    parser.add_argument("--lr", "--learning-rate", dest="learning_rate", type=float, default=0.001, help="Adam's alpha / momentum SGD's, LARS's and LAMB's lr")
     parser.add_argument("--weight-decay", type=float, default=0.0, help="weight_decay_rate of the optimiser")
-    parser.add_argument("--optimizer", default='adam', choices=['adam', 'sgd', 'lars'], help="Adam, SGD with momentum, or LARS: momentum SGD with per-layer trust ratios, for large batches")
+    parser.add_argument("--optimizer", default='adam', choices=['adam', 'sgd', 'lars', 'lamb'], help="Adam, SGD with momentum, LARS (momentum SGD with per-layer trust ratios) or LAMB (Adam with decoupled decay and per-layer trust ratios), the last two for large batches")
     parser.add_argument("--momentum", type=float, default=0.9, help="momentum of --optimizer sgd / lars")
     parser.add_argument("--lr-drop-epochs", type=int, nargs='+', default=(), help="epochs at whose first iteration the rate is multiplied by --lr-drop-factor")
     parser.add_argument("--lr-drop-factor", type=float, default=0.1, help="factor of each learning rate step")
     parser.add_argument("--label-smoothing", type=float, default=0.0, help="label smoothing of the training loss (uniform over all classes)")
-    parser.add_argument("--topk", type=int, default=None, help="also report top-k accuracy (default: 5 with --optimizer sgd / lars, off with adam; 0: off)")
+    parser.add_argument("--topk", type=int, default=None, help="also report top-k accuracy (default: 5 with --optimizer sgd / lars / lamb, off with adam; 0: off)")
     parser.add_argument("--num-epoch", type=int, default=100, help="number of epochs to train")
     parser.add_argument("--iterations", type=int, default=None, help="stop after this many iterations (before --num-epoch epochs)")
     parser.add_argument("--image-size", type=int, nargs=2, default=(224, 224), help="input size")
@@ -299,10 +317,14 @@ def parse_args(argv=None):
     parser.add_argument("--ema-decay", type=float, default=argparse.SUPPRESS, help="keep an exponential moving average of the weights with this decay (warmed up as (1 + t) / (10 + t)); validated and snapshotted beside the live model (default 0: off)")
     parser.add_argument("--lr-schedule", default=argparse.SUPPRESS, choices=['step', 'cosine'], help="step: --lr-drop-epochs; cosine: half a cosine from --lr down to --lr-min over --num-epoch, behind the warm-up (default step)")
     parser.add_argument("--lr-min", type=float, default=argparse.SUPPRESS, help="the rate --lr-schedule cosine ends at (default 0)")
-    parser.add_argument("--no-decay-1d", action='store_true', default=argparse.SUPPRESS, help="with --optimizer sgd / lars: no weight decay on BN scales / shifts and on biases")
+    parser.add_argument("--no-decay-1d", action='store_true', default=argparse.SUPPRESS, help="with --optimizer sgd / lars / lamb: no weight decay on BN scales / shifts and on biases")
     # LARS
     parser.add_argument("--lars-eta", type=float, default=argparse.SUPPRESS, help="with --optimizer lars: the trust coefficient (default 0.001)")
     parser.add_argument("--lars-eps", type=float, default=argparse.SUPPRESS, help="with --optimizer lars: added to the trust ratio's denominator (default 1e-8)")
+    # LAMB
+    parser.add_argument("--lamb-beta1", type=float, default=argparse.SUPPRESS, help="with --optimizer lamb: decay of the first moment (default 0.9)")
+    parser.add_argument("--lamb-beta2", type=float, default=argparse.SUPPRESS, help="with --optimizer lamb: decay of the second moment (default 0.999)")
+    parser.add_argument("--lamb-eps", type=float, default=argparse.SUPPRESS, help="with --optimizer lamb: added to the root of the second moment (default 1e-6)")
     checkpoint.add_arguments(parser, argparse.SUPPRESS)
     args = parser.parse_args(argv, namespace=Arguments())
     try:
@@ -311,10 +333,11 @@ def parse_args(argv=None):
         check_photo_arguments(args)
         check_average_arguments(args)
         check_lars_arguments(args)
+        check_lamb_arguments(args)
         if args.resume is not None:
             check_average_resume(args)
             world = os.environ.get('WORLD_SIZE')        # a rank under a launcher: the group's size, whatever --gpus says
-            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS_WITH_PHOTO)
+            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS_WITH_LAMB)
     except ValueError as e:
         parser.error(str(e))
     return args
@@ -374,7 +397,7 @@ def check_average_arguments(args):
         raise ValueError('--lr-drop-epochs belongs to --lr-schedule step: the cosine rate has no steps')
     if args.lr_min < 0:
         raise ValueError('--lr-min must not be negative, got %r' % args.lr_min)
-    if args.no_decay_1d and args.optimizer not in ('sgd', 'lars'):
+    if args.no_decay_1d and args.optimizer not in ('sgd', 'lars', 'lamb'):
         raise ValueError('--no-decay-1d is built for --optimizer sgd: Adam\'s kernel applies one weight decay to every parameter')
 
 
@@ -386,6 +409,17 @@ def check_lars_arguments(args):
         raise ValueError('--lars-eps must not be negative, got %r' % args.lars_eps)
     if args.optimizer != 'lars' and any(name in vars(args) for name in Arguments._LARS):
         raise ValueError('--lars-eta / --lars-eps belong to --optimizer lars')
+
+
+def check_lamb_arguments(args):
+    """ValueError for betas or an epsilon the kernels refuse, and for any of the three given to another optimiser"""
+    for name in ('lamb_beta1', 'lamb_beta2'):
+        if not 0 <= getattr(args, name) < 1:
+            raise ValueError('--%s must lie in [0, 1), got %r' % (name.replace('_', '-'), getattr(args, name)))
+    if not args.lamb_eps >= 0:
+        raise ValueError('--lamb-eps must not be negative, got %r' % args.lamb_eps)
+    if args.optimizer != 'lamb' and any(name in vars(args) for name in Arguments._LAMB):
+        raise ValueError('--lamb-beta1 / --lamb-beta2 / --lamb-eps belong to --optimizer lamb')
 
 
 AVERAGE_RESUME = {False: '--resume: the checkpoint was written without --ema-decay and holds no weight average: resume it without the option',
@@ -407,9 +441,12 @@ ALL_RESUME_DEFAULTS = dict(RESUME_DEFAULTS, **RESUME_DEFAULTS_AVERAGE)
 # ... and for --lars-eta / --lars-eps
 RESUME_DEFAULTS_LARS = {name: getattr(Arguments, name) for name in Arguments._LARS}
 RESUME_DEFAULTS_WITH_LARS = dict(ALL_RESUME_DEFAULTS, **RESUME_DEFAULTS_LARS)
-# ... and for the photometric options; this is the table --resume uses
+# ... and for the photometric options
 RESUME_DEFAULTS_PHOTO = {name: getattr(Arguments, name) for name in Arguments._PHOTO}
 RESUME_DEFAULTS_WITH_PHOTO = dict(RESUME_DEFAULTS_WITH_LARS, **RESUME_DEFAULTS_PHOTO)
+# ... and for --lamb-beta1 / --lamb-beta2 / --lamb-eps; this is the table --resume uses
+RESUME_DEFAULTS_LAMB = {name: getattr(Arguments, name) for name in Arguments._LAMB}
+RESUME_DEFAULTS_WITH_LAMB = dict(RESUME_DEFAULTS_WITH_PHOTO, **RESUME_DEFAULTS_LAMB)
 
 
 def cache_budgets(total_bytes, n_train, n_validation):
@@ -443,9 +480,9 @@ def warmup_factor(epoch_detail, warmup_epochs, start_factor):
 
 
 def resolved_topk(args):
-    """k of the reported top-k accuracy, or None: ``--topk`` where given (0: off), else 5 with SGD and LARS and off with Adam"""
+    """k of the reported top-k accuracy, or None: ``--topk`` where given (0: off), else 5 with SGD, LARS and LAMB and off with Adam"""
     if args.topk is None:
-        return 5 if args.optimizer in ('sgd', 'lars') else None
+        return 5 if args.optimizer in ('sgd', 'lars', 'lamb') else None
     return args.topk if args.topk > 0 else None
 
 
@@ -535,6 +572,7 @@ def run(args, log=print):
     check_photo_arguments(args)
     check_average_arguments(args)
     check_lars_arguments(args)
+    check_lamb_arguments(args)
     chief = comm.rank == 0                     # prints, logs and writes snapshots
 
     # --augment rrc: the iterators hand out (frames, labels) already resident on the device
@@ -593,6 +631,9 @@ def run(args, log=print):
     if args.optimizer == 'lars':
         optimizer, rate_name = loans_amd.LARS(lr=args.learning_rate, momentum=args.momentum, weight_decay_rate=args.weight_decay,
                                               eta=args.lars_eta, eps=args.lars_eps, decay_exempt_1d=bool(args.no_decay_1d)), 'lr'
+    elif args.optimizer == 'lamb':
+        optimizer, rate_name = loans_amd.LAMB(lr=args.learning_rate, beta1=args.lamb_beta1, beta2=args.lamb_beta2, eps=args.lamb_eps,
+                                              weight_decay_rate=args.weight_decay, decay_exempt_1d=bool(args.no_decay_1d)), 'lr'
     elif args.optimizer == 'sgd':
         exempt = {'decay_exempt_1d': True} if args.no_decay_1d else {}
         optimizer, rate_name = loans_amd.MomentumSGD(lr=args.learning_rate, momentum=args.momentum, weight_decay_rate=args.weight_decay, **exempt), 'lr'
@@ -648,7 +689,7 @@ def run(args, log=print):
         # the run continues in the checkpoint's log directory: no new <time>_<name>
         check_average_resume(args)
         resumed, changed = checkpoint.resolve_resume(args, RESUME_FIXED, log if chief else (lambda line: None), world=comm.size,
-                                                     defaults=RESUME_DEFAULTS_WITH_PHOTO)
+                                                     defaults=RESUME_DEFAULTS_WITH_LAMB)
         args.log_dir = os.path.dirname(os.path.abspath(args.resume))
         for line in changed if chief else ():
             log(line)
@@ -668,6 +709,8 @@ def run(args, log=print):
             continue
         if argument in Arguments._LARS and args.optimizer != 'lars':
             continue        # a run with another optimiser logs what it always logged
+        if argument in Arguments._LAMB and args.optimizer != 'lamb':
+            continue
         data_to_log[argument] = getattr(args, argument)
     log_entries = []
     state = dict(models={'model': model}, optimizers={'main': optimizer}, iterators={'main': train_iter}, comm=comm)
@@ -696,6 +739,9 @@ def run(args, log=print):
         if args.optimizer == 'lars':
             optimizer.hyperparam.decay_exempt_1d, optimizer.hyperparam.momentum = bool(args.no_decay_1d), args.momentum
             optimizer.hyperparam.eta, optimizer.hyperparam.eps = args.lars_eta, args.lars_eps
+        if args.optimizer == 'lamb':
+            optimizer.hyperparam.decay_exempt_1d = bool(args.no_decay_1d)
+            optimizer.hyperparam.beta1, optimizer.hyperparam.beta2, optimizer.hyperparam.eps = args.lamb_beta1, args.lamb_beta2, args.lamb_eps
         it = updater.iteration = int(resumed['iteration'])
         t0 -= float(resumed['elapsed_time'])
         log_entries = checkpoint.read_log(args.log_dir, it)
