@@ -760,6 +760,32 @@ int loans_lamb_update_f32(float* p, const float* m, const float* v, int64_t n, d
                           double weight_decay_rate, const int64_t* seg_end_dev, const uint8_t* seg_flags_dev,
                           const float* ratios_dev, const int64_t* seg_end_host, int32_t nseg, void* stream);
 
+/* Gradient clipping by the global L2 norm (chainer.optimizer_hooks.GradientClipping) over the first n floats g of a flat gradient
+ * buffer; grad_scale = the optimiser's (1 / world size where the buffer holds the sum over ranks), max_norm = the threshold c > 0:
+ *   S    = sum g_i^2                      every g_i converted to double and squared (exact), summed in fp64 in a FIXED order
+ *   N    = |grad_scale| * sqrt(S)         in double: the norm of the gradient the optimiser will actually apply
+ *   k    = (N is finite and N > c) ? c / N : 1          in double, rounded to fp32 ONCE
+ *   g_i' = fl32(g_i * k)                  one fp32 product per element, in place -- skipped entirely when k == 1
+ * N == c does not clip (Chainer's `rate < 1`); an all-zero gradient gives N = 0, k = 1 and no division; a non-finite N (a NaN or inf
+ * anywhere in g, or a sum that overflows) gives k = 1: g stays bit for bit as it was and the record holds the non-finite N (Chainer
+ * would write 0 * inf); max_norm = +inf is legal and means "measure only".
+ *
+ * loans_grad_norm_f32: two launches -- one fp64 partial per unit of LOANS_LARS_UNIT floats (unit u = floats [4096 u, ..)), then one
+ * wave that sums the partials of lane l = l, l + 64, .. in ascending order and the 64 lane sums in an xor butterfly -- leave
+ * record_dev[0] = N (rounded to fp32 once) and record_dev[1] = k.  The order of the additions is a function of n alone and no atomic
+ * is used: the same inputs give the same bits.  workspace: device memory, 16-byte aligned, of at least
+ * loans_grad_clip_workspace_bytes(n) bytes (host arithmetic only; < 0: a LOANS_E* code); it need not be initialised.
+ * loans_grad_clip_apply_f32: one launch; every block reads record_dev[1] and returns at once if it is 1, else g *= k in place.
+ * Nothing is synchronised with the host.
+ *
+ * LOANS_EINVAL, and no launch: a null pointer, g or workspace off a 16-byte boundary, record_dev off an 8-byte one, n <= 0, a
+ * workspace that is too small, max_norm not > 0 (or NaN), a non-finite grad_scale.  LOANS_ERANGE: n > LOANS_GRAD_CLIP_MAX_N. */
+#define LOANS_GRAD_CLIP_MAX_N ((int64_t)1 << 42)
+int64_t loans_grad_clip_workspace_bytes(int64_t n);
+int loans_grad_norm_f32(const float* g, int64_t n, double grad_scale, double max_norm, void* workspace, int64_t workspace_bytes,
+                        float* record_dev /* [0] = N, [1] = k */, void* stream);
+int loans_grad_clip_apply_f32(float* g, int64_t n, const float* record_dev, void* stream);
+
 /* A table of streaming jobs over float ranges in ONE launch: the exponential moving average of a model's weights
  * (loans_amd/runtime/average.py) -- job 0 the whole parameter arena, the others the ~100 small BN statistics tensors.
  *   LOANS_AVG_UPDATE:  dst += omd * (src - dst)      (omd = 1 - decay; exactly nothing where dst == src)

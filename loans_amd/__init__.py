@@ -2,12 +2,12 @@
 
 Public surface mirrors the reference's (Bartzi/loans) for this path:
 ``SheepLocalizer``, ``ResnetAssessor``, ``SheepAssessor`` (alias ``SheepUpdater``),
-``rotation_dropout``, ``DirectionLossCalculator``, ``OutOfImageLossCalculator``, ``Adam``; ``Classifier``, ``MomentumSGD``, ``LARS``, ``LAMB`` and
-``WeightAverage`` for the ImageNet pre-training arm (``SheepLocalizer(train_imagenet=True)``).
+``rotation_dropout``, ``DirectionLossCalculator``, ``OutOfImageLossCalculator``, ``Adam``; ``Classifier``, ``MomentumSGD``, ``LARS``, ``LAMB``,
+``GradientClipping`` and ``WeightAverage`` for the ImageNet pre-training arm (``SheepLocalizer(train_imagenet=True)``).
 """
 from .runtime.core import (Variable, Function, Link, Chain, ChainList, Parameter, config, using_config,  # noqa: F401
                            report, reporter, save_npz, load_npz)
-from .runtime.optimizers import Adam, MomentumSGD, LARS, LAMB  # noqa: F401
+from .runtime.optimizers import Adam, MomentumSGD, LARS, LAMB, GradientClipping  # noqa: F401
 from .runtime.average import WeightAverage, ema_decay_at  # noqa: F401
 from .runtime.checkpoint import save_checkpoint, load_checkpoint  # noqa: F401
 from .sheep.sheep_localizer import SheepLocalizer, Resnet50SheepLocalizer  # noqa: F401

@@ -2902,6 +2902,38 @@ def lamb_update(p, m, v, lr, c1, c2, eps, weight_decay_rate, table):
           'loans_lamb_update_f32')
 
 
+class GradClipState:
+    """What ``grad_norm`` / ``grad_clip_apply`` need beside a gradient buffer of up to ``numel`` floats, allocated here, once: the
+    workspace of the per-unit fp64 partial sums and the device record ``[N, k]`` (two floats: the norm before clipping, rounded to
+    fp32 once, and the coefficient the buffer is multiplied by).  No device allocation happens in a step."""
+
+    def __init__(self, numel, device):
+        self.numel = int(numel)
+        nbytes = _lib.load().loans_grad_clip_workspace_bytes(self.numel)
+        if nbytes < 0:
+            check(int(nbytes), 'loans_grad_clip_workspace_bytes')
+        self.workspace = torch.empty(nbytes // 8, device=device, dtype=torch.float64)
+        self.record = torch.tensor([0.0, 1.0], dtype=torch.float32).to(device)
+
+
+def grad_norm(g, max_norm, state, grad_scale=1.0):
+    """``N = |grad_scale| * |g|_2`` (squares and sums in float64, a fixed order) and ``k = c / N if N is finite and N > c else 1``
+    with ``c = max_norm > 0`` (``inf``: measure only) into ``state.record``: two launches on the current stream, nothing comes back
+    to the host"""
+    if CLASS_COUNT is not None: _acct('optimizer', 0, _nbytes(g), _nbytes(state.record))
+    if g.numel() > state.numel:
+        raise ValueError('a GradClipState for %d floats was given %d' % (state.numel, g.numel()))
+    check(_lib.load().loans_grad_norm_f32(_ptr(g), g.numel(), grad_scale, max_norm, _ptr(state.workspace), state.workspace.numel() * 8,
+                                          _ptr(state.record), _stream()), 'loans_grad_norm_f32')
+
+
+def grad_clip_apply(g, state):
+    """``g *= k`` in place with the ``k`` that ``grad_norm`` left in ``state.record``, one fp32 product per element; a launch that
+    returns before it touches ``g`` where ``k == 1``"""
+    if CLASS_COUNT is not None: _acct('optimizer', 0, _nbytes(g), _nbytes(g))
+    check(_lib.load().loans_grad_clip_apply_f32(_ptr(g), g.numel(), _ptr(state.record), _stream()), 'loans_grad_clip_apply_f32')
+
+
 class AverageJobs:
     """The job table of ``average_jobs``: pairs of float32 device tensors ``(dst, src)`` of equal size, kept alive here; the
     table is built and uploaded once."""

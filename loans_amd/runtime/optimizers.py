@@ -478,7 +478,7 @@ class LAMB(GradientMethod):
     ``c1`` and ``c2`` are formed in double here and rounded to fp32 once; ``W``, ``U`` and ``r`` are formed in double from fp64 sums
     of the squares of the fp32 values, and ``r`` is rounded to fp32 once.  Parameters whose Chainer shape has at most one dimension
     -- BN ``gamma`` / ``beta``, biases -- never adapt (r = 1) and, with ``decay_exempt_1d=True``, take no decay, as for ``LARS``.
-    There is no clamp on ``W`` and no gradient clipping.  Wherever a segment adapts, ``|p' - p|_2 = lr |p|_2`` at every step,
+    There is no clamp on ``W``; clipping by the global norm is the ``GradientClipping`` hook.  Wherever a segment adapts, ``|p' - p|_2 = lr |p|_2`` at every step,
     whatever the gradient.  ``v = g^2`` overflows fp32 beyond ``|g gs|`` ~ 1e19: Adam's own limit.
 
     Three launches per step (``ops.lamb_moments``, ``ops.lamb_ratios``, ``ops.lamb_update``; ``csrc/lamb.hip``); the bias correction
@@ -521,3 +521,64 @@ class LAMB(GradientMethod):
                          table, grad_scale)
         ops.lamb_ratios(table)
         ops.lamb_update(arena.data[:n], m[:n], v[:n], lr, c1, c2, hp.eps, hp.weight_decay_rate, table)
+
+
+class GradientClipping:
+    """``chainer.optimizer_hooks.GradientClipping(threshold)``: clip the gradient by its global L2 norm, on the device.  Used as
+    ``optimizer.add_hook(loans_amd.GradientClipping(1.0))`` with any ``GradientMethod`` (``Adam``, ``MomentumSGD`` in both forms,
+    ``LARS``, ``LAMB``): ``update()`` calls it once per step, after the data-parallel all-reduce and before the parameters move.
+    For the first ``n = arena.active_numel`` floats ``g`` of the gradient arena, ``gs = optimizer.grad_scale`` (1 / world size where
+    the arena holds the sum over ranks) and the threshold ``c > 0``::
+
+        S    = sum g_i^2                      every g_i converted to double and squared (exact), summed in fp64 in a FIXED order
+        N    = |gs| * sqrt(S)                 in double: the norm of the gradient the optimiser will actually apply
+        k    = (N is finite and N > c) ? c / N : 1          in double, rounded to fp32 ONCE
+        g_i' = fl32(g_i * k)                  one fp32 product per element, in place -- skipped entirely when k == 1
+
+    ``N == c`` does not clip (Chainer's ``rate < 1``); an all-zero gradient gives ``N = 0``, ``k = 1`` and no division.  A non-finite
+    ``N`` -- a NaN or inf anywhere in ``g``, or a sum that overflows -- gives ``k = 1``: the gradient is left bit for bit as it was and
+    the record holds the non-finite ``N``, so that a log shows it.  This is a deliberate departure from Chainer, which would write
+    ``0 * inf`` over the whole gradient.  ``threshold=inf`` is legal and means "measure only": the norm is recorded, nothing is scaled.
+
+    Two launches for the norm (``ops.grad_norm``), a third for the product (``ops.grad_clip_apply``; not issued for ``inf``, and
+    returning before it touches ``g`` where ``k == 1``); ``N`` (rounded to fp32 once) and ``k`` stay in a two-float device record,
+    nothing returns to the host.  The gradients ``update()`` zeroes behind ``n`` afterwards are zero either way.  The hook holds no
+    training state -- its workspace is allocated once per arena, nothing goes into a checkpoint.  Hooks run on the host, so
+    ``update()`` refuses them inside a captured step: clipping in a hipGraph step is not built.
+
+    ``last_norm()`` and ``last_coefficient()`` read the record.  They synchronise with the device: for diagnostics, tests and a log
+    entry's synchronisation point, not for every step of a training loop."""
+    name = 'GradientClipping'
+
+    def __init__(self, threshold):
+        threshold = float(threshold)
+        if not threshold > 0.0:
+            raise ValueError('the threshold of GradientClipping must be positive (inf: measure only), got %r' % threshold)
+        self.threshold = threshold
+        self._clip = None       # (arena, ops.GradClipState)
+
+    def __call__(self, opt):
+        arena = opt.target.arena
+        n = arena.active_numel
+        if n <= 0:
+            return
+        if self._clip is None or self._clip[0] is not arena:
+            self._clip = (arena, ops.GradClipState(arena.numel, arena.device))
+        state = self._clip[1]
+        g = arena.grad[:n]
+        ops.grad_norm(g, self.threshold, state, getattr(opt, 'grad_scale', 1.0))
+        if self.threshold != math.inf:
+            ops.grad_clip_apply(g, state)
+
+    def _record(self):
+        if self._clip is None:
+            raise RuntimeError('no step has been taken yet')
+        return self._clip[1].record.detach().cpu().numpy()
+
+    def last_norm(self):
+        """``N`` of the last step, before clipping, as the device record holds it (fp32).  Synchronises with the device."""
+        return float(self._record()[0])
+
+    def last_coefficient(self):
+        """``k`` of the last step (1.0: nothing was scaled).  Synchronises with the device."""
+        return float(self._record()[1])

@@ -110,7 +110,15 @@ augmentation options above were built for:
 
     python train_imagenet.py train.tsv val.tsv --gpus 8 -b 256 --dtype bf16 --optimizer lamb --lr 5e-3 --weight-decay 0.02 \
         --no-decay-1d --lr-schedule cosine --lr-min 1e-6 --warmup-epochs 5 --num-epoch 300 --augment rrc --mixup-alpha 0.2 \
-        --cutmix-alpha 1.0 --color-jitter 0.4 0.4 0.4 --random-erase-prob 0.25 --ema-decay 0.9999
+        --cutmix-alpha 1.0 --color-jitter 0.4 0.4 0.4 --random-erase-prob 0.25 --ema-decay 0.9999 --clip-grad-norm 1.0
+
+``--clip-grad-norm C`` (``C > 0``) clips the gradient by its global L2 norm before every step, with every ``--optimizer``
+(``loans_amd.GradientClipping``, added behind the data-parallel exchange): where the norm ``N`` of the gradient the optimiser is about
+to apply exceeds ``C`` the whole gradient is multiplied by ``C / N``, on the device, with nothing returning to the host.  Every log
+entry then holds ``grad_norm``, the norm before clipping of the step the entry belongs to (read at the entry's synchronisation
+point; under ``--gpus N`` it is the exchanged gradient's, the same on every rank), and the logged arguments hold
+``clip_grad_norm``.  ``inf`` logs the norm and clips nothing.  A non-finite norm is logged and the gradient left as it is; the step
+is not skipped.  Without the option no hook is added and the log holds what it always held.  The threshold may change on resume.
 
 ``--checkpoint-interval N`` writes a full-state checkpoint, ``checkpoint_<iteration>.npz`` in the log directory, after every
 N-th iteration and after the last one (default 0: none; ``--checkpoint-keep K``, default 2, keeps the newest K): the model with
@@ -124,7 +132,7 @@ resume (one error lists every one that differs): the architecture, ``--dtype``, 
 ``--rrc-*`` / ``--val-crop-pct`` / ``--augment-seed``, ``--mixup-alpha`` / ``--cutmix-alpha`` / ``--mix-*``, ``--color-jitter`` / ``--lighting-std`` / ``--random-erase-*`` / ``--photo-seed``, ``--ema-decay`` (a checkpoint from
 before these options existed ran at their defaults), ``--seed``.  Taken from the new command line (each one that differs is
 printed once): ``--num-epoch``, ``--iterations``, the log, snapshot and checkpoint intervals, ``--loader-threads``, the frame
-cache options, ``--lr``, ``--weight-decay``, ``--momentum``, ``--lr-drop-*``, ``--lr-schedule``, ``--lr-min``, ``--no-decay-1d``, ``--lars-eta``, ``--lars-eps``, ``--lamb-beta1``, ``--lamb-beta2``, ``--lamb-eps``, ``--warmup-*``, ``--label-smoothing``, ``--topk``.  The
+cache options, ``--lr``, ``--weight-decay``, ``--momentum``, ``--lr-drop-*``, ``--lr-schedule``, ``--lr-min``, ``--no-decay-1d``, ``--lars-eta``, ``--lars-eps``, ``--lamb-beta1``, ``--lamb-beta2``, ``--lamb-eps``, ``--clip-grad-norm``, ``--warmup-*``, ``--label-smoothing``, ``--topk``.  The
 frame caches start empty after a resume and refill during the first epoch.
 
     python train_imagenet.py train.tsv val.tsv -b 256 --optimizer sgd --lr 0.1 --lr-drop-epochs 30 60 90 --checkpoint-interval 500
@@ -251,6 +259,10 @@ class Arguments(argparse.Namespace):
     _LARS = ('lars_eta', 'lars_eps')
     _LAMB = ('lamb_beta1', 'lamb_beta2', 'lamb_eps')
 
+    # --clip-grad-norm (loans_amd/runtime/optimizers.py: GradientClipping); None: off, no hook, nothing logged
+    clip_grad_norm = None
+    _CLIP = ('clip_grad_norm',)
+
 
 def parse_args(argv=None):
     parser = argparse.ArgumentParser(description="ImageNet pre-training of a localizer backbone (MI355X-native)")
@@ -325,6 +337,8 @@ def parse_args(argv=None):
     parser.add_argument("--lamb-beta1", type=float, default=argparse.SUPPRESS, help="with --optimizer lamb: decay of the first moment (default 0.9)")
     parser.add_argument("--lamb-beta2", type=float, default=argparse.SUPPRESS, help="with --optimizer lamb: decay of the second moment (default 0.999)")
     parser.add_argument("--lamb-eps", type=float, default=argparse.SUPPRESS, help="with --optimizer lamb: added to the root of the second moment (default 1e-6)")
+    # gradient clipping
+    parser.add_argument("--clip-grad-norm", type=float, default=argparse.SUPPRESS, metavar='C', help="clip the gradient to the global L2 norm C > 0 before every step and log its norm as grad_norm; inf: log the norm only (default: off)")
     checkpoint.add_arguments(parser, argparse.SUPPRESS)
     args = parser.parse_args(argv, namespace=Arguments())
     try:
@@ -334,10 +348,11 @@ def parse_args(argv=None):
         check_average_arguments(args)
         check_lars_arguments(args)
         check_lamb_arguments(args)
+        check_clip_arguments(args)
         if args.resume is not None:
             check_average_resume(args)
             world = os.environ.get('WORLD_SIZE')        # a rank under a launcher: the group's size, whatever --gpus says
-            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS_WITH_LAMB)
+            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS_WITH_CLIP)
     except ValueError as e:
         parser.error(str(e))
     return args
@@ -422,6 +437,14 @@ def check_lamb_arguments(args):
         raise ValueError('--lamb-beta1 / --lamb-beta2 / --lamb-eps belong to --optimizer lamb')
 
 
+def check_clip_arguments(args):
+    """ValueError for a --clip-grad-norm that is no threshold"""
+    c = args.clip_grad_norm
+    if c is not None and not c > 0:
+        raise ValueError('--clip-grad-norm is the largest gradient norm a step is taken with: it must be positive, or inf to log the '
+                         'norm without clipping, got %r' % c)
+
+
 AVERAGE_RESUME = {False: '--resume: the checkpoint was written without --ema-decay and holds no weight average: resume it without the option',
                   True: '--resume: the checkpoint was written with --ema-decay %g and holds a weight average: resume it with the option'}
 
@@ -444,9 +467,12 @@ RESUME_DEFAULTS_WITH_LARS = dict(ALL_RESUME_DEFAULTS, **RESUME_DEFAULTS_LARS)
 # ... and for the photometric options
 RESUME_DEFAULTS_PHOTO = {name: getattr(Arguments, name) for name in Arguments._PHOTO}
 RESUME_DEFAULTS_WITH_PHOTO = dict(RESUME_DEFAULTS_WITH_LARS, **RESUME_DEFAULTS_PHOTO)
-# ... and for --lamb-beta1 / --lamb-beta2 / --lamb-eps; this is the table --resume uses
+# ... and for --lamb-beta1 / --lamb-beta2 / --lamb-eps
 RESUME_DEFAULTS_LAMB = {name: getattr(Arguments, name) for name in Arguments._LAMB}
 RESUME_DEFAULTS_WITH_LAMB = dict(RESUME_DEFAULTS_WITH_PHOTO, **RESUME_DEFAULTS_LAMB)
+# ... and for --clip-grad-norm; this is the table --resume uses
+RESUME_DEFAULTS_CLIP = {name: getattr(Arguments, name) for name in Arguments._CLIP}
+RESUME_DEFAULTS_WITH_CLIP = dict(RESUME_DEFAULTS_WITH_LAMB, **RESUME_DEFAULTS_CLIP)
 
 
 def cache_budgets(total_bytes, n_train, n_validation):
@@ -573,6 +599,7 @@ def run(args, log=print):
     check_average_arguments(args)
     check_lars_arguments(args)
     check_lamb_arguments(args)
+    check_clip_arguments(args)
     chief = comm.rank == 0                     # prints, logs and writes snapshots
 
     # --augment rrc: the iterators hand out (frames, labels) already resident on the device
@@ -641,7 +668,12 @@ def run(args, log=print):
         optimizer, rate_name = loans_amd.Adam(alpha=args.learning_rate, weight_decay_rate=args.weight_decay), 'alpha'
     optimizer.setup(model)
     parallel.create_multi_node_optimizer(optimizer, comm)
-    topk = 'accuracy_top%d' % model.topk if model.topk is not None else None
+    clipping = None
+    if args.clip_grad_norm is not None:
+        # behind the communicator: the hook sees the exchanged gradient, the same on every rank
+        clipping = loans_amd.GradientClipping(args.clip_grad_norm)
+        optimizer.add_hook(clipping)
+    topk ='accuracy_top%d' % model.topk if model.topk is not None else None
     train_keys = ('loss', 'accuracy') + ((topk,) if topk else ())
     updater = training.StandardUpdater(train_iter, optimizer, converter=train_converter, device=args.gpu, comm=comm)
     # every rank keeps its own average: the parameters agree on all ranks (built after bcast_data), the BN statistics are local
@@ -689,7 +721,7 @@ def run(args, log=print):
         # the run continues in the checkpoint's log directory: no new <time>_<name>
         check_average_resume(args)
         resumed, changed = checkpoint.resolve_resume(args, RESUME_FIXED, log if chief else (lambda line: None), world=comm.size,
-                                                     defaults=RESUME_DEFAULTS_WITH_LAMB)
+                                                     defaults=RESUME_DEFAULTS_WITH_CLIP)
         args.log_dir = os.path.dirname(os.path.abspath(args.resume))
         for line in changed if chief else ():
             log(line)
@@ -710,6 +742,8 @@ def run(args, log=print):
         if argument in Arguments._LARS and args.optimizer != 'lars':
             continue        # a run with another optimiser logs what it always logged
         if argument in Arguments._LAMB and args.optimizer != 'lamb':
+            continue
+        if argument in Arguments._CLIP and clipping is None:
             continue
         data_to_log[argument] = getattr(args, argument)
     log_entries = []
@@ -774,6 +808,10 @@ def run(args, log=print):
             else:
                 entry.update({k: float(obs[k]) for k in train_keys})
             entry['lr'] = lr                    # the rate this iteration was stepped with
+            if clipping is not None:
+                # the norm before clipping of this iteration's step, from the device record: local to the rank -- every rank
+                # holds the same exchanged gradient --, so no collective and LOCK STEP holds
+                entry['grad_norm'] = clipping.last_norm()
             if validate is not None:
                 keep = {k: obs[k] for k in train_keys}
                 entry.update({k: v for k, v in validate().items() if k.startswith('validation/')})
