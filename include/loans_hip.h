@@ -587,6 +587,17 @@ int loans_softmax_xent_ls_fwd_f32(const float* z, const int32_t* t, float* gz, f
 int loans_softmax_xent_mix_fwd_f32(const float* z, const int32_t* ta, const int32_t* tb, float lam, float oml,
                                    float* gz, float* row_loss, float* row_hit, float* row_hitk, float* out /* [3] */,
                                    int32_t B, int32_t N, double eps, int32_t k, void* stream);
+/* Per-class sigmoid binary cross-entropy against the same two-label target q = (1 - eps) w + eps / N, made 0 / 1 by the strict
+ * comparison q > thresh where thresh >= 0 (a negative thresh: no threshold).  With e = exp(-|z|):
+ * row_loss = sum_i max(z_i, 0) - z_i q_i + log1p(e_i) (finite for every finite z), gz = (sigmoid(z) - q) / denom with
+ * denom = count * N (the mean over classes, torch's binary_cross_entropy_with_logits) or count (sum_classes != 0: the sum over
+ * classes, the mean over rows), rounded to fp32 once.  out[0] = sum(row_loss) / denom; rows that count, row_hit, row_hitk,
+ * out[1] and out[2] as for loans_softmax_xent_mix_fwd_f32.  The weights (1, 0) / (0, 1) are the one-label loss on ta / on tb: the
+ * label of weight zero is not read and does not decide whether a row counts; tb == NULL is one label with the weights (1, 0).
+ * No atomics: two runs give the same bits.  Limits as above; LOANS_EINVAL also for a non-finite weight, thresh >= 1 or NaN. */
+int loans_sigmoid_bce_fwd_f32(const float* z, const int32_t* ta, const int32_t* tb, float lam, float oml,
+                              float* gz, float* row_loss, float* row_hit, float* row_hitk, float* out /* [3] */,
+                              int32_t B, int32_t N, double eps, int32_t k, float thresh, int32_t sum_classes, void* stream);
 /* Evaluation: the plain loss (eps = 0), the top-1 and the top-k hit of every row as defined above, summed into running totals;
  * no gradient is written.  rows: 3 * B floats of scratch (row loss, hit, top-k hit).  acc[5], doubles, read-modify-write:
  * acc[0] += sum of row losses, acc[1] += top-1 hits, acc[2] += top-k hits, acc[3] += rows not ignored, acc[4] += B.  The five sums

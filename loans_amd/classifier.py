@@ -2,12 +2,14 @@
 ``softmax_cross_entropy`` and ``accuracy`` from one pass over the logits, reports both under ``loss`` / ``accuracy`` and returns
 the loss.  The ImageNet pre-training arm of the reference (train_imagenet=True localizers) is trained through it.
 ``label_smoothing`` smooths the training loss (``config.train``; the validation loss stays the plain one, comparable between
-runs), ``topk=k`` also reports ``accuracy_top<k>``; with neither, the loss function and the reported keys are the plain ones."""
+runs), ``topk=k`` also reports ``accuracy_top<k>``; with neither, the loss function and the reported keys are the plain ones.
+``loss='bce'`` trains (``config.train``) with the per-class sigmoid binary cross-entropy on the same smoothed / mixed target,
+under the same keys; its validation loss is the plain softmax cross-entropy too, by the same rule."""
 import torch
 
 from . import ops
-from .functions.ops_small import (_as_labels, softmax_cross_entropy_mixed, softmax_cross_entropy_with_accuracy,
-                                  softmax_cross_entropy_with_topk_accuracy)
+from .functions.ops_small import (_as_labels, sigmoid_binary_cross_entropy, softmax_cross_entropy_mixed,
+                                  softmax_cross_entropy_with_accuracy, softmax_cross_entropy_with_topk_accuracy)
 from .mixed_labels import MixedLabels
 from .runtime.core import Chain, Variable, config, report, using_config
 
@@ -16,7 +18,8 @@ class Classifier(Chain):
 
     compute_accuracy = True
 
-    def __init__(self, predictor, label_key=-1, label_smoothing=0.0, topk=None):
+    def __init__(self, predictor, label_key=-1, label_smoothing=0.0, topk=None, loss='softmax', bce_target_threshold=None,
+                 bce_sum=False):
         super().__init__()
         if label_key != -1:
             raise ValueError('the label is the last argument (label_key=-1)')
@@ -24,7 +27,14 @@ class Classifier(Chain):
             raise ValueError('label_smoothing must be in [0, 1)')
         if topk is not None and topk < 1:
             raise ValueError('topk must be at least 1')
+        if loss not in ('softmax', 'bce'):
+            raise ValueError('loss must be \'softmax\' or \'bce\', got %r' % (loss,))
+        if bce_target_threshold is not None and not 0.0 <= bce_target_threshold < 1.0:
+            raise ValueError('bce_target_threshold must be in [0, 1)')
+        if loss != 'bce' and (bce_target_threshold is not None or bce_sum):
+            raise ValueError('bce_target_threshold and bce_sum belong to loss=\'bce\'')
         self.label_smoothing, self.topk = label_smoothing, topk
+        self.loss_name, self.bce_target_threshold, self.bce_sum = loss, bce_target_threshold, bool(bce_sum)
         with self.init_scope():
             self.predictor = predictor
         self.y = self.loss = self.accuracy = self.accuracy_topk = None
@@ -57,6 +67,13 @@ class Classifier(Chain):
     def __call__(self, *args):
         *xs, t = args
         self._predict(*xs)
+        if self.loss_name == 'bce' and config.train:    # plain or mixed labels; in test mode the softmax paths below, as they are
+            self.loss, self.accuracy, self.accuracy_topk = sigmoid_binary_cross_entropy(
+                self.y, t, self.label_smoothing, self.topk or 1, self.bce_target_threshold, self.bce_sum)
+            report({'loss': self.loss, 'accuracy': self.accuracy}, self)
+            if self.topk is not None:
+                report({'accuracy_top%d' % self.topk: self.accuracy_topk}, self)
+            return self.loss
         if isinstance(t, MixedLabels):          # a mixup / CutMix batch: the same keys, the accuracies against the dominant label
             self.loss, self.accuracy, self.accuracy_topk = softmax_cross_entropy_mixed(
                 self.y, t, self.label_smoothing if config.train else 0.0, self.topk or 1)

@@ -368,6 +368,89 @@ __global__ __launch_bounds__(256) void softmax_xent_mix_reduce_kernel(const floa
     if (tid == 0) { out[0] = L / (float)count; out[1] = A / (float)B; out[2] = AK / (float)B; }
 }
 
+// Per-class sigmoid binary cross-entropy against the two-label target (loans_sigmoid_bce_fwd_f32: the loss of timm's A1 - A3
+// procedures).  The target is the mix kernel's, q = (1 - eps) w + eps / N with w_i = lam [i == ta] + oml [i == tb], made 0 / 1 by
+// the strict comparison q > thresh where a threshold is given (thresh < 0: none).  Per element, with e = expf(-|z|) in (0, 1]:
+//   l = max(z, 0) - z q + log1pf(e)                    never exp(z) itself: finite for every finite z
+//   s = z >= 0 ? 1 / (1 + e) : e / (1 + e)             the sigmoid
+//   row_loss = sum_i l_i,   gz = (s - q) / denom,   denom = count * N (the mean over classes) or count (sum_classes)
+// A row counts when BOTH labels lie in [0, N); hit and rank are those of the softmax kernels (the sigmoid is monotone), against
+// the dominant label.  The launcher hands a one-label call the same array twice, so the weights (1, 0) and (0, 1) need no code
+// of their own: w is lam + oml = 1 on the one label, and the array of weight zero is never seen.  denom is one fp32 rounding of
+// the integer count * N (at most 2^29), formed the same way in the reduce kernel.
+struct SigmoidBce { float lam, oml, omeps, q_off, thresh; int k, sum_classes; };
+
+__device__ __forceinline__ float bce_denom(int count, int N, int sum_classes) { return (float)(sum_classes ? count : count * N); }
+
+__global__ __launch_bounds__(256) void sigmoid_bce_rows_kernel(const float* __restrict__ z, const int* __restrict__ ta,
+                                                               const int* __restrict__ tb, float* __restrict__ gz,
+                                                               float* __restrict__ row_loss, float* __restrict__ row_hit,
+                                                               float* __restrict__ row_hitk, int B, int N, SigmoidBce bc) {
+    extern __shared__ __attribute__((aligned(16))) float row[];
+    __shared__ float shf[4];
+    __shared__ int shi[4];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const float* zr = z + (int64_t)b * N;
+    float* gr = gz + (int64_t)b * N;
+
+    int valid = 0;
+    for (int i = tid; i < B; i += 256) valid += ((unsigned)ta[i] < (unsigned)N) & ((unsigned)tb[i] < (unsigned)N);
+    const int count = max(block_count_256(valid, shi), 1);
+
+    float m;
+    int am;
+    row_stage_argmax(zr, row, N, shf, shi, m, am);
+
+    const int la = ta[b], lb = tb[b];
+    if ((unsigned)la >= (unsigned)N || (unsigned)lb >= (unsigned)N) {       // ignored row (uniform per block)
+        for (int i = tid; i < N; i += 256) gr[i] = 0.f;
+        if (tid == 0) { row_loss[b] = 0.f; row_hit[b] = 0.f; row_hitk[b] = 0.f; }
+        return;
+    }
+    const int label = bc.lam >= bc.oml ? la : lb;
+    if (tid == 0) row_hit[b] = (am == label) ? 1.f : 0.f;
+    const int rank = row_rank(row, N, label, row[label], shi);
+    if (tid == 0) row_hitk[b] = (rank < bc.k) ? 1.f : 0.f;
+
+    const float denom = bce_denom(count, N, bc.sum_classes);
+    float ls = 0.f;
+    for (int i = tid; i < N; i += 256) {
+        const float v = row[i];
+        const float w = (i == la ? bc.lam : 0.f) + (i == lb ? bc.oml : 0.f);
+        float q = bc.omeps * w + bc.q_off;
+        if (bc.thresh >= 0.f) q = q > bc.thresh ? 1.f : 0.f;
+        const float e = expf(-fabsf(v));
+        ls += (fmaxf(v, 0.f) - v * q) + log1pf(e);
+        const float s = (v >= 0.f ? 1.f : e) / (1.f + e);
+        gr[i] = (s - q) / denom;
+    }
+    const float L = block_sum_256(ls, shf);
+    if (tid == 0) row_loss[b] = L;
+}
+
+// out[0] = (sum_b row_loss[b]) / denom ; out[1] = (sum_b row_hit[b]) / B ; out[2] = (sum_b row_hitk[b]) / B
+__global__ __launch_bounds__(256) void sigmoid_bce_reduce_kernel(const float* __restrict__ row_loss, const float* __restrict__ row_hit,
+                                                                 const float* __restrict__ row_hitk, const int* __restrict__ ta,
+                                                                 const int* __restrict__ tb, float* __restrict__ out, int B, int N,
+                                                                 int sum_classes) {
+    __shared__ float shf[4];
+    __shared__ int shi[4];
+    const int tid = threadIdx.x;
+    int valid = 0;
+    float l = 0.f, a = 0.f, ak = 0.f;
+    for (int i = tid; i < B; i += 256) {
+        valid += ((unsigned)ta[i] < (unsigned)N) & ((unsigned)tb[i] < (unsigned)N);
+        l += row_loss[i];
+        a += row_hit[i];
+        ak += row_hitk[i];
+    }
+    const int count = max(block_count_256(valid, shi), 1);
+    const float L = block_sum_256(l, shf);
+    const float A = block_sum_256(a, shf);
+    const float AK = block_sum_256(ak, shf);
+    if (tid == 0) { out[0] = L / bce_denom(count, N, sum_classes); out[1] = A / (float)B; out[2] = AK / (float)B; }
+}
+
 // Evaluation (loans_softmax_xent_eval_f32): the plain loss, the top-1 and the top-k hit of every row -- the eps == 0 expressions
 // of softmax_xent_ls_rows_kernel on the same row code -- and no gradient.  rows: [0, B) loss, [B, 2B) hit, [2B, 3B) top-k hit.
 __global__ __launch_bounds__(256) void softmax_xent_eval_rows_kernel(const float* __restrict__ z, const int* __restrict__ t,
@@ -529,6 +612,30 @@ extern "C" int loans_softmax_xent_mix_fwd_f32(const float* z, const int32_t* ta,
                        row_hit, row_hitk, B, N, mx);
     LOANS_LAUNCH_CHECK();
     hipLaunchKernelGGL(softmax_xent_mix_reduce_kernel, dim3(1), dim3(256), 0, st, row_loss, row_hit, row_hitk, ta, tb, out, B, N);
+    LOANS_LAUNCH_CHECK();
+    return LOANS_OK;
+}
+
+extern "C" int loans_sigmoid_bce_fwd_f32(const float* z, const int32_t* ta, const int32_t* tb, float lam, float oml, float* gz,
+                                         float* row_loss, float* row_hit, float* row_hitk, float* out, int32_t B, int32_t N,
+                                         double eps, int32_t k, float thresh, int32_t sum_classes, void* stream) {
+    if (!tb) { tb = ta; lam = 1.f; oml = 0.f; }         // one label
+    if (!z || !ta || !gz || !row_loss || !row_hit || !row_hitk || !out || B <= 0 || N <= 0) return LOANS_EINVAL;
+    if (!(eps >= 0.0 && eps < 1.0) || k < 1 || !__builtin_isfinite(lam) || !__builtin_isfinite(oml)) return LOANS_EINVAL;
+    if (!(thresh < 1.f)) return LOANS_EINVAL;           // (a NaN too)
+    if (N > XENT_MAX_N || B > XENT_MAX_B) return LOANS_ERANGE;
+    // one label per row: the array that carries the whole weight in both places, so the other one is not read
+    if (lam == 1.f && oml == 0.f) tb = ta;
+    if (lam == 0.f && oml == 1.f) ta = tb;
+    SigmoidBce bc;
+    bc.lam = lam; bc.oml = oml; bc.omeps = (float)(1.0 - eps); bc.q_off = (float)(eps / N);
+    bc.thresh = thresh < 0.f ? -1.f : thresh; bc.k = k; bc.sum_classes = sum_classes != 0;
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(sigmoid_bce_rows_kernel, dim3(B), dim3(256), (size_t)N * sizeof(float), st, z, ta, tb, gz, row_loss, row_hit,
+                       row_hitk, B, N, bc);
+    LOANS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sigmoid_bce_reduce_kernel, dim3(1), dim3(256), 0, st, row_loss, row_hit, row_hitk, ta, tb, out, B, N,
+                       bc.sum_classes);
     LOANS_LAUNCH_CHECK();
     return LOANS_OK;
 }

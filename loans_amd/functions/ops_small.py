@@ -6,6 +6,7 @@ the reference calls: ``_global_average_pooling_2d`` (sheep_localizer.py:58),
 import torch
 
 from .. import ops
+from ..mixed_labels import MixedLabels
 from ..runtime.core import Function, Parameter, Variable, using_config
 
 
@@ -177,6 +178,25 @@ class SoftmaxCrossEntropyMixed(SoftmaxCrossEntropyTopK):
         return out[0], out[1], out[2]
 
 
+class SigmoidBCE(SoftmaxCrossEntropyTopK):
+    """The per-class sigmoid binary cross-entropy against the same target -- label-smoothed, one label or the two of a mixed batch,
+    made 0 / 1 by ``target > target_threshold`` where a threshold is given -- from one pass over the logits: inputs (x, t_a) or
+    (x, t_a, t_b), outputs (loss, accuracy, accuracy_topk).  The loss is the mean over classes and rows (``sum_classes``: the sum
+    over classes, the mean over rows); the accuracies are the softmax ones, the sigmoid being monotone.  The backward is the
+    parent's: the forward leaves ``(sigmoid - target) / denominator`` behind."""
+
+    def __init__(self, lam32, oml32, label_smoothing, topk, target_threshold=None, sum_classes=False):
+        super().__init__(label_smoothing, topk)
+        self.lam32, self.oml32 = float(lam32), float(oml32)
+        self.target_threshold, self.sum_classes = target_threshold, bool(sum_classes)
+
+    def forward(self, inputs):
+        x, ta, tb = (tuple(a.contiguous() for a in inputs) + (None,))[:3]
+        out, self.gz, _, _, _ = ops.sigmoid_bce_fwd(x, ta, tb, self.lam32, self.oml32, self.label_smoothing, self.topk,
+                                                    self.target_threshold, self.sum_classes)
+        return out[0], out[1], out[2]
+
+
 def _as_labels(x, t):
     import numpy as np
     if isinstance(t, Variable):
@@ -205,6 +225,20 @@ def softmax_cross_entropy_mixed(x, labels, label_smoothing=0.0, topk=1):
     batch.  The accuracies are against each row's dominant label."""
     return SoftmaxCrossEntropyMixed(labels.lam32, labels.oml32, label_smoothing, topk)(
         x, _as_labels(x, labels.t_a.reshape(-1)), _as_labels(x, labels.t_b.reshape(-1)))
+
+
+def sigmoid_binary_cross_entropy(x, t, label_smoothing=0.0, topk=1, target_threshold=None, sum_classes=False):
+    """(loss, accuracy, accuracy_topk) of the logits ``x`` under the per-class sigmoid binary cross-entropy (timm's
+    ``BinaryCrossEntropy``): ``t`` is a label array or a ``MixedLabels``, the target the label-smoothed one of the softmax losses,
+    made 0 / 1 by ``target > target_threshold`` where a threshold is given.  The loss is torch's
+    ``binary_cross_entropy_with_logits`` -- the mean over classes and over the rows with a label -- or, with ``sum_classes``, its
+    sum over the classes.  The accuracies are against each row's (dominant) label."""
+    if target_threshold is not None and not 0.0 <= target_threshold < 1.0:
+        raise ValueError('target_threshold must be in [0, 1)')
+    if isinstance(t, MixedLabels):
+        return SigmoidBCE(t.lam32, t.oml32, label_smoothing, topk, target_threshold, sum_classes)(
+            x, _as_labels(x, t.t_a.reshape(-1)), _as_labels(x, t.t_b.reshape(-1)))
+    return SigmoidBCE(1.0, 0.0, label_smoothing, topk, target_threshold, sum_classes)(x, _as_labels(x, t))
 
 
 def softmax_cross_entropy(x, t, ignore_label=-1):

@@ -2491,6 +2491,29 @@ def softmax_xent_mix_fwd(z, ta, tb, lam, oml, eps, k):
     return out, gz, row_loss, row_hit, row_hitk
 
 
+def sigmoid_bce_fwd(z, ta, tb, lam, oml, eps, k, thresh=None, sum_classes=False):
+    """the per-class sigmoid binary cross-entropy against softmax_xent_mix_fwd's target, made 0 / 1 by ``target > thresh`` where a
+    threshold is given -> (out, gz, row_loss, row_hit, row_hitk) as softmax_xent_mix_fwd returns them.  out[0] is the mean over
+    classes and rows that count (``sum_classes``: the sum over classes, the mean over rows); gz = (sigmoid - target) / that
+    denominator.  ``tb`` None: one label per row, the weights (1, 0).  No host synchronisation."""
+    assert z.dtype == torch.float32 and z.dim() == 2 and z.is_contiguous(), 'logits must be a contiguous (B, N) fp32 array'
+    for t in (ta,) if tb is None else (ta, tb):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == z.shape[0] and t.device == z.device, \
+            'labels must be int32, one per row, on the logits\' device'
+    B, N = z.shape
+    gz = _empty_like(z)
+    row_loss = _empty((B,), device=z.device, dtype=torch.float32)
+    row_hit = _empty((B,), device=z.device, dtype=torch.float32)
+    row_hitk = _empty((B,), device=z.device, dtype=torch.float32)
+    out = _empty((3,), device=z.device, dtype=torch.float32)
+    if CLASS_COUNT is not None: _acct('heads', 0, _nbytes(z), _nbytes(gz))
+    check(_lib.load().loans_sigmoid_bce_fwd_f32(_ptr(z), _ptr(ta), _ptr(tb), float(lam), float(oml), _ptr(gz), _ptr(row_loss),
+                                                _ptr(row_hit), _ptr(row_hitk), _ptr(out), B, N, float(eps), int(k),
+                                                -1.0 if thresh is None else float(thresh), int(bool(sum_classes)), _stream()),
+          'loans_sigmoid_bce_fwd_f32')
+    return out, gz, row_loss, row_hit, row_hitk
+
+
 def batch_mix(x, shift, lam, oml, box=(0, 0, 0, 0), out=None):
     """mixup / CutMix of the device batch x [B][C][H][W] fp32 with itself shifted by ``shift`` rows, one launch on the current
     stream: inside ``box`` = (y0, x0, y1, x1) row b is row (b - shift) % B, outside it lam * x[b] + oml * x[partner] (oml == 0: x[b]

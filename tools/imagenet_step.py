@@ -3,6 +3,8 @@
 say what the head costs: the flop counts of the three head GEMMs against the backbone's (``ops`` class accounting).
 
     python tools/imagenet_step.py -b 256 --steps 20 --warmup 5             (step time, ms: median / min / max)
+    python tools/imagenet_step.py -b 256 --resnet-50 --loss bce --bce-target-thresh 0.2
+        (the ResNet-50 localizer, the sigmoid binary cross-entropy on the label-smoothed target: tools/bce_bench.py)
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/imagenet_step.py -b 256 --steps 3 --warmup 2
         (per-kernel times: gemm_tile_kernel / colsum_ordered_kernel / softmax_xent_* are the head and the loss)
 """
@@ -28,13 +30,19 @@ def main(argv=None):
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--dtype', default='f32', choices=['f32', 'bf16'])
+    ap.add_argument('--resnet-50', action='store_true', help='the ResNet-50 localizer instead of the ResNet-18 one')
+    ap.add_argument('--loss', default='softmax', choices=['softmax', 'bce'])
+    ap.add_argument('--bce-target-thresh', type=float, default=None)
+    ap.add_argument('--label-smoothing', type=float, default=0.0)
     ap.add_argument('--out', default=None, help='also write the JSON result here')
     a = ap.parse_args(argv)
     assert torch.cuda.is_available(), 'this measurement needs a GPU'
     B, (H, W) = a.batch_size, a.image_size
 
     np.random.seed(0)
-    model = loans_amd.Classifier(loans_amd.SheepLocalizer((75, 75), train_imagenet=True))
+    localizer = loans_amd.Resnet50SheepLocalizer if a.resnet_50 else loans_amd.SheepLocalizer
+    options = dict(loss='bce', bce_target_threshold=a.bce_target_thresh) if a.loss == 'bce' else {}
+    model = loans_amd.Classifier(localizer((75, 75), train_imagenet=True), label_smoothing=a.label_smoothing, **options)
     if a.dtype == 'bf16':
         model.set_precision('bf16', 'bf16')
     x, t = synthetic.make_classification_set(0, min(B, 64), 1000, H, W)
@@ -55,8 +63,8 @@ def main(argv=None):
         e1.record()
         e1.synchronize()
         times.append(e0.elapsed_time(e1))
-    head_flop = 3 * 2 * B * 512 * 1000
-    res = {'what': 'imagenet_step', 'dtype': a.dtype, 'batch': B, 'image_size': [H, W], 'steps': a.steps,
+    head_flop = 3 * 2 * B * (2048 if a.resnet_50 else 512) * 1000
+    res = {'what': 'imagenet_step', 'dtype': a.dtype, 'localizer': localizer.__name__, 'loss_function': a.loss, 'batch': B, 'image_size': [H, W], 'steps': a.steps,
            'step_ms_median': float(np.median(times)), 'step_ms_min': float(min(times)), 'step_ms_max': float(max(times)),
            'images_per_s': B / (float(np.median(times)) * 1e-3), 'head_gflop': head_flop / 1e9,
            'loss': float(loans_amd.reporter.observation['loss']), 'accuracy': float(loans_amd.reporter.observation['accuracy'])}
@@ -65,6 +73,7 @@ def main(argv=None):
     if a.out:
         with open(a.out, 'w') as f:
             f.write(line + '\n')
+    return res
 
 
 if __name__ == '__main__':

@@ -120,6 +120,21 @@ point; under ``--gpus N`` it is the exchanged gradient's, the same on every rank
 ``clip_grad_norm``.  ``inf`` logs the norm and clips nothing.  A non-finite norm is logged and the gradient left as it is; the step
 is not skipped.  Without the option no hook is added and the log holds what it always held.  The threshold may change on resume.
 
+``--loss bce`` trains with the per-class sigmoid binary cross-entropy of "ResNet strikes back" (timm's A1 - A3 procedures) instead
+of the softmax cross-entropy, on the same target: the label-smoothed one-hot row, or the two-label row of a mixup / CutMix batch
+(csrc/classify.hip, ``loans_sigmoid_bce_fwd_f32``; one pass over the logits, like the softmax loss).  The logged ``loss`` is the mean
+over classes and rows, torch's ``binary_cross_entropy_with_logits``; ``--bce-sum`` sums over the classes instead (1000 times the
+value and the gradient on ImageNet).  ``--bce-target-thresh T`` (``0 <= T < 1``) makes the target 0 / 1 by ``target > T``: at 0.2 both
+labels of a mixed row whose weights exceed it become positives.  ``accuracy`` and the top-k accuracy are what they are for the
+softmax loss (the sigmoid is monotone), and the validation loss stays the plain softmax cross-entropy, comparable between runs of
+either loss.  The three options are logged where one of them is given -- ``--loss`` as ``loss_function``, an entry's ``loss`` being
+the training loss -- and may change on resume.
+
+    python train_imagenet.py train.tsv val.tsv --gpus 8 -b 256 --dtype bf16 --optimizer lamb --lr 5e-3 --weight-decay 0.02 \
+        --no-decay-1d --lr-schedule cosine --lr-min 1e-6 --warmup-epochs 5 --num-epoch 300 --augment rrc --mixup-alpha 0.2 \
+        --cutmix-alpha 1.0 --color-jitter 0.4 0.4 0.4 --random-erase-prob 0.25 --ema-decay 0.9999 --clip-grad-norm 1.0 \
+        --loss bce --bce-target-thresh 0.2
+
 ``--checkpoint-interval N`` writes a full-state checkpoint, ``checkpoint_<iteration>.npz`` in the log directory, after every
 N-th iteration and after the last one (default 0: none; ``--checkpoint-keep K``, default 2, keeps the newest K): the model with
 its BN statistics, the optimiser's buffers and step count, the training iterator as of the batch the step consumed (shuffle
@@ -132,7 +147,7 @@ resume (one error lists every one that differs): the architecture, ``--dtype``, 
 ``--rrc-*`` / ``--val-crop-pct`` / ``--augment-seed``, ``--mixup-alpha`` / ``--cutmix-alpha`` / ``--mix-*``, ``--color-jitter`` / ``--lighting-std`` / ``--random-erase-*`` / ``--photo-seed``, ``--ema-decay`` (a checkpoint from
 before these options existed ran at their defaults), ``--seed``.  Taken from the new command line (each one that differs is
 printed once): ``--num-epoch``, ``--iterations``, the log, snapshot and checkpoint intervals, ``--loader-threads``, the frame
-cache options, ``--lr``, ``--weight-decay``, ``--momentum``, ``--lr-drop-*``, ``--lr-schedule``, ``--lr-min``, ``--no-decay-1d``, ``--lars-eta``, ``--lars-eps``, ``--lamb-beta1``, ``--lamb-beta2``, ``--lamb-eps``, ``--clip-grad-norm``, ``--warmup-*``, ``--label-smoothing``, ``--topk``.  The
+cache options, ``--lr``, ``--weight-decay``, ``--momentum``, ``--lr-drop-*``, ``--lr-schedule``, ``--lr-min``, ``--no-decay-1d``, ``--lars-eta``, ``--lars-eps``, ``--lamb-beta1``, ``--lamb-beta2``, ``--lamb-eps``, ``--clip-grad-norm``, ``--warmup-*``, ``--label-smoothing``, ``--topk``, ``--loss``, ``--bce-target-thresh``, ``--bce-sum``.  The
 frame caches start empty after a resume and refill during the first epoch.
 
     python train_imagenet.py train.tsv val.tsv -b 256 --optimizer sgd --lr 0.1 --lr-drop-epochs 30 60 90 --checkpoint-interval 500
@@ -263,6 +278,12 @@ class Arguments(argparse.Namespace):
     clip_grad_norm = None
     _CLIP = ('clip_grad_norm',)
 
+    # --loss bce (loans_amd/classifier.py, csrc/classify.hip: loans_sigmoid_bce_fwd_f32); logged only where given
+    loss = 'softmax'
+    bce_target_thresh = None
+    bce_sum = False
+    _LOSS = ('loss', 'bce_target_thresh', 'bce_sum')
+
 
 def parse_args(argv=None):
     parser = argparse.ArgumentParser(description="ImageNet pre-training of a localizer backbone (MI355X-native)")
@@ -339,6 +360,10 @@ def parse_args(argv=None):
     parser.add_argument("--lamb-eps", type=float, default=argparse.SUPPRESS, help="with --optimizer lamb: added to the root of the second moment (default 1e-6)")
     # gradient clipping
     parser.add_argument("--clip-grad-norm", type=float, default=argparse.SUPPRESS, metavar='C', help="clip the gradient to the global L2 norm C > 0 before every step and log its norm as grad_norm; inf: log the norm only (default: off)")
+    # the training loss
+    parser.add_argument("--loss", default=argparse.SUPPRESS, choices=['softmax', 'bce'], help="softmax cross-entropy (default) or the per-class sigmoid binary cross-entropy on the same smoothed / mixed target; the validation loss is the plain softmax cross-entropy either way")
+    parser.add_argument("--bce-target-thresh", type=float, default=argparse.SUPPRESS, metavar='T', help="with --loss bce: make the target 0 / 1 by target > T, T in [0, 1) (default: the soft target)")
+    parser.add_argument("--bce-sum", action='store_true', default=argparse.SUPPRESS, help="with --loss bce: sum the loss over the classes instead of averaging it (the mean over the rows either way)")
     checkpoint.add_arguments(parser, argparse.SUPPRESS)
     args = parser.parse_args(argv, namespace=Arguments())
     try:
@@ -349,10 +374,11 @@ def parse_args(argv=None):
         check_lars_arguments(args)
         check_lamb_arguments(args)
         check_clip_arguments(args)
+        check_loss_arguments(args)
         if args.resume is not None:
             check_average_resume(args)
             world = os.environ.get('WORLD_SIZE')        # a rank under a launcher: the group's size, whatever --gpus says
-            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS_WITH_CLIP)
+            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS_WITH_LOSS)
     except ValueError as e:
         parser.error(str(e))
     return args
@@ -445,6 +471,17 @@ def check_clip_arguments(args):
                          'norm without clipping, got %r' % c)
 
 
+def check_loss_arguments(args):
+    """ValueError for a --bce-target-thresh that is no threshold, and for a BCE option given to the softmax loss"""
+    if args.loss not in ('softmax', 'bce'):
+        raise ValueError('--loss is softmax or bce, got %r' % (args.loss,))
+    t = args.bce_target_thresh
+    if t is not None and not 0.0 <= t < 1.0:
+        raise ValueError('--bce-target-thresh is compared with a target in [0, 1]: it must lie in [0, 1), got %r' % t)
+    if args.loss != 'bce' and (t is not None or args.bce_sum):
+        raise ValueError('--bce-target-thresh / --bce-sum belong to --loss bce')
+
+
 AVERAGE_RESUME = {False: '--resume: the checkpoint was written without --ema-decay and holds no weight average: resume it without the option',
                   True: '--resume: the checkpoint was written with --ema-decay %g and holds a weight average: resume it with the option'}
 
@@ -470,9 +507,12 @@ RESUME_DEFAULTS_WITH_PHOTO = dict(RESUME_DEFAULTS_WITH_LARS, **RESUME_DEFAULTS_P
 # ... and for --lamb-beta1 / --lamb-beta2 / --lamb-eps
 RESUME_DEFAULTS_LAMB = {name: getattr(Arguments, name) for name in Arguments._LAMB}
 RESUME_DEFAULTS_WITH_LAMB = dict(RESUME_DEFAULTS_WITH_PHOTO, **RESUME_DEFAULTS_LAMB)
-# ... and for --clip-grad-norm; this is the table --resume uses
+# ... and for --clip-grad-norm
 RESUME_DEFAULTS_CLIP = {name: getattr(Arguments, name) for name in Arguments._CLIP}
 RESUME_DEFAULTS_WITH_CLIP = dict(RESUME_DEFAULTS_WITH_LAMB, **RESUME_DEFAULTS_CLIP)
+# ... and for --loss / --bce-target-thresh / --bce-sum; this is the table --resume uses
+RESUME_DEFAULTS_LOSS = {name: getattr(Arguments, name) for name in Arguments._LOSS}
+RESUME_DEFAULTS_WITH_LOSS = dict(RESUME_DEFAULTS_WITH_CLIP, **RESUME_DEFAULTS_LOSS)
 
 
 def cache_budgets(total_bytes, n_train, n_validation):
@@ -512,13 +552,20 @@ def resolved_topk(args):
     return args.topk if args.topk > 0 else None
 
 
+def loss_options(args):
+    """the ``Classifier`` arguments of ``--loss``; none for the softmax loss, which is built as it always was"""
+    if args.loss != 'bce':
+        return {}
+    return dict(loss='bce', bce_target_threshold=args.bce_target_thresh, bce_sum=bool(args.bce_sum))
+
+
 def build_model(args):
     """the localizer in its ``train_imagenet`` form under a ``Classifier``; host side only"""
     if args.seed is not None:
         np.random.seed(args.seed)
     localizer_class = loans_amd.SheepLocalizer if args.use_resnet_18 else loans_amd.Resnet50SheepLocalizer
     model = loans_amd.Classifier(localizer_class((75, 75), train_imagenet=True), label_smoothing=args.label_smoothing,
-                                 topk=resolved_topk(args))
+                                 topk=resolved_topk(args), **loss_options(args))
     model.materialize()         # the ResNet-18 variant's lazily sized fc
     return model
 
@@ -600,6 +647,7 @@ def run(args, log=print):
     check_lars_arguments(args)
     check_lamb_arguments(args)
     check_clip_arguments(args)
+    check_loss_arguments(args)
     chief = comm.rank == 0                     # prints, logs and writes snapshots
 
     # --augment rrc: the iterators hand out (frames, labels) already resident on the device
@@ -721,7 +769,7 @@ def run(args, log=print):
         # the run continues in the checkpoint's log directory: no new <time>_<name>
         check_average_resume(args)
         resumed, changed = checkpoint.resolve_resume(args, RESUME_FIXED, log if chief else (lambda line: None), world=comm.size,
-                                                     defaults=RESUME_DEFAULTS_WITH_CLIP)
+                                                     defaults=RESUME_DEFAULTS_WITH_LOSS)
         args.log_dir = os.path.dirname(os.path.abspath(args.resume))
         for line in changed if chief else ():
             log(line)
@@ -745,7 +793,10 @@ def run(args, log=print):
             continue
         if argument in Arguments._CLIP and clipping is None:
             continue
-        data_to_log[argument] = getattr(args, argument)
+        if argument in Arguments._LOSS and not any(name in vars(args) for name in Arguments._LOSS):
+            continue        # logged where one of them is given
+        # (an entry's ``loss`` is the training loss: the option of that name is logged as ``loss_function``)
+        data_to_log['loss_function' if argument == 'loss' else argument] = getattr(args, argument)
     log_entries = []
     state = dict(models={'model': model}, optimizers={'main': optimizer}, iterators={'main': train_iter}, comm=comm)
     if average is not None:
