@@ -934,6 +934,38 @@ int loans_photo_apply_f32(const float* x, float* out, int32_t B, int32_t C, int3
                           const loans_photo_job* jobs_dev, const loans_photo_job* jobs_host, const void* workspace,
                           int64_t workspace_bytes, void* stream);
 
+/* ---- RandAugment / TrivialAugmentWide on a device batch (csrc/randaug.hip; the fourteen operations and their arithmetic are listed
+ *      in that file's header and stated in loans_amd/common/datasets/rand_augment.py).  x, out: contiguous [B][3][H][W] fp32; image
+ *      n runs the `layers` (1 .. 4) layers of jobs[n] one behind the other.  Per layer l: op[l] 0 .. 13 (Identity, ShearX, ShearY,
+ *      TranslateX, TranslateY, Rotate, Brightness, Color, Contrast, Sharpness, Posterize, Solarize, AutoContrast, Equalize);
+ *      a[l]: for ops 1 .. 5 the six 16.16 fixed-point coefficients of the output -> input map, xin = (a0 x + a1 y + a2) >> 16,
+ *      yin = (a3 x + a4 y + a5) >> 16 (|a0|, |a1|, |a3|, |a4| <= 2^20, |a2|, |a5| <= 2^50), for Posterize a[l][0] = the bits kept, 2 .. 8;
+ *      f[l]: for ops 6 .. 9 the factor and fl32(1 - factor), rounded once by the caller, for Solarize f[l][0] = the threshold.  `fill`
+ *      is what a pixel becomes whose source lies outside the frame.  A layer that is the identity for its image leaves it bit for bit.
+ *      `workspace`: device memory, 16-byte aligned, loans_ra_workspace_bytes(B, H, W) bytes at least (block records, folded records,
+ *      one scratch batch); it need not be initialised.  loans_ra_stats_f32: the statistics of layer `layer` (0 .. 3) of the batch x as
+ *      it stands -- the grey mean for Contrast, the channel extremes for AutoContrast, the channel histograms for Equalize -- folded
+ *      in a fixed order into the workspace; no floating-point atomics; no launch when no image's layer needs one.
+ *      loans_ra_apply_f32: the whole stage, per layer the statistics step where an image needs it and one apply launch; the result ends
+ *      in out, which may be x; x is only read where out is another tensor (neither may overlap the workspace).  Two runs give the same
+ *      bits.  jobs_dev: the table in DEVICE memory; jobs_host: the same table in host memory, checked on every call.  LOANS_EINVAL --
+ *      before any launch -- for a null or misaligned pointer (4 bytes for x / out, 8 for the tables, 16 for the workspace),
+ *      non-positive sizes, C != 3, a workspace that is too small, a layer count outside [1, 4], an unknown operation, a coefficient
+ *      beyond the limits, a non-finite factor, threshold or fill, bits outside [2, 8]; LOANS_ERANGE for 3 * H * W >= 2^30 (the batch
+ *      itself is indexed in 64 bits).  Nothing is synchronised with the host. ---- */
+typedef struct loans_ra_job {
+    int64_t a[4][6];            /* per layer: fixed-point coefficients (ops 1 .. 5), or the bits in a[l][0] (Posterize) */
+    float f[4][2];              /* per layer: factor and fl32(1 - factor) (ops 6 .. 9), or the threshold in f[l][0] (Solarize) */
+    int32_t op[4];              /* per layer: the operation, 0 .. 13 */
+    int32_t layers;             /* 1 .. 4 */
+    float fill[3];              /* RGB of a pixel whose source lies outside the frame */
+} loans_ra_job;
+int64_t loans_ra_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int loans_ra_stats_f32(const float* x, int32_t B, int32_t C, int32_t H, int32_t W, const loans_ra_job* jobs_dev,
+                       const loans_ra_job* jobs_host, int32_t layer, void* workspace, int64_t workspace_bytes, void* stream);
+int loans_ra_apply_f32(const float* x, float* out, int32_t B, int32_t C, int32_t H, int32_t W, const loans_ra_job* jobs_dev,
+                       const loans_ra_job* jobs_host, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* library / build identification */
 const char* loans_hip_version(void);
 

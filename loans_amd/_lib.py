@@ -197,12 +197,15 @@ SIGNATURES = {
     'loans_photo_workspace_bytes': [_i32, _i32, _i32],
     'loans_photo_grey_means_f32': [_p, _i32, _i32, _i32, _i32, _p, _p, _p, _i64, _p],
     'loans_photo_apply_f32': [_p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _i64, _p],
+    'loans_ra_workspace_bytes': [_i32, _i32, _i32],
+    'loans_ra_stats_f32': [_p, _i32, _i32, _i32, _i32, _p, _p, _i32, _p, _i64, _p],
+    'loans_ra_apply_f32': [_p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _i64, _p],
 }
 
 # every entry point returns int (0 / LOANS_E* / hipError_t) except:
 RESTYPES = {'loans_wgrad_bf16s_ws_floats': C.c_int64, 'loans_crop_band_rows': C.c_int, 'loans_momentum_sgd_max_segments': C.c_int,
             'loans_lars_workspace_bytes': C.c_int64, 'loans_photo_workspace_bytes': C.c_int64,
-            'loans_grad_clip_workspace_bytes': C.c_int64}      # (sizes / counts, not a status)
+            'loans_grad_clip_workspace_bytes': C.c_int64, 'loans_ra_workspace_bytes': C.c_int64}    # (sizes / counts, not a status)
 
 _lib = None
 

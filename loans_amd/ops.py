@@ -2593,6 +2593,71 @@ def photometric(x, jobs, out=None):
     return out
 
 
+# mirror of loans_ra_job (include/loans_hip.h)
+RA_JOB = np.dtype([('a', '<i8', (4, 6)), ('f', '<f4', (4, 2)), ('op', '<i4', (4,)), ('layers', '<i4'), ('fill', '<f4', (3,))])
+assert RA_JOB.itemsize == 256
+_RA_SAME = np.array([65536, 0, 32768, 0, 65536, 32768], np.int64)      # the coefficients of a zero shear / shift / angle
+_ra_workspaces = {}             # (device index, raw stream) -> uint8 tensor: block records, folded records, the scratch batch
+
+
+def ra_workspace(device, nbytes):
+    """the workspace of ``rand_augment`` on ``device`` for the current stream, at least ``nbytes`` bytes: kept from call to call
+    (it is never part of a step arena), grown when a larger batch comes"""
+    key = (device.index, _stream())
+    ws = _ra_workspaces.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _ra_workspaces[key] = torch.empty(max(int(nbytes), 16), device=device, dtype=torch.uint8)
+    return ws
+
+
+def ra_identity(jobs, H, W):
+    """[B][4] bool: which layers of an ``RA_JOB`` table change nothing of an H x W image -- beyond the job's layer count,
+    Identity, a zero shear / shift / angle, a factor of 1, 8 bits, Sharpness on a frame without an interior (csrc/randaug.hip,
+    ra_effective)"""
+    op, layer = jobs['op'], np.arange(4)[None, :]
+    same = (op == 0) | (layer >= jobs['layers'][:, None])
+    same |= (op >= 1) & (op <= 5) & (jobs['a'] == _RA_SAME).all(axis=2)
+    same |= (op >= 6) & (op <= 9) & (jobs['f'][:, :, 0] == 1)
+    if H < 3 or W < 3:
+        same |= op == 9
+    same |= (op == 10) & (jobs['a'][:, :, 0] == 8)
+    return same
+
+
+def rand_augment(x, jobs, out=None):
+    """RandAugment / TrivialAugmentWide of the device batch x [B][3][H][W] fp32 (csrc/randaug.hip; the arithmetic is stated in
+    loans_amd/common/datasets/rand_augment.py): ``jobs`` is a NumPy record array of dtype ``RA_JOB``, one job of 1..4 layers per
+    image.  The table goes up through the pinned staging ring; then, on the current stream, per layer the statistics step where
+    an image's layer is Contrast, AutoContrast or Equalize and one apply launch -- none at all where every layer of every job is
+    the identity and ``out`` is ``x``.
+    Returns a fresh tensor, or ``out``, which may be ``x`` itself; ``x`` is left untouched otherwise.  No host synchronisation."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()):
+        raise ValueError('the batch must be a contiguous float32 [B][3][H][W] device tensor')
+    if out is None:
+        out = torch.empty_like(x)
+    elif not (out.dtype == x.dtype and out.device == x.device and out.is_contiguous() and out.shape == x.shape):
+        raise ValueError('out must be a contiguous float32 tensor of the batch\'s shape on its device')
+    B, C, H, W = x.shape
+    if not (isinstance(jobs, np.ndarray) and jobs.dtype == RA_JOB and jobs.shape == (B,)):
+        raise ValueError('jobs must be an RA_JOB record array with one job per image of the batch')
+    jobs = np.ascontiguousarray(jobs)
+    if out.data_ptr() == x.data_ptr() and ra_identity(jobs, H, W).all():
+        return out
+    from .common.datasets import resample           # (imports this module)
+    lib = _lib.load()
+    ring, slot, host = resample._staging.get(jobs.nbytes, kind='randaug')      # (a ring of its own, as the photometric stage has)
+    host[:jobs.nbytes].numpy()[:] = jobs.view(np.uint8)
+    jobs_d = host[:jobs.nbytes].to(x.device, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(x.device))
+    ring['events'][slot] = ev
+    ws_bytes = int(lib.loans_ra_workspace_bytes(B, H, W))
+    ws = ra_workspace(x.device, ws_bytes)
+    check(lib.loans_ra_apply_f32(_ptr(x), _ptr(out), B, C, H, W, _ptr(jobs_d), jobs.ctypes.data, _ptr(ws), ws_bytes, _stream()),
+          'loans_ra_apply_f32')
+    return out
+
+
 def softmax_xent_eval(z, t, acc, k=1):
     """Evaluation: add the batch's plain loss sum, top-1 hits, top-k hits, valid rows and rows to ``acc`` (5 float64 on the
     device, read-modify-write).  No gradient is written.  No host synchronisation."""

@@ -76,6 +76,21 @@ Validation frames are never touched.
     python train_imagenet.py train.tsv val.tsv -b 256 --optimizer sgd --lr 0.1 --augment rrc --label-smoothing 0.1 \
         --color-jitter 0.4 0.4 0.4 --lighting-std 0.1 --random-erase-prob 0.25
 
+``--rand-augment N M`` and ``--trivial-augment`` (with ``--augment rrc``; one of the two; default: off) are the learned-policy-free
+augmentations of the RandAugment family, on training batches only, between the crop and the photometric stage (crop -> RandAugment
+-> jitter / lighting / erase -> mix): RandAugment applies N (1 to 4) operations per image, each drawn uniformly from torchvision's
+fourteen (Identity, ShearX/Y, TranslateX/Y, Rotate, Brightness, Color, Contrast, Sharpness, Posterize, Solarize, AutoContrast,
+Equalize), at the magnitude bin M (0 to 30) with a random sign; TrivialAugmentWide applies one operation at a magnitude bin drawn
+uniformly from 0..30 of its wider ranges.  ``--ra-fill R G B`` is what a pixel becomes whose source lies outside the frame after a
+shear, shift or rotation (the ImageNet mean by default).  The draws come from a stream of their own (``--ra-seed``, rank r from
+seed + 7919 r; the crops, the photometric and the mix draws do not depend on it) on the host, one job per image; the pixels are
+changed on the GPU on the iterator's stream: per layer one small statistics step where an image needs one (Contrast's mean,
+AutoContrast's extremes, Equalize's histograms) and one apply launch (loans_amd/common/datasets/rand_augment.py,
+csrc/randaug.hip).  Validation frames are never touched.
+
+    python train_imagenet.py train.tsv val.tsv -b 256 --optimizer sgd --lr 0.1 --augment rrc --label-smoothing 0.1 \
+        --rand-augment 2 9
+
 ``--ema-decay D`` (default 0: off) keeps an exponential moving average of the weights and the BN statistics
 (loans_amd/runtime/average.py, ``WeightAverage``: one launch per step behind the optimiser's; update t uses the decay
 ``min(D, (1 + t) / (10 + t))``).  When validation runs it runs twice -- the live model first, as always, then the averaged one, whose
@@ -132,19 +147,19 @@ the training loss -- and may change on resume.
 
     python train_imagenet.py train.tsv val.tsv --gpus 8 -b 256 --dtype bf16 --optimizer lamb --lr 5e-3 --weight-decay 0.02 \
         --no-decay-1d --lr-schedule cosine --lr-min 1e-6 --warmup-epochs 5 --num-epoch 300 --augment rrc --mixup-alpha 0.2 \
-        --cutmix-alpha 1.0 --color-jitter 0.4 0.4 0.4 --random-erase-prob 0.25 --ema-decay 0.9999 --clip-grad-norm 1.0 \
-        --loss bce --bce-target-thresh 0.2
+        --cutmix-alpha 1.0 --color-jitter 0.4 0.4 0.4 --random-erase-prob 0.25 --rand-augment 2 9 --ema-decay 0.9999 \
+        --clip-grad-norm 1.0 --loss bce --bce-target-thresh 0.2
 
 ``--checkpoint-interval N`` writes a full-state checkpoint, ``checkpoint_<iteration>.npz`` in the log directory, after every
 N-th iteration and after the last one (default 0: none; ``--checkpoint-keep K``, default 2, keeps the newest K): the model with
 its BN statistics, the optimiser's buffers and step count, the training iterator as of the batch the step consumed (shuffle
-stream, order, position, the crop / mirror draw stream, the photometric and the mix draw stream), NumPy's global stream and the run's arguments
+stream, order, position, the crop / mirror draw stream, the RandAugment, the photometric and the mix draw stream), NumPy's global stream and the run's arguments
 (loans_amd/runtime/checkpoint.py; under ``--gpus N`` one small record per rank beside rank 0's file, which is written last).
 ``--resume PATH`` -- a checkpoint file, or a log directory, whose newest complete checkpoint is taken -- continues that run in
 its log directory: the ``log`` file is read back and appended to, ``elapsed_time`` and the snapshot names count on.  Fixed on
 resume (one error lists every one that differs): the architecture, ``--dtype``, ``--optimizer``, ``-b``, ``--gpus``,
 ``--image-size``, the dataset files or the synthetic sizes, classes and ``--data-seed``, ``--no-shuffle``, ``--augment`` /
-``--rrc-*`` / ``--val-crop-pct`` / ``--augment-seed``, ``--mixup-alpha`` / ``--cutmix-alpha`` / ``--mix-*``, ``--color-jitter`` / ``--lighting-std`` / ``--random-erase-*`` / ``--photo-seed``, ``--ema-decay`` (a checkpoint from
+``--rrc-*`` / ``--val-crop-pct`` / ``--augment-seed``, ``--mixup-alpha`` / ``--cutmix-alpha`` / ``--mix-*``, ``--color-jitter`` / ``--lighting-std`` / ``--random-erase-*`` / ``--photo-seed``, ``--rand-augment`` / ``--trivial-augment`` / ``--ra-fill`` / ``--ra-seed``, ``--ema-decay`` (a checkpoint from
 before these options existed ran at their defaults), ``--seed``.  Taken from the new command line (each one that differs is
 printed once): ``--num-epoch``, ``--iterations``, the log, snapshot and checkpoint intervals, ``--loader-threads``, the frame
 cache options, ``--lr``, ``--weight-decay``, ``--momentum``, ``--lr-drop-*``, ``--lr-schedule``, ``--lr-min``, ``--no-decay-1d``, ``--lars-eta``, ``--lars-eps``, ``--lamb-beta1``, ``--lamb-beta2``, ``--lamb-eps``, ``--clip-grad-norm``, ``--warmup-*``, ``--label-smoothing``, ``--topk``, ``--loss``, ``--bce-target-thresh``, ``--bce-sum``.  The
@@ -189,7 +204,7 @@ RESUME_FIXED = ('use_resnet_18', 'dtype', 'optimizer', 'batch_size', 'gpus', 'im
                 'validation_size', 'synthetic_classes', 'data_seed', 'no_shuffle', 'augment', 'rrc_scale', 'rrc_ratio', 'val_crop_pct',
                 'augment_seed', 'seed', 'mixup_alpha', 'cutmix_alpha', 'mix_prob', 'mix_switch_prob', 'mix_seed', 'ema_decay',
                 'color_jitter', 'lighting_std', 'random_erase_prob', 'random_erase_scale', 'random_erase_ratio', 'random_erase_value',
-                'photo_seed')
+                'photo_seed', 'rand_augment', 'trivial_augment', 'ra_fill', 'ra_seed')
 
 
 class SyntheticClasses:
@@ -266,6 +281,14 @@ class Arguments(argparse.Namespace):
     random_erase_ratio = (0.3, 3.3)
     random_erase_value = (0.485, 0.456, 0.406)
     photo_seed = None
+
+    # RandAugment / TrivialAugmentWide of the --augment rrc feed (loans_amd/common/datasets/rand_augment.py); off by default, logged
+    # where one of them is given
+    rand_augment = None
+    trivial_augment = False
+    ra_fill = (0.485, 0.456, 0.406)
+    ra_seed = None
+    _RA = ('rand_augment', 'trivial_augment', 'ra_fill', 'ra_seed')
 
     _MIX = ('mixup_alpha', 'cutmix_alpha', 'mix_prob', 'mix_switch_prob', 'mix_seed')
     _PHOTO = ('color_jitter', 'lighting_std', 'random_erase_prob', 'random_erase_scale', 'random_erase_ratio', 'random_erase_value',
@@ -346,6 +369,11 @@ def parse_args(argv=None):
     parser.add_argument("--random-erase-ratio", type=float, nargs=2, default=argparse.SUPPRESS, metavar=('LO', 'HI'), help="aspect ratio (height / width) of the erased box, log-uniform (default 0.3 3.3)")
     parser.add_argument("--random-erase-value", type=float, nargs=3, default=argparse.SUPPRESS, metavar=('R', 'G', 'B'), help="what an erased pixel becomes (default 0.485 0.456 0.406, the ImageNet mean: the frames are not mean-subtracted)")
     parser.add_argument("--photo-seed", type=int, default=argparse.SUPPRESS, help="seed of the colour jitter / lighting / erase draws (a stream of their own)")
+    # RandAugment / TrivialAugmentWide
+    parser.add_argument("--rand-augment", type=int, nargs=2, default=argparse.SUPPRESS, metavar=('N', 'M'), help="with --augment rrc: RandAugment, N random operations (1 to 4) per training image at magnitude bin M (0 to 30), between the crop and the photometric stage (default: off)")
+    parser.add_argument("--trivial-augment", action='store_true', default=argparse.SUPPRESS, help="with --augment rrc: TrivialAugmentWide, one random operation per training image at a random magnitude; not with --rand-augment (default: off)")
+    parser.add_argument("--ra-fill", type=float, nargs=3, default=argparse.SUPPRESS, metavar=('R', 'G', 'B'), help="what a pixel becomes whose source lies outside the frame after a shear, shift or rotation (default 0.485 0.456 0.406, the ImageNet mean)")
+    parser.add_argument("--ra-seed", type=int, default=argparse.SUPPRESS, help="seed of the RandAugment / TrivialAugment draws (a stream of their own)")
     # weight average, cosine rate, decay-free 1-d parameters
     parser.add_argument("--ema-decay", type=float, default=argparse.SUPPRESS, help="keep an exponential moving average of the weights with this decay (warmed up as (1 + t) / (10 + t)); validated and snapshotted beside the live model (default 0: off)")
     parser.add_argument("--lr-schedule", default=argparse.SUPPRESS, choices=['step', 'cosine'], help="step: --lr-drop-epochs; cosine: half a cosine from --lr down to --lr-min over --num-epoch, behind the warm-up (default step)")
@@ -370,6 +398,7 @@ def parse_args(argv=None):
         check_cache_arguments(args)
         check_mix_arguments(args)
         check_photo_arguments(args)
+        check_ra_arguments(args)
         check_average_arguments(args)
         check_lars_arguments(args)
         check_lamb_arguments(args)
@@ -378,7 +407,7 @@ def parse_args(argv=None):
         if args.resume is not None:
             check_average_resume(args)
             world = os.environ.get('WORLD_SIZE')        # a rank under a launcher: the group's size, whatever --gpus says
-            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS_WITH_LOSS)
+            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS_WITH_RA)
     except ValueError as e:
         parser.error(str(e))
     return args
@@ -428,6 +457,26 @@ def check_photo_arguments(args):
         raise ValueError('--random-erase-value takes three finite numbers, got %r' % (tuple(args.random_erase_value),))
     if photo_enabled(args) and args.augment != 'rrc':
         raise ValueError('--color-jitter / --lighting-std / --random-erase-prob change the batches the GPU crops: they need --augment rrc')
+
+
+def ra_enabled(args):
+    """whether RandAugment or TrivialAugment is switched on"""
+    return args.rand_augment is not None or bool(args.trivial_augment)
+
+
+def check_ra_arguments(args):
+    """ValueError for a RandAugment that names no policy, for both policies at once, and where the stage is asked of a feed that is
+    not on the device"""
+    if args.rand_augment is not None:
+        pair = tuple(args.rand_augment)
+        if len(pair) != 2 or not all(isinstance(v, int) for v in pair) or not 1 <= pair[0] <= 4 or not 0 <= pair[1] <= 30:
+            raise ValueError('--rand-augment takes N layers, 1 to 4, and a magnitude bin M, 0 to 30, got %r' % (pair,))
+        if args.trivial_augment:
+            raise ValueError('--rand-augment and --trivial-augment are two policies: give one of them')
+    if len(args.ra_fill) != 3 or not all(math.isfinite(v) for v in args.ra_fill):
+        raise ValueError('--ra-fill takes three finite numbers, got %r' % (tuple(args.ra_fill),))
+    if ra_enabled(args) and args.augment != 'rrc':
+        raise ValueError('--rand-augment / --trivial-augment change the batches the GPU crops: they need --augment rrc')
 
 
 def check_average_arguments(args):
@@ -510,9 +559,12 @@ RESUME_DEFAULTS_WITH_LAMB = dict(RESUME_DEFAULTS_WITH_PHOTO, **RESUME_DEFAULTS_L
 # ... and for --clip-grad-norm
 RESUME_DEFAULTS_CLIP = {name: getattr(Arguments, name) for name in Arguments._CLIP}
 RESUME_DEFAULTS_WITH_CLIP = dict(RESUME_DEFAULTS_WITH_LAMB, **RESUME_DEFAULTS_CLIP)
-# ... and for --loss / --bce-target-thresh / --bce-sum; this is the table --resume uses
+# ... and for --loss / --bce-target-thresh / --bce-sum
 RESUME_DEFAULTS_LOSS = {name: getattr(Arguments, name) for name in Arguments._LOSS}
 RESUME_DEFAULTS_WITH_LOSS = dict(RESUME_DEFAULTS_WITH_CLIP, **RESUME_DEFAULTS_LOSS)
+# ... and for --rand-augment / --trivial-augment / --ra-fill / --ra-seed; this is the table --resume uses
+RESUME_DEFAULTS_RA = {name: getattr(Arguments, name) for name in Arguments._RA}
+RESUME_DEFAULTS_WITH_RA = dict(RESUME_DEFAULTS_WITH_LOSS, **RESUME_DEFAULTS_RA)
 
 
 def cache_budgets(total_bytes, n_train, n_validation):
@@ -639,10 +691,14 @@ def run(args, log=print):
     # ... and so are the _PHOTO options
     photo_given = any((tuple(v) if isinstance(v, (list, tuple)) else v) != getattr(Arguments, name)
                       for name, v in ((name, getattr(args, name)) for name in Arguments._PHOTO))
+    # ... and the _RA options
+    ra_given = any((tuple(v) if isinstance(v, (list, tuple)) else v) != getattr(Arguments, name)
+                   for name, v in ((name, getattr(args, name)) for name in Arguments._RA))
     args.gpus = comm.size
     check_cache_arguments(args)
     check_mix_arguments(args)
     check_photo_arguments(args)
+    check_ra_arguments(args)
     check_average_arguments(args)
     check_lars_arguments(args)
     check_lamb_arguments(args)
@@ -678,6 +734,15 @@ def run(args, log=print):
     # every rank built the same sets and takes every comm.size-th example: the training share padded by wrapping (all ranks make
     # the same iterations and epochs), the validation share not (every example is counted once; shares may differ by one)
     train_dataset = ShardedDataset(train_dataset, comm.rank, comm.size, pad=True)
+    if ra_enabled(args):
+        # between the crop and the photometric stage, with draws of its own: the stream of --ra-seed + 7919 r
+        from loans_amd.common.datasets.rand_augment import RandAugmentBatches, RandAugmentPolicy
+        ra_seed = None if args.ra_seed is None else args.ra_seed + 7919 * comm.rank
+        if args.trivial_augment:
+            ra_policy = RandAugmentPolicy('trivial', fill=tuple(args.ra_fill), seed=ra_seed)
+        else:
+            ra_policy = RandAugmentPolicy('rand', int(args.rand_augment[0]), int(args.rand_augment[1]), tuple(args.ra_fill), ra_seed)
+        train_dataset = RandAugmentBatches(train_dataset, ra_policy, tuple(args.image_size))
     if photo_enabled(args):
         # between the crop and the mix, with draws of its own: the stream of --photo-seed + 7919 r
         from loans_amd.common.datasets.photometric import PhotometricBatches, PhotoPolicy
@@ -769,7 +834,7 @@ def run(args, log=print):
         # the run continues in the checkpoint's log directory: no new <time>_<name>
         check_average_resume(args)
         resumed, changed = checkpoint.resolve_resume(args, RESUME_FIXED, log if chief else (lambda line: None), world=comm.size,
-                                                     defaults=RESUME_DEFAULTS_WITH_LOSS)
+                                                     defaults=RESUME_DEFAULTS_WITH_RA)
         args.log_dir = os.path.dirname(os.path.abspath(args.resume))
         for line in changed if chief else ():
             log(line)
@@ -786,6 +851,8 @@ def run(args, log=print):
         if argument in Arguments._AVERAGE and not averaging:
             continue
         if argument in Arguments._PHOTO and not photo_given:
+            continue
+        if argument in Arguments._RA and not ra_given:
             continue
         if argument in Arguments._LARS and args.optimizer != 'lars':
             continue        # a run with another optimiser logs what it always logged
