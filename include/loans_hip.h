@@ -966,6 +966,37 @@ int loans_ra_stats_f32(const float* x, int32_t B, int32_t C, int32_t H, int32_t 
 int loans_ra_apply_f32(const float* x, float* out, int32_t B, int32_t C, int32_t H, int32_t W, const loans_ra_job* jobs_dev,
                        const loans_ra_job* jobs_host, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- stochastic depth at a residual unit's junction (csrc/bn_pool.hip; torchvision's StochasticDepth(mode='row') = timm's
+ *      drop_path).  The tensors are [B][rows_per_sample][C] (NHWC, rows_per_sample = Ho * Wo); r: B floats in device memory, 0 for a
+ *      dropped sample, 1 / (1 - p) for a kept one.  Relu and sign bits (loans_bn_apply_bits_*'s layout, one byte per four channels)
+ *      always.
+ *      loans_bn_apply_rows_*: y = relu(r[b] (x scale + shift) + second), second = x2 (mode 1) or x2 scale2 + shift2 (mode 2); a
+ *      sample with r[b] == 0 is relu(second) to the bit.
+ *      loans_bn_bwd_reduce_rows_*: with g = gy * bit, sums fp64 [replicas][2][C] = [sum r g | sum r g xhat], dual (x2 given)
+ *      [replicas][4][C] = [sum r g | sum r g xhat | sum g | sum g xhat2], zeroed by the caller: loans_bn_bwd_reduce_rep_*'s layout,
+ *      summed by loans_bn_bwd_coeffs_rep_f32 (centred = 0).
+ *      loans_bn_bwd_apply_rows_*: gx = k1 (r[b] g) + k2 x + k3, and with x2: gx2 = k1b g + k2b x2 + k3b.
+ *      Channel counts: C / V units per row (V = 4 fp32 / 8 bf16 channels) a divisor of 256 or a multiple of it, else LOANS_EINVAL;
+ *      LOANS_ERANGE for a sample of 2^30 units or more.  No floating-point atomics but the reduction's fp64 ones. ---- */
+int loans_bn_apply_rows_f32(const float* x, const float* scale, const float* shift, const float* x2, const float* scale2,
+                            const float* shift2, const float* r, float* y, uint8_t* signbits, int32_t B, int64_t rows_per_sample,
+                            int32_t C, int32_t mode, void* stream);
+int loans_bn_apply_rows_bf16(const void* x, const float* scale, const float* shift, const void* x2, const float* scale2,
+                             const float* shift2, const float* r, void* y, uint8_t* signbits, int32_t B, int64_t rows_per_sample,
+                             int32_t C, int32_t mode, void* stream);
+int loans_bn_bwd_reduce_rows_f32(const float* gy, const uint8_t* signbits, const float* r, const float* x, const float* mean,
+                                 const float* rstd, const float* x2, const float* mean2, const float* rstd2, double* sums,
+                                 int32_t replicas, int32_t B, int64_t rows_per_sample, int32_t C, void* stream);
+int loans_bn_bwd_reduce_rows_bf16(const void* gy, const uint8_t* signbits, const float* r, const void* x, const float* mean,
+                                  const float* rstd, const void* x2, const float* mean2, const float* rstd2, double* sums,
+                                  int32_t replicas, int32_t B, int64_t rows_per_sample, int32_t C, void* stream);
+int loans_bn_bwd_apply_rows_f32(const float* gy, const uint8_t* signbits, const float* r, const float* x, const float* k1,
+                                const float* k2, const float* k3, float* gx, const float* x2, const float* k1b, const float* k2b,
+                                const float* k3b, float* gx2, int32_t B, int64_t rows_per_sample, int32_t C, void* stream);
+int loans_bn_bwd_apply_rows_bf16(const void* gy, const uint8_t* signbits, const float* r, const void* x, const float* k1,
+                                 const float* k2, const float* k3, void* gx, const void* x2, const float* k1b, const float* k2b,
+                                 const float* k3b, void* gx2, int32_t B, int64_t rows_per_sample, int32_t C, void* stream);
+
 /* library / build identification */
 const char* loans_hip_version(void);
 

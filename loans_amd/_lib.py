@@ -200,6 +200,12 @@ SIGNATURES = {
     'loans_ra_workspace_bytes': [_i32, _i32, _i32],
     'loans_ra_stats_f32': [_p, _i32, _i32, _i32, _i32, _p, _p, _i32, _p, _i64, _p],
     'loans_ra_apply_f32': [_p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _i64, _p],
+    'loans_bn_apply_rows_f32': [_p] * 9 + [_i32, _i64, _i32, _i32, _p],
+    'loans_bn_apply_rows_bf16': [_p] * 9 + [_i32, _i64, _i32, _i32, _p],
+    'loans_bn_bwd_reduce_rows_f32': [_p] * 10 + [_i32, _i32, _i64, _i32, _p],
+    'loans_bn_bwd_reduce_rows_bf16': [_p] * 10 + [_i32, _i32, _i64, _i32, _p],
+    'loans_bn_bwd_apply_rows_f32': [_p] * 13 + [_i32, _i64, _i32, _p],
+    'loans_bn_bwd_apply_rows_bf16': [_p] * 13 + [_i32, _i64, _i32, _p],
 }
 
 # every entry point returns int (0 / LOANS_E* / hipError_t) except:

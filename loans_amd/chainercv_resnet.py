@@ -3,7 +3,7 @@ stages ``res6`` / ``res7`` of ``Resnet50SheepLocalizer`` (sheep/sheep_localizer.
 ``a`` with a 1x1 ``residual_conv`` + (n_layer - 1) identity bottlenecks ``b1`` ..., stride on the 3x3 conv
 (``stride_first=False``).  Parameter paths match chainercv's (``a/conv1/conv/W``, ``a/conv1/bn/gamma`` ...)."""
 from . import links as L
-from .functions import blocks
+from .functions import blocks, drop_path
 from .runtime.core import Chain
 
 
@@ -31,7 +31,7 @@ class Bottleneck(Chain):
     def __call__(self, x):
         stages = [(c.conv, c.bn) for c in (self.conv1, self.conv2, self.conv3)]
         sc = (self.residual_conv.conv, self.residual_conv.bn) if self.has_residual_conv else None
-        return blocks.residual_unit(x, stages, sc)
+        return blocks.residual_unit(x, stages, sc, drop=drop_path.unit_vector(self))
 
 
 class ResBlock(Chain):

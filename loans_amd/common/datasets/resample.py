@@ -228,6 +228,18 @@ class _Staging:
             buf = ring['bufs'][i] = torch.empty(max(int(nbytes * 1.25), 1 << 20), dtype=torch.uint8).pin_memory()
         return ring, i, buf
 
+    def upload(self, fill, nbytes, device, kind):
+        """``nbytes`` through the calling thread's ring of ``kind``: ``fill(view)`` writes them into the pinned buffer (a uint8
+        NumPy view of that length), one asynchronous copy on the current stream takes them up, and the slot carries that copy's
+        event, so that the buffer is overwritten only once the copy has finished.  Returns the device uint8 tensor."""
+        ring, slot, host = self.get(nbytes, kind)
+        fill(host[:nbytes].numpy())
+        out = host[:nbytes].to(device, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(device))
+        ring['events'][slot] = ev
+        return out
+
     def drop(self, thread_ident):
         """forget (and free) the buffers of a thread that is gone -- a feed iterator's finish thread"""
         with self.lock:
@@ -243,6 +255,11 @@ _staging = _Staging()
 
 def release_staging(thread_ident):
     _staging.drop(thread_ident)
+
+
+def upload_staged(fill, nbytes, device, kind):
+    """a small host table to the device through the pinned staging ring (``_Staging.upload``)"""
+    return _staging.upload(fill, nbytes, device, kind)
 
 
 def upload_frames(images, device, map_fn=map):

@@ -1581,3 +1581,391 @@ extern "C" int loans_pool_bn_bwd_reduce_rep_bf16(const void* gy, const uint8_t* 
     return pool_bn_bwd_reduce_impl<__bf16>(static_cast<const __bf16*>(gy), idx, static_cast<const __bf16*>(x), scale, shift, mean, rstd,
                                            sums, B, H, W, C, OH, OW, stream, replicas);
 }
+
+// ---- stochastic depth at a residual unit's junction: the three passes with a per-SAMPLE factor r[b] on the main branch -------------
+// out = relu(r[b] (x scale + shift) + second), g = gy * bit, the gradient into the last BN r[b] g, into the shortcut g
+// (functions/blocks.py, functions/drop_path.py).  The kernels are the 16-byte-unit ones above with one more operand, a float per
+// sample: a thread keeps (sample, position inside it) beside its unit index and moves both by additions -- one 64-bit division
+// per thread, none per element -- and fetches r[b] with the loads of the iteration.  Same grids, same slabs, same accumulators.
+// Two ways through a row, so that EVERY channel count of the models is covered (U = C / V units per row):
+//   U <= 256 dividing 256 .... a block streams a contiguous slab, 256 units per step, a thread's channel unit is tid % U
+//   U a multiple of 256 ...... (2048 channels in fp32) blockIdx.y picks 256 of a row's units, a block walks rows, U units per step
+// and both are ONE loop: unit index i = slab start + blockIdx.y * 256 + tid, stepped by `step` (256 or U) up to the slab's end.
+namespace {
+
+template <typename T> static inline int rows_units(int C) {
+    constexpr int V = unit16<T>::V;
+    if (C <= 0 || C % V) return 0;
+    const int U = C / V;
+    return ((U <= 256 && 256 % U == 0) || U % 256 == 0) ? U : 0;
+}
+
+struct RowsPlan { int gx, gy, step; int64_t per; };
+// `per` units per block: a multiple of 256 (contiguous slabs) or of U (whole rows), so that a thread's channels never change
+static inline RowsPlan rows_plan(int64_t rows, int U) {
+    RowsPlan p;
+    const int64_t nunits = rows * U;
+    const int g = slab_grid(nunits);
+    if (U <= 256) {
+        p.gy = 1; p.step = 256;
+        p.per = ((nunits + g - 1) / g + 255) & ~(int64_t)255;
+        p.gx = (int)((nunits + p.per - 1) / p.per);
+    } else {
+        p.gy = U / 256; p.step = U;
+        const int64_t gx = g / p.gy > 0 ? g / p.gy : 1, rpb = (rows + gx - 1) / gx;
+        p.per = rpb * U;
+        p.gx = (int)((rows + rpb - 1) / rpb);
+    }
+    return p;
+}
+
+struct RowsWalk { int64_t i, end; int b, pin; };
+__device__ __forceinline__ RowsWalk rows_walk(int64_t nunits, int64_t per, int nps) {
+    const int64_t lo = (int64_t)blockIdx.x * per;
+    RowsWalk w;
+    w.i = lo + blockIdx.y * 256 + threadIdx.x;
+    w.end = lo + per < nunits ? lo + per : nunits;
+    w.b = (int)(w.i / nps);                     // the sample of the thread's first unit and the unit's place inside it
+    w.pin = (int)(w.i - (int64_t)w.b * nps);
+    return w;
+}
+__device__ __forceinline__ void rows_next(int& b, int& pin, int step, int nps) {
+    pin += step;
+    while (pin >= nps) { pin -= nps; ++b; }
+}
+
+// y = relu(r[b] (x scale + shift) + second), second = x2 (MODE 1) or x2 scale2 + shift2 (MODE 2); sign bits always.  A dropped
+// sample (r[b] == 0) is relu(second) to the bit, whatever x holds.
+template <int MODE, bool NT, typename T>
+__global__ __launch_bounds__(256) void bn_apply_rows_kernel(const T* x, const float* scale, const float* shift, const T* x2,
+                                                            const float* scale2, const float* shift2, const float* rvec, T* y,
+                                                            uint8_t* signbits, int64_t nunits, int U, int nps, int step, int64_t per) {
+    constexpr int V = unit16<T>::V, NV = unit16<T>::NV;
+    typedef typename unit16<T>::raw_t raw_t;
+    const int cu = (blockIdx.y * 256 + threadIdx.x) % U;
+    f32x4 s[NV], t[NV], s2[NV], t2[NV];
+#pragma unroll
+    for (int q = 0; q < NV; ++q) {
+        s[q] = ld4(scale + cu * V + 4 * q); t[q] = ld4(shift + cu * V + 4 * q);
+        if (MODE == 2) { s2[q] = ld4(scale2 + cu * V + 4 * q); t2[q] = ld4(shift2 + cu * V + 4 * q); }
+    }
+    auto one = [&](int64_t i, raw_t xr, raw_t rr, float rv) {
+        f32x4 v[NV], xv[NV], sv[NV];
+        unit16<T>::cvt(xr, xv);
+        unit16<T>::cvt(rr, sv);
+#pragma unroll
+        for (int q = 0; q < NV; ++q) {
+            if (MODE == 2) sv[q] = sv[q] * s2[q] + t2[q];
+            const f32x4 a = rv * (xv[q] * s[q] + t[q]) + sv[q];
+            v[q] = relu4(rv == 0.f ? sv[q] : a);
+        }
+        unit16<T>::template st<NT>(y + i * V, v);
+        st_bits<NV>(signbits + i * NV, v);
+    };
+    RowsWalk w = rows_walk(nunits, per, nps);
+    int64_t i = w.i;
+    int b = w.b, pin = w.pin;
+    for (; i + (int64_t)(SLAB_UNR - 1) * step < w.end; i += (int64_t)SLAB_UNR * step) {
+        raw_t a[SLAB_UNR], r[SLAB_UNR];
+        float rv[SLAB_UNR];
+#pragma unroll
+        for (int u = 0; u < SLAB_UNR; ++u) {
+            const int64_t j = i + (int64_t)u * step;
+            a[u] = unit16<T>::template ldr<NT>(x + j * V);
+            r[u] = unit16<T>::template ldr<NT>(x2 + j * V);
+            rv[u] = rvec[b];
+            rows_next(b, pin, step, nps);
+        }
+#pragma unroll
+        for (int u = 0; u < SLAB_UNR; ++u) one(i + (int64_t)u * step, a[u], r[u], rv[u]);
+    }
+    for (; i < w.end; i += step) {
+        const raw_t a = unit16<T>::template ldr<NT>(x + i * V), r = unit16<T>::template ldr<NT>(x2 + i * V);
+        const float rv = rvec[b];
+        rows_next(b, pin, step, nps);
+        one(i, a, r, rv);
+    }
+}
+
+// gx = k1 (r[b] g) + k2 x + k3, g = gy * bit; DUAL: gx2 = k1b g + k2b x2 + k3b
+template <bool DUAL, bool NT, typename T>
+__global__ __launch_bounds__(256) void bn_bwd_apply_rows_kernel(const T* gy, const uint8_t* bits, const float* rvec, const T* x,
+                                                                const float* k1, const float* k2, const float* k3, T* gx,
+                                                                const T* x2, const float* k1b, const float* k2b, const float* k3b,
+                                                                T* gx2, int64_t nunits, int U, int nps, int step, int64_t per) {
+    constexpr int V = unit16<T>::V, NV = unit16<T>::NV;
+    typedef typename unit16<T>::raw_t raw_t;
+    const int cu = (blockIdx.y * 256 + threadIdx.x) % U;
+    f32x4 a1[NV], a2[NV], a3[NV], b1[NV], b2[NV], b3[NV];
+#pragma unroll
+    for (int q = 0; q < NV; ++q) {
+        const int c = cu * V + 4 * q;
+        a1[q] = ld4(k1 + c); a2[q] = ld4(k2 + c); a3[q] = ld4(k3 + c);
+        if (DUAL) { b1[q] = ld4(k1b + c); b2[q] = ld4(k2b + c); b3[q] = ld4(k3b + c); }
+    }
+    auto one = [&](int64_t i, raw_t gr, raw_t xr, const uint8_t* mb, raw_t wr, float rv) {
+        f32x4 o[NV], g[NV], xv[NV], xw[NV];
+        unit16<T>::cvt(gr, g);
+        unit16<T>::cvt(xr, xv);
+        if (DUAL) unit16<T>::cvt(wr, xw);
+#pragma unroll
+        for (int q = 0; q < NV; ++q) {
+            g[q] = maskbits4(g[q], mb[q]);
+            o[q] = a1[q] * (rv * g[q]) + a2[q] * xv[q] + a3[q];
+        }
+        unit16<T>::template st<NT>(gx + i * V, o);
+        if (DUAL) {
+#pragma unroll
+            for (int q = 0; q < NV; ++q) o[q] = b1[q] * g[q] + b2[q] * xw[q] + b3[q];
+            unit16<T>::template st<NT>(gx2 + i * V, o);
+        }
+    };
+    RowsWalk w = rows_walk(nunits, per, nps);
+    int64_t i = w.i;
+    int b = w.b, pin = w.pin;
+    for (; i + (int64_t)(SLAB_UNR - 1) * step < w.end; i += (int64_t)SLAB_UNR * step) {
+        raw_t g[SLAB_UNR], xv[SLAB_UNR], xw[SLAB_UNR];
+        uint8_t mb[SLAB_UNR][NV];
+        float rv[SLAB_UNR];
+#pragma unroll
+        for (int u = 0; u < SLAB_UNR; ++u) {
+            const int64_t j = i + (int64_t)u * step;
+            g[u] = unit16<T>::template ldr<NT>(gy + j * V);
+            xv[u] = unit16<T>::template ldr<NT>(x + j * V);
+            ld_bits<NV>(bits + j * NV, mb[u]);
+            xw[u] = DUAL ? unit16<T>::template ldr<NT>(x2 + j * V) : g[u];
+            rv[u] = rvec[b];
+            rows_next(b, pin, step, nps);
+        }
+#pragma unroll
+        for (int u = 0; u < SLAB_UNR; ++u) one(i + (int64_t)u * step, g[u], xv[u], mb[u], xw[u], rv[u]);
+    }
+    for (; i < w.end; i += step) {
+        const raw_t g = unit16<T>::template ldr<NT>(gy + i * V), xv = unit16<T>::template ldr<NT>(x + i * V);
+        const raw_t xw = DUAL ? unit16<T>::template ldr<NT>(x2 + i * V) : g;
+        uint8_t mb[NV];
+        ld_bits<NV>(bits + i * NV, mb);
+        const float rv = rvec[b];
+        rows_next(b, pin, step, nps);
+        one(i, g, xv, mb, xw, rv);
+    }
+}
+
+// bn_bwd_reduce_u16_kernel with the sign-bit mask and the factor: [sum r g | sum r g xhat], DUAL: + [sum g | sum g xhat2], into
+// `replicas` accumulators.  Thread (cu, rl) walks the rows rl, rl + RL, ... of its block's slab and with them their samples.
+template <bool DUAL, typename T>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_rows_kernel(const T* gy, const uint8_t* bits, const float* rvec, const T* x,
+                                                                 const float* mean, const float* rstd, const T* x2,
+                                                                 const float* mean2, const float* rstd2, double* sums, int64_t rows,
+                                                                 int U, int rps, int rows_per_block, int replicas, int UB) {
+    constexpr int V = unit16<T>::V, NV = unit16<T>::NV, NS = DUAL ? 4 : 2;
+    __shared__ f32x4 red[NS * NV][256];
+    const int tid = threadIdx.x, cl = tid % UB, cu = blockIdx.y * UB + cl, rl = tid / UB, RL = 256 / UB;
+    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+    int64_t r1 = r0 + rows_per_block;
+    if (r1 > rows) r1 = rows;
+    f32x4 mu[NV], rs[NV], mu2[NV], rs2[NV], srg[NV], srgx[NV], sg[NV], sgx2[NV];
+#pragma unroll
+    for (int q = 0; q < NV; ++q) {
+        const int c = cu * V + 4 * q;
+        mu[q] = ld4(mean + c); rs[q] = ld4(rstd + c);
+        if (DUAL) { mu2[q] = ld4(mean2 + c); rs2[q] = ld4(rstd2 + c); }
+        srg[q] = srgx[q] = sg[q] = sgx2[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    constexpr int UF = DUAL ? 2 : 4;
+    auto fold = [&](f32x4* g, const f32x4* xv, const uint8_t* mb, const f32x4* xw, float rv) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) {
+            g[q] = maskbits4(g[q], mb[q]);
+            const f32x4 rg = rv * g[q];
+            srg[q] += rg;
+            srgx[q] += rg * ((xv[q] - mu[q]) * rs[q]);
+            if (DUAL) { sg[q] += g[q]; sgx2[q] += g[q] * ((xw[q] - mu2[q]) * rs2[q]); }
+        }
+    };
+    int64_t r = r0 + rl;
+    int b = (int)(r / rps), rin = (int)(r - (int64_t)b * rps);
+    for (; r + (int64_t)(UF - 1) * RL < r1; r += (int64_t)UF * RL) {
+        f32x4 g[UF][NV], xv[UF][NV], xw[UF][NV];
+        uint8_t mb[UF][NV];
+        float rv[UF];
+#pragma unroll
+        for (int u = 0; u < UF; ++u) {
+            const int64_t i = (r + (int64_t)u * RL) * U + cu;
+            unit16<T>::ld(gy + i * V, g[u]);
+            unit16<T>::ld(x + i * V, xv[u]);
+            ld_bits<NV>(bits + i * NV, mb[u]);
+            if (DUAL) unit16<T>::ld(x2 + i * V, xw[u]);
+            rv[u] = rvec[b];
+            rows_next(b, rin, RL, rps);
+        }
+#pragma unroll
+        for (int u = 0; u < UF; ++u) fold(g[u], xv[u], mb[u], xw[u], rv[u]);
+    }
+    for (; r < r1; r += RL) {
+        const int64_t i = r * U + cu;
+        f32x4 g[NV], xv[NV], xw[NV];
+        uint8_t mb[NV];
+        unit16<T>::ld(gy + i * V, g);
+        unit16<T>::ld(x + i * V, xv);
+        ld_bits<NV>(bits + i * NV, mb);
+        if (DUAL) unit16<T>::ld(x2 + i * V, xw);
+        const float rv = rvec[b];
+        rows_next(b, rin, RL, rps);
+        fold(g, xv, mb, xw, rv);
+    }
+#pragma unroll
+    for (int q = 0; q < NV; ++q) {
+        red[q][tid] = srg[q];
+        red[NV + q][tid] = srgx[q];
+        if (DUAL) { red[2 * NV + q][tid] = sg[q]; red[3 * NV + q][tid] = sgx2[q]; }
+    }
+    __syncthreads();
+    if (tid < UB) {
+        const int C = U * V;
+        sums += (size_t)(blockIdx.x % replicas) * NS * C;
+#pragma unroll
+        for (int q = 0; q < NV; ++q) {
+            f32x4 a = srg[q], bb = srgx[q], c2 = sg[q], d2 = sgx2[q];
+            for (int k = 1; k < RL; ++k) {
+                a += red[q][tid + k * UB];
+                bb += red[NV + q][tid + k * UB];
+                if (DUAL) { c2 += red[2 * NV + q][tid + k * UB]; d2 += red[3 * NV + q][tid + k * UB]; }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int ch = cu * V + 4 * q + e;
+                atomic_add_f64(sums + ch, (double)a[e]);
+                atomic_add_f64(sums + C + ch, (double)bb[e]);
+                if (DUAL) {
+                    atomic_add_f64(sums + 2 * C + ch, (double)c2[e]);
+                    atomic_add_f64(sums + 3 * C + ch, (double)d2[e]);
+                }
+            }
+        }
+    }
+}
+
+// the sizes every rows entry checks: a channel count the two walks cover, a sample of fewer than 2^30 units
+template <typename T> static inline int rows_check(int32_t B, int64_t rows_per_sample, int32_t C, int* U) {
+    if (B <= 0 || rows_per_sample <= 0 || !(*U = rows_units<T>(C))) return LOANS_EINVAL;
+    if (rows_per_sample * *U >= ((int64_t)1 << 30)) return LOANS_ERANGE;
+    return LOANS_OK;
+}
+
+template <typename T>
+static int bn_apply_rows_impl(const void* x_, const float* scale, const float* shift, const void* x2_, const float* scale2,
+                              const float* shift2, const float* r, void* y_, uint8_t* signbits, int32_t B, int64_t rows_per_sample,
+                              int32_t C, int32_t mode, void* stream) {
+    const T *x = static_cast<const T*>(x_), *x2 = static_cast<const T*>(x2_);
+    T* y = static_cast<T*>(y_);
+    if (!x || !scale || !shift || !x2 || !r || !y || !signbits) return LOANS_EINVAL;
+    if (mode < 1 || mode > 2 || (mode == 2 && (!scale2 || !shift2))) return LOANS_EINVAL;
+    int U;
+    if (int rc = rows_check<T>(B, rows_per_sample, C, &U)) return rc;
+    const int64_t rows = (int64_t)B * rows_per_sample, nunits = rows * U;
+    const RowsPlan p = rows_plan(rows, U);
+    const int nps = (int)(rows_per_sample * U);
+    const bool nt = slab_nt(nunits * 16);
+    hipStream_t st = as_stream(stream);
+#define LAUNCH_AR_(M, N_) hipLaunchKernelGGL((bn_apply_rows_kernel<M, N_, T>), dim3(p.gx, p.gy), dim3(256), 0, st, x, scale, shift, x2, scale2, shift2, r, y, signbits, nunits, U, nps, p.step, p.per)
+#define LAUNCH_AR(M) do { if (nt) LAUNCH_AR_(M, true); else LAUNCH_AR_(M, false); } while (0)
+    if (mode == 1) LAUNCH_AR(1); else LAUNCH_AR(2);
+#undef LAUNCH_AR
+#undef LAUNCH_AR_
+    LOANS_LAUNCH_CHECK();
+    return LOANS_OK;
+}
+
+template <typename T>
+static int bn_bwd_reduce_rows_impl(const void* gy_, const uint8_t* signbits, const float* r, const void* x_, const float* mean,
+                                   const float* rstd, const void* x2_, const float* mean2, const float* rstd2, double* sums,
+                                   int32_t replicas, int32_t B, int64_t rows_per_sample, int32_t C, void* stream) {
+    const T *gy = static_cast<const T*>(gy_), *x = static_cast<const T*>(x_), *x2 = static_cast<const T*>(x2_);
+    if (!gy || !signbits || !r || !x || !mean || !rstd || !sums || (x2 && (!mean2 || !rstd2))) return LOANS_EINVAL;
+    if (replicas < 1 || replicas > 32) return LOANS_EINVAL;
+    int U;
+    if (int rc = rows_check<T>(B, rows_per_sample, C, &U)) return rc;
+    const int64_t rows = (int64_t)B * rows_per_sample;
+    // the geometry of bn_bwd_reduce_impl's 16-byte-unit path (rows per thread, blocks, channel slabs of 16 units)
+    const int UB = U <= 16 ? U : 16, slabs = U / UB, RL = 256 / UB;
+    const int max_blocks = (4096 + slabs - 1) / slabs;
+    int64_t rpb = ((rows + max_blocks - 1) / max_blocks + RL - 1) / RL * RL;
+    int64_t rpt = 32;
+    while (rpt > 4 && ((rows + rpt * RL - 1) / (rpt * RL)) * slabs < 512) rpt >>= 1;
+    if (rpb < rpt * RL) rpb = rpt * RL;
+    if (rpb >= ((int64_t)1 << 31)) return LOANS_ERANGE;
+    const int gx = (int)((rows + rpb - 1) / rpb);
+    hipStream_t st = as_stream(stream);
+#define LAUNCH_RR(D) hipLaunchKernelGGL((bn_bwd_reduce_rows_kernel<D, T>), dim3(gx, slabs), dim3(256), 0, st, gy, signbits, r, x, mean, rstd, x2, mean2, rstd2, sums, rows, U, (int)rows_per_sample, (int)rpb, replicas, UB)
+    if (x2) LAUNCH_RR(true); else LAUNCH_RR(false);
+#undef LAUNCH_RR
+    LOANS_LAUNCH_CHECK();
+    return LOANS_OK;
+}
+
+template <typename T>
+static int bn_bwd_apply_rows_impl(const void* gy_, const uint8_t* signbits, const float* r, const void* x_, const float* k1,
+                                  const float* k2, const float* k3, void* gx_, const void* x2_, const float* k1b, const float* k2b,
+                                  const float* k3b, void* gx2_, int32_t B, int64_t rows_per_sample, int32_t C, void* stream) {
+    const T *gy = static_cast<const T*>(gy_), *x = static_cast<const T*>(x_), *x2 = static_cast<const T*>(x2_);
+    T *gx = static_cast<T*>(gx_), *gx2 = static_cast<T*>(gx2_);
+    if (!gy || !signbits || !r || !x || !k1 || !k2 || !k3 || !gx) return LOANS_EINVAL;
+    if (x2 && (!k1b || !k2b || !k3b || !gx2)) return LOANS_EINVAL;
+    int U;
+    if (int rc = rows_check<T>(B, rows_per_sample, C, &U)) return rc;
+    const int64_t rows = (int64_t)B * rows_per_sample, nunits = rows * U;
+    const RowsPlan p = rows_plan(rows, U);
+    const int nps = (int)(rows_per_sample * U);
+    const bool nt = slab_nt(nunits * 16);
+    hipStream_t st = as_stream(stream);
+#define LAUNCH_PR_(D, N_) hipLaunchKernelGGL((bn_bwd_apply_rows_kernel<D, N_, T>), dim3(p.gx, p.gy), dim3(256), 0, st, gy, signbits, r, x, k1, k2, k3, gx, x2, k1b, k2b, k3b, gx2, nunits, U, nps, p.step, p.per)
+#define LAUNCH_PR(D) do { if (nt) LAUNCH_PR_(D, true); else LAUNCH_PR_(D, false); } while (0)
+    if (x2) LAUNCH_PR(true); else LAUNCH_PR(false);
+#undef LAUNCH_PR
+#undef LAUNCH_PR_
+    LOANS_LAUNCH_CHECK();
+    return LOANS_OK;
+}
+
+}  // namespace
+
+extern "C" int loans_bn_apply_rows_f32(const float* x, const float* scale, const float* shift, const float* x2, const float* scale2,
+                                       const float* shift2, const float* r, float* y, uint8_t* signbits, int32_t B,
+                                       int64_t rows_per_sample, int32_t C, int32_t mode, void* stream) {
+    return bn_apply_rows_impl<float>(x, scale, shift, x2, scale2, shift2, r, y, signbits, B, rows_per_sample, C, mode, stream);
+}
+
+extern "C" int loans_bn_apply_rows_bf16(const void* x, const float* scale, const float* shift, const void* x2, const float* scale2,
+                                        const float* shift2, const float* r, void* y, uint8_t* signbits, int32_t B,
+                                        int64_t rows_per_sample, int32_t C, int32_t mode, void* stream) {
+    return bn_apply_rows_impl<__bf16>(x, scale, shift, x2, scale2, shift2, r, y, signbits, B, rows_per_sample, C, mode, stream);
+}
+
+extern "C" int loans_bn_bwd_reduce_rows_f32(const float* gy, const uint8_t* signbits, const float* r, const float* x,
+                                            const float* mean, const float* rstd, const float* x2, const float* mean2,
+                                            const float* rstd2, double* sums, int32_t replicas, int32_t B, int64_t rows_per_sample,
+                                            int32_t C, void* stream) {
+    return bn_bwd_reduce_rows_impl<float>(gy, signbits, r, x, mean, rstd, x2, mean2, rstd2, sums, replicas, B, rows_per_sample, C, stream);
+}
+
+extern "C" int loans_bn_bwd_reduce_rows_bf16(const void* gy, const uint8_t* signbits, const float* r, const void* x,
+                                             const float* mean, const float* rstd, const void* x2, const float* mean2,
+                                             const float* rstd2, double* sums, int32_t replicas, int32_t B, int64_t rows_per_sample,
+                                             int32_t C, void* stream) {
+    return bn_bwd_reduce_rows_impl<__bf16>(gy, signbits, r, x, mean, rstd, x2, mean2, rstd2, sums, replicas, B, rows_per_sample, C, stream);
+}
+
+extern "C" int loans_bn_bwd_apply_rows_f32(const float* gy, const uint8_t* signbits, const float* r, const float* x, const float* k1,
+                                           const float* k2, const float* k3, float* gx, const float* x2, const float* k1b,
+                                           const float* k2b, const float* k3b, float* gx2, int32_t B, int64_t rows_per_sample,
+                                           int32_t C, void* stream) {
+    return bn_bwd_apply_rows_impl<float>(gy, signbits, r, x, k1, k2, k3, gx, x2, k1b, k2b, k3b, gx2, B, rows_per_sample, C, stream);
+}
+
+extern "C" int loans_bn_bwd_apply_rows_bf16(const void* gy, const uint8_t* signbits, const float* r, const void* x, const float* k1,
+                                            const float* k2, const float* k3, void* gx, const void* x2, const float* k1b,
+                                            const float* k2b, const float* k3b, void* gx2, int32_t B, int64_t rows_per_sample,
+                                            int32_t C, void* stream) {
+    return bn_bwd_apply_rows_impl<__bf16>(gy, signbits, r, x, k1, k2, k3, gx, x2, k1b, k2b, k3b, gx2, B, rows_per_sample, C, stream);
+}

@@ -119,10 +119,14 @@ class ResidualUnitFunction(Function):
       BottleNeckA / BottleNeckB .. sheep/resnet.py:163-216 = chainer ResNet50Layers' blocks (3 stages; 1x1 shortcut / identity)
       chainercv Bottleneck ....... Resnet50SheepLocalizer's res6 / res7 (sheep_localizer.py:131-132)
     ``stages`` = [(conv_link, bn_link), ...], ``shortcut`` = (conv_link, bn_link) or None.
-    inputs: x, then (W, gamma, beta) per stage, then (W, gamma, beta) of the shortcut."""
+    inputs: x, then (W, gamma, beta) per stage, then (W, gamma, beta) of the shortcut.
+    ``drop``: stochastic depth -- the unit's device vector r of B floats (functions/drop_path.py: 0 for a sample whose main branch
+    is dropped, 1 / (1 - p) for a kept one), or None: the junction becomes relu(r_b * bn_n(c_n) + shortcut), its backward hands
+    r_b * g to bn_n and g to the shortcut.  Training only (a unit hands None otherwise: drop_path.unit_vector); everything but the
+    two junction calls is the same.  The rows kernels have the sign-bit form alone, so the bits are written with or without backprop."""
 
-    def __init__(self, stages, shortcut=None):
-        self.stages, self.shortcut = list(stages), shortcut
+    def __init__(self, stages, shortcut=None, drop=None):
+        self.stages, self.shortcut, self.drop = list(stages), shortcut, drop
 
     def forward(self, inputs):
         x = inputs[0]
@@ -156,11 +160,17 @@ class ResidualUnitFunction(Function):
                         continue
                 h = self.h[i] = ops.bn_apply(self.c[i], self.st[i], relu=True)
         bits = config.train and config.enable_backprop     # the backward's ReLU mask as sign bits (ops.bn_apply)
+        drop = self.drop             # (None outside training: drop_path.unit_vector)
         if self.shortcut is not None:
             W, g, b = inputs[1 + 3 * n:4 + 3 * n]
             if not paired:
                 self.cs, self.sts, self.geos = _ConvBN.forward(x, self.shortcut[0], self.shortcut[1], W, None, g, b)
-            self.out = ops.bn_apply(self.c[-1], self.st[-1], relu=True, x2=self.cs, st2=self.sts, want_bits=bits)
+            if drop is not None:
+                self.out = ops.bn_apply_rows(self.c[-1], self.st[-1], drop, x2=self.cs, st2=self.sts)
+            else:
+                self.out = ops.bn_apply(self.c[-1], self.st[-1], relu=True, x2=self.cs, st2=self.sts, want_bits=bits)
+        elif drop is not None:
+            self.out = ops.bn_apply_rows(self.c[-1], self.st[-1], drop, residual=x)
         else:
             self.out = ops.bn_apply(self.c[-1], self.st[-1], relu=True, residual=x, want_bits=bits)
         return self.out
@@ -191,7 +201,14 @@ class ResidualUnitFunction(Function):
         gout = gys[0].contiguous()
         Wl, gl, bl = P[1 + 3 * (n - 1):4 + 3 * (n - 1)]
         gcs = None
-        if self.shortcut is not None:
+        if self.drop is not None:
+            if self.shortcut is not None:
+                Ws, gs, bs = P[1 + 3 * n:4 + 3 * n]
+                g, gcs = ops.bn_backward_rows(gout, self.out, self.drop, self.c[-1], self.st[-1], gl.data, gl.grad_view, bl.grad_view,
+                                              x2=self.cs, st2=self.sts, gamma2=gs.data, ggamma2=gs.grad_view, gbeta2=bs.grad_view)
+            else:
+                g = ops.bn_backward_rows(gout, self.out, self.drop, self.c[-1], self.st[-1], gl.data, gl.grad_view, bl.grad_view)
+        elif self.shortcut is not None:
             Ws, gs, bs = P[1 + 3 * n:4 + 3 * n]
             g, gcs = ops.bn_backward(gout, self.out, self.c[-1], self.st[-1], gl.data, gl.grad_view, bl.grad_view,
                                      x2=self.cs, st2=self.sts, gamma2=gs.data, ggamma2=gs.grad_view, gbeta2=bs.grad_view)
@@ -235,11 +252,11 @@ class ResidualUnitFunction(Function):
         self.x = self.c = self.h = self.st = self.out = self.cs = None
 
 
-def residual_unit(x, stages, shortcut=None):
+def residual_unit(x, stages, shortcut=None, drop=None):
     args = [x]
     for conv, bn in list(stages) + ([shortcut] if shortcut is not None else []):
         args += [conv.W, bn.gamma, bn.beta]
-    return ResidualUnitFunction(stages, shortcut)(*args)
+    return ResidualUnitFunction(stages, shortcut, drop)(*args)
 
 
 # --------------------------------------------------------------------------- #

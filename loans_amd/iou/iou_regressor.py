@@ -11,7 +11,7 @@ converted Caffe model that is not available offline; weights are HeNormal(scale=
 import collections
 
 from .. import links as L
-from ..functions import blocks
+from ..functions import blocks, drop_path
 from ..functions import global_average_pooling_2d, linear
 from ..runtime.core import Chain
 
@@ -31,7 +31,7 @@ class BottleneckA(Chain):
 
     def __call__(self, x):
         return blocks.residual_unit(x, [(self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)],
-                                    (self.conv4, self.bn4))
+                                    (self.conv4, self.bn4), drop=drop_path.unit_vector(self))
 
 
 class BottleneckB(Chain):
@@ -46,7 +46,8 @@ class BottleneckB(Chain):
             self.bn3 = L.BatchNormalization(in_channels)
 
     def __call__(self, x):
-        return blocks.residual_unit(x, [(self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)])
+        return blocks.residual_unit(x, [(self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)],
+                                    drop=drop_path.unit_vector(self))
 
 
 class BuildingBlock(Chain):
@@ -66,7 +67,7 @@ class BuildingBlock(Chain):
         return x
 
 
-class ResNet50Layers(Chain):
+class ResNet50Layers(Chain, drop_path.DropPathOwner):
     def __init__(self, pretrained_model='auto'):
         super().__init__()
         w = L.HeNormal(scale=1.0)
@@ -81,6 +82,10 @@ class ResNet50Layers(Chain):
         self.pretrained_model = pretrained_model
 
     exchange_stages = ('res4', 'res5')        # see sheep/resnet.py
+
+    def drop_path_stages(self):
+        """the stages whose residual units ``set_drop_path`` counts, in forward order"""
+        return [self.res2, self.res3, self.res4, self.res5]
 
     def _stem(self, x):
         return blocks.StemFunction(self.conv1, self.bn1)(x, self.conv1.W, self.conv1.b, self.bn1.gamma, self.bn1.beta)
@@ -111,6 +116,7 @@ class ResNet50Layers(Chain):
 
     def __call__(self, x, layers=['prob']):
         h = x
+        self.draw_drop_path(x.shape[0], x.data.device)      # stochastic depth: one keep table per training forward
         activations = {}
         target_layers = set(layers)
         for key, funcs in self.functions.items():

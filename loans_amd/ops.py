@@ -2274,6 +2274,63 @@ def bn_backward(gy, mask, x, st, gamma, ggamma, gbeta, x2=None, st2=None, gamma2
     return (gx, gx2) if dual else gx
 
 
+def bn_apply_rows(x, st, r, residual=None, x2=None, st2=None):
+    """The junction of a residual unit under stochastic depth: y = relu(r[b] * bn(x) + residual | + bn2(x2)) for the samples b
+    of the NHWC tensor x, ``r`` a device vector of B floats (0: the sample's main branch is dropped, 1 / (1 - p): kept).  Always
+    with the sign bits, hung on the result as ``y.relu_bits`` like bn_apply(..., want_bits=True)."""
+    B, C_ = x.shape[0], x.shape[-1]
+    rps = x.numel() // (B * C_)
+    assert (residual is None) != (x2 is None) and r.dtype == torch.float32 and r.numel() == B
+    mode, second = (1, residual) if residual is not None else (2, x2)
+    assert second.dtype == x.dtype and second.shape == x.shape
+    y = _empty_like(x)
+    bits = _empty(B * rps * (C_ // 4), device=x.device, dtype=torch.uint8)
+    if CLASS_COUNT is not None: _acct('bn_fwd', 0, _nbytes(x, second, r), _nbytes(y, bits))
+    lib = _lib.load()
+    fn = lib.loans_bn_apply_rows_bf16 if _is16(x) else lib.loans_bn_apply_rows_f32
+    check(fn(_ptr(x), _ptr(st.scale), _ptr(st.shift), _ptr(second), _ptr(st2.scale if st2 else None),
+             _ptr(st2.shift if st2 else None), _ptr(r), _ptr(y), _ptr(bits), B, rps, C_, mode, _stream()), 'loans_bn_apply_rows')
+    y.relu_bits = bits
+    return y
+
+
+def bn_backward_rows(gy, out, r, x, st, gamma, ggamma, gbeta, x2=None, st2=None, gamma2=None, ggamma2=None, gbeta2=None):
+    """bn_backward for the junction bn_apply_rows made: g = gy * (out > 0) from ``out.relu_bits``; the last BN (x, st) takes
+    r[b] g, the shortcut BN (x2, st2) g.  Accumulates ggamma / gbeta in place, returns gx (and gx2): reduce -> coefficients from
+    the replicas (the launches of bn_backward) -> apply."""
+    lib = _lib.load()
+    B, C_ = x.shape[0], x.shape[-1]
+    rps = x.numel() // (B * C_)
+    rows = B * rps
+    dual = x2 is not None
+    s16 = _is16(x)
+    bits = out.relu_bits
+    assert _is16(gy) == s16 and (x2 is None or _is16(x2) == s16) and bits.numel() == rows * (C_ // 4) and r.numel() == B
+    if CLASS_COUNT is not None: _acct('bn_bwd', 0, 2 * _nbytes(gy, x, x2, bits, r), _nbytes(x) * (2 if dual else 1))
+    s = _stream()
+    ns = 4 if dual else 2
+    sums = _zeros_f64((STATS_REPLICAS, ns, C_), x.device)
+    red = lib.loans_bn_bwd_reduce_rows_bf16 if s16 else lib.loans_bn_bwd_reduce_rows_f32
+    check(red(_ptr(gy), _ptr(bits), _ptr(r), _ptr(x), _ptr(st.mean), _ptr(st.rstd), _ptr(x2), _ptr(st2.mean if dual else None),
+              _ptr(st2.rstd if dual else None), _ptr(sums), STATS_REPLICAS, B, rps, C_, s), 'loans_bn_bwd_reduce_rows')
+    k = _empty((6 if dual else 3, C_), device=x.device, dtype=torch.float32)
+    check(lib.loans_bn_bwd_coeffs_rep_f32(_ptr(sums), STATS_REPLICAS, ns * C_, 0, C_, rows, _ptr(gamma), _ptr(st.mean),
+                                          _ptr(st.rstd), _ptr(ggamma), _ptr(gbeta), _ptr(k[0]), _ptr(k[1]), _ptr(k[2]), s),
+          'loans_bn_bwd_coeffs_rep_f32')
+    gx = _empty_like(x)
+    gx2 = None
+    if dual:
+        check(lib.loans_bn_bwd_coeffs_rep_f32(_ptr(sums[0, 2]), STATS_REPLICAS, ns * C_, 0, C_, rows, _ptr(gamma2), _ptr(st2.mean),
+                                              _ptr(st2.rstd), _ptr(ggamma2), _ptr(gbeta2), _ptr(k[3]), _ptr(k[4]), _ptr(k[5]), s),
+              'loans_bn_bwd_coeffs_rep_f32')
+        gx2 = _empty_like(x2)
+    app = lib.loans_bn_bwd_apply_rows_bf16 if s16 else lib.loans_bn_bwd_apply_rows_f32
+    check(app(_ptr(gy), _ptr(bits), _ptr(r), _ptr(x), _ptr(k[0]), _ptr(k[1]), _ptr(k[2]), _ptr(gx), _ptr(x2),
+              _ptr(k[3]) if dual else 0, _ptr(k[4]) if dual else 0, _ptr(k[5]) if dual else 0, _ptr(gx2), B, rps, C_, s),
+          'loans_bn_bwd_apply_rows')
+    return (gx, gx2) if dual else gx
+
+
 def bn_backward_from_sums(gy, x, st, sums, gamma, ggamma, gbeta):
     """bn_backward(gy, relu(bn(x)), x, st, ..., mask_is_own_relu=True) with the reduction already done: `sums` are the
     [replicas][2][C] accumulators conv_dgrad(..., bn_sums=(x, st)) filled while gy was in registers.  One pass over the

@@ -10,11 +10,11 @@ instantiate (18 / 20 / 34) are built; the bottleneck variants
 ``class_labels=K`` adds the ImageNet head of sheep/resnet.py:65-87: global average pooling and ``fc = L.Linear(None, K)``.
 """
 from .. import links as L
-from ..functions import blocks, global_average_pooling_2d, linear
+from ..functions import blocks, drop_path, global_average_pooling_2d, linear
 from ..runtime.core import Chain, ChainList
 
 
-class ResNet(Chain):
+class ResNet(Chain, drop_path.DropPathOwner):
 
     def __init__(self, n_layers, class_labels=None):
         super(ResNet, self).__init__()
@@ -54,10 +54,15 @@ class ResNet(Chain):
         if self.class_labels is not None:
             self.fc.ensure_initialized(512)
 
+    def drop_path_stages(self):
+        """the stages whose residual units ``set_drop_path`` counts, in forward order"""
+        return [getattr(self, n) for n in ('res2', 'res3', 'res4', 'res5', 'res6', 'res7') if hasattr(self, n)]
+
     def __call__(self, x):
         """x: preprocessed frames (``prepare_images``: the padded packed-RGB buffer conv1 reads).  Returns the NHWC feature map,
         or the (B, class_labels) logits when the model has the classification head."""
         self.materialize_head()
+        self.draw_drop_path(x.shape[0], x.data.device)      # stochastic depth: one keep table per training forward
         h = blocks.StemFunction(self.conv1, self.bn1)(x, self.conv1.W, self.conv1.b, self.bn1.gamma, self.bn1.beta)
         h = self.res2(h)
         h = self.res3(h)
@@ -105,7 +110,8 @@ class BasicA(Chain):
             self.bn3 = L.BatchNormalization(ch)
 
     def __call__(self, x):
-        return blocks.residual_unit(x, [(self.conv1, self.bn1), (self.conv2, self.bn2)], (self.conv3, self.bn3))
+        return blocks.residual_unit(x, [(self.conv1, self.bn1), (self.conv2, self.bn2)], (self.conv3, self.bn3),
+                                    drop=drop_path.unit_vector(self))
 
 
 class BasicB(Chain):
@@ -120,4 +126,4 @@ class BasicB(Chain):
             self.bn2 = L.BatchNormalization(ch)
 
     def __call__(self, x):
-        return blocks.residual_unit(x, [(self.conv1, self.bn1), (self.conv2, self.bn2)])
+        return blocks.residual_unit(x, [(self.conv1, self.bn1), (self.conv2, self.bn2)], drop=drop_path.unit_vector(self))

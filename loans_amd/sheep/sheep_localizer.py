@@ -16,6 +16,7 @@ from .. import ops
 from ..common.utils import Size
 from ..functions import (global_average_pooling_2d, linear, reshape, rotation_dropout,
                          spatial_transformer_grid, spatial_transformer_sampler)
+from ..functions.drop_path import DropPathOwner
 from ..functions.ops_small import ExposeNCHW, rois_to_grayscale
 from ..runtime.core import Chain, Variable, as_variable, config, using_config
 from ..chainercv_resnet import ResBlock
@@ -31,7 +32,7 @@ def _as_device_batch(images, device):
     return images.to(device=device, dtype=torch.float32).contiguous()
 
 
-class SheepLocalizer(Chain):
+class SheepLocalizer(Chain, DropPathOwner):
 
     def __init__(self, out_size, transform_rois_to_grayscale=False, train_imagenet=False):
         super().__init__()
@@ -54,10 +55,16 @@ class SheepLocalizer(Chain):
         self.transform_rois_to_grayscale = transform_rois_to_grayscale
         self.train_imagenet = train_imagenet
 
+    def drop_path_stages(self):
+        """the backbone's stages, then res6 / res7 where the localizer has them (``set_drop_path`` counts the units of all of
+        them, whatever the frame height runs)"""
+        return self.feature_extractor.drop_path_stages() + [getattr(self, n) for n in ('res6', 'res7') if hasattr(self, n)]
+
     def __call__(self, images):
         self.visual_backprop_anchors.clear()
         device = images.data.device if isinstance(images, Variable) else (
             images.device if torch.is_tensor(images) and images.is_cuda else torch.device('cuda', torch.cuda.current_device()))
+        self.draw_drop_path(images.shape[0], device)        # stochastic depth: one keep table per training forward
         if self.train_imagenet:             # ImageNet pre-training: the logits of the backbone's own head
             self.feature_extractor.materialize_head()
             self.finalize(device)
@@ -180,6 +187,7 @@ class Resnet50SheepLocalizer(SheepLocalizer):
             images.device if torch.is_tensor(images) and images.is_cuda else torch.device('cuda', torch.cuda.current_device()))
         self.finalize(device)
         images = _as_device_batch(images, device)
+        self.draw_drop_path(images.shape[0], device)        # stochastic depth: one keep table per training forward
         if self.train_imagenet:
             return self.feature_extractor(self.prepare_images(images), layers=['fc6'])['fc6']
         height = images.shape[-2]

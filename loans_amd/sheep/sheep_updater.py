@@ -11,6 +11,7 @@ import torch
 from .. import ops
 from ..common.utils import DirectionLossCalculator, OutOfImageLossCalculator, Size
 from ..functions import mean_squared_error
+from ..functions.drop_path import refuse_captured_step
 from ..runtime import training
 from ..runtime.core import Variable, report, reporter
 
@@ -97,6 +98,7 @@ class SheepAssessor(training.StandardUpdater):
         ins = [t.data if isinstance(t, Variable) else t for t in (real_images, labels, fake_images)]
         g = self._graph
         if g is None:
+            refuse_captured_step(self.localizer)    # stochastic depth draws on the host in every step: refused, with a sentence
             if self.iteration < self.graph_warmup:
                 return self._step(real_images, labels, fake_images)
             dev = torch.device('cuda', self.device) if isinstance(self.device, int) else self.device

@@ -5,6 +5,7 @@ say what the head costs: the flop counts of the three head GEMMs against the bac
     python tools/imagenet_step.py -b 256 --steps 20 --warmup 5             (step time, ms: median / min / max)
     python tools/imagenet_step.py -b 256 --resnet-50 --loss bce --bce-target-thresh 0.2
         (the ResNet-50 localizer, the sigmoid binary cross-entropy on the label-smoothed target: tools/bce_bench.py)
+    python tools/imagenet_step.py -b 256 --resnet-50 --drop-path 0.05     (stochastic depth: tools/droppath_bench.py)
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/imagenet_step.py -b 256 --steps 3 --warmup 2
         (per-kernel times: gemm_tile_kernel / colsum_ordered_kernel / softmax_xent_* are the head and the loss)
 """
@@ -34,6 +35,7 @@ def main(argv=None):
     ap.add_argument('--loss', default='softmax', choices=['softmax', 'bce'])
     ap.add_argument('--bce-target-thresh', type=float, default=None)
     ap.add_argument('--label-smoothing', type=float, default=0.0)
+    ap.add_argument('--drop-path', type=float, default=0.0, help='stochastic depth at this rate (tools/droppath_bench.py)')
     ap.add_argument('--out', default=None, help='also write the JSON result here')
     a = ap.parse_args(argv)
     assert torch.cuda.is_available(), 'this measurement needs a GPU'
@@ -43,6 +45,8 @@ def main(argv=None):
     localizer = loans_amd.Resnet50SheepLocalizer if a.resnet_50 else loans_amd.SheepLocalizer
     options = dict(loss='bce', bce_target_threshold=a.bce_target_thresh) if a.loss == 'bce' else {}
     model = loans_amd.Classifier(localizer((75, 75), train_imagenet=True), label_smoothing=a.label_smoothing, **options)
+    if a.drop_path > 0:
+        model.predictor.set_drop_path(a.drop_path, seed=0)
     if a.dtype == 'bf16':
         model.set_precision('bf16', 'bf16')
     x, t = synthetic.make_classification_set(0, min(B, 64), 1000, H, W)
@@ -64,7 +68,7 @@ def main(argv=None):
         e1.synchronize()
         times.append(e0.elapsed_time(e1))
     head_flop = 3 * 2 * B * (2048 if a.resnet_50 else 512) * 1000
-    res = {'what': 'imagenet_step', 'dtype': a.dtype, 'localizer': localizer.__name__, 'loss_function': a.loss, 'batch': B, 'image_size': [H, W], 'steps': a.steps,
+    res = {'what': 'imagenet_step', 'dtype': a.dtype, 'localizer': localizer.__name__, 'loss_function': a.loss, 'drop_path': a.drop_path, 'batch': B, 'image_size': [H, W], 'steps': a.steps,
            'step_ms_median': float(np.median(times)), 'step_ms_min': float(min(times)), 'step_ms_max': float(max(times)),
            'images_per_s': B / (float(np.median(times)) * 1e-3), 'head_gflop': head_flop / 1e9,
            'loss': float(loans_amd.reporter.observation['loss']), 'accuracy': float(loans_amd.reporter.observation['accuracy'])}

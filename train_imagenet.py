@@ -150,16 +150,32 @@ the training loss -- and may change on resume.
         --cutmix-alpha 1.0 --color-jitter 0.4 0.4 0.4 --random-erase-prob 0.25 --rand-augment 2 9 --ema-decay 0.9999 \
         --clip-grad-norm 1.0 --loss bce --bce-target-thresh 0.2
 
+``--drop-path P`` (``0 <= P < 1``; default 0: off) is stochastic depth, the regulariser of the same procedures (A1 / A2: 0.05):
+torchvision's ``StochasticDepth(mode='row')``, timm's ``drop_path``.  Residual unit l of the backbone's L (8 in the ResNet-18
+variant, 16 in ResNet-50), in forward order, has the rate ``p_l = P l / (L - 1)``; in a training step every sample drops the
+unit's main branch with that probability and a kept one is scaled by ``1 / (1 - p_l)``: ``relu(r_b * bn(conv(..)) + shortcut)``.
+The BN statistics are taken over all samples as before, validation (the averaged model's too) drops nothing, and a unit whose
+rate is 0 -- every unit without the option -- runs the launches it always ran.  The keep table of a step is drawn on the host
+from a stream of its own (``--drop-path-seed``, rank r from seed + 7919 r: the ranks drop different samples) and goes up in one
+asynchronous copy; the junction's three passes are kernels of their own (loans_amd/functions/drop_path.py, csrc/bn_pool.hip:
+``loans_bn_*_rows_*``).  Works with every ``--optimizer``, ``--dtype``, ``--loss`` and ``--gpus N``; both options are fixed on resume,
+and the stream's state is part of the checkpoint.
+
+    python train_imagenet.py train.tsv val.tsv --gpus 8 -b 256 --dtype bf16 --optimizer lamb --lr 5e-3 --weight-decay 0.02 \
+        --no-decay-1d --lr-schedule cosine --lr-min 1e-6 --warmup-epochs 5 --num-epoch 300 --augment rrc --mixup-alpha 0.2 \
+        --cutmix-alpha 1.0 --color-jitter 0.4 0.4 0.4 --random-erase-prob 0.25 --rand-augment 2 9 --ema-decay 0.9999 \
+        --clip-grad-norm 1.0 --loss bce --bce-target-thresh 0.2 --drop-path 0.05
+
 ``--checkpoint-interval N`` writes a full-state checkpoint, ``checkpoint_<iteration>.npz`` in the log directory, after every
 N-th iteration and after the last one (default 0: none; ``--checkpoint-keep K``, default 2, keeps the newest K): the model with
 its BN statistics, the optimiser's buffers and step count, the training iterator as of the batch the step consumed (shuffle
-stream, order, position, the crop / mirror draw stream, the RandAugment, the photometric and the mix draw stream), NumPy's global stream and the run's arguments
+stream, order, position, the crop / mirror draw stream, the RandAugment, the photometric and the mix draw stream), the stochastic depth draw stream, NumPy's global stream and the run's arguments
 (loans_amd/runtime/checkpoint.py; under ``--gpus N`` one small record per rank beside rank 0's file, which is written last).
 ``--resume PATH`` -- a checkpoint file, or a log directory, whose newest complete checkpoint is taken -- continues that run in
 its log directory: the ``log`` file is read back and appended to, ``elapsed_time`` and the snapshot names count on.  Fixed on
 resume (one error lists every one that differs): the architecture, ``--dtype``, ``--optimizer``, ``-b``, ``--gpus``,
 ``--image-size``, the dataset files or the synthetic sizes, classes and ``--data-seed``, ``--no-shuffle``, ``--augment`` /
-``--rrc-*`` / ``--val-crop-pct`` / ``--augment-seed``, ``--mixup-alpha`` / ``--cutmix-alpha`` / ``--mix-*``, ``--color-jitter`` / ``--lighting-std`` / ``--random-erase-*`` / ``--photo-seed``, ``--rand-augment`` / ``--trivial-augment`` / ``--ra-fill`` / ``--ra-seed``, ``--ema-decay`` (a checkpoint from
+``--rrc-*`` / ``--val-crop-pct`` / ``--augment-seed``, ``--mixup-alpha`` / ``--cutmix-alpha`` / ``--mix-*``, ``--color-jitter`` / ``--lighting-std`` / ``--random-erase-*`` / ``--photo-seed``, ``--rand-augment`` / ``--trivial-augment`` / ``--ra-fill`` / ``--ra-seed``, ``--drop-path`` / ``--drop-path-seed``, ``--ema-decay`` (a checkpoint from
 before these options existed ran at their defaults), ``--seed``.  Taken from the new command line (each one that differs is
 printed once): ``--num-epoch``, ``--iterations``, the log, snapshot and checkpoint intervals, ``--loader-threads``, the frame
 cache options, ``--lr``, ``--weight-decay``, ``--momentum``, ``--lr-drop-*``, ``--lr-schedule``, ``--lr-min``, ``--no-decay-1d``, ``--lars-eta``, ``--lars-eps``, ``--lamb-beta1``, ``--lamb-beta2``, ``--lamb-eps``, ``--clip-grad-norm``, ``--warmup-*``, ``--label-smoothing``, ``--topk``, ``--loss``, ``--bce-target-thresh``, ``--bce-sum``.  The
@@ -204,7 +220,7 @@ RESUME_FIXED = ('use_resnet_18', 'dtype', 'optimizer', 'batch_size', 'gpus', 'im
                 'validation_size', 'synthetic_classes', 'data_seed', 'no_shuffle', 'augment', 'rrc_scale', 'rrc_ratio', 'val_crop_pct',
                 'augment_seed', 'seed', 'mixup_alpha', 'cutmix_alpha', 'mix_prob', 'mix_switch_prob', 'mix_seed', 'ema_decay',
                 'color_jitter', 'lighting_std', 'random_erase_prob', 'random_erase_scale', 'random_erase_ratio', 'random_erase_value',
-                'photo_seed', 'rand_augment', 'trivial_augment', 'ra_fill', 'ra_seed')
+                'photo_seed', 'rand_augment', 'trivial_augment', 'ra_fill', 'ra_seed', 'drop_path', 'drop_path_seed')
 
 
 class SyntheticClasses:
@@ -307,6 +323,11 @@ class Arguments(argparse.Namespace):
     bce_sum = False
     _LOSS = ('loss', 'bce_target_thresh', 'bce_sum')
 
+    # --drop-path: stochastic depth in the residual units (loans_amd/functions/drop_path.py); 0: off, logged only where given
+    drop_path = 0.0
+    drop_path_seed = None
+    _DROP = ('drop_path', 'drop_path_seed')
+
 
 def parse_args(argv=None):
     parser = argparse.ArgumentParser(description="ImageNet pre-training of a localizer backbone (MI355X-native)")
@@ -392,6 +413,9 @@ def parse_args(argv=None):
     parser.add_argument("--loss", default=argparse.SUPPRESS, choices=['softmax', 'bce'], help="softmax cross-entropy (default) or the per-class sigmoid binary cross-entropy on the same smoothed / mixed target; the validation loss is the plain softmax cross-entropy either way")
     parser.add_argument("--bce-target-thresh", type=float, default=argparse.SUPPRESS, metavar='T', help="with --loss bce: make the target 0 / 1 by target > T, T in [0, 1) (default: the soft target)")
     parser.add_argument("--bce-sum", action='store_true', default=argparse.SUPPRESS, help="with --loss bce: sum the loss over the classes instead of averaging it (the mean over the rows either way)")
+    # stochastic depth
+    parser.add_argument("--drop-path", type=float, default=argparse.SUPPRESS, metavar='P', help="stochastic depth: in training, residual unit l of L drops its main branch per sample with probability P l / (L - 1) and scales the kept ones by 1 / (1 - p), P in [0, 1) (default 0: off)")
+    parser.add_argument("--drop-path-seed", type=int, default=argparse.SUPPRESS, help="seed of the stochastic depth draws (a stream of their own)")
     checkpoint.add_arguments(parser, argparse.SUPPRESS)
     args = parser.parse_args(argv, namespace=Arguments())
     try:
@@ -404,10 +428,11 @@ def parse_args(argv=None):
         check_lamb_arguments(args)
         check_clip_arguments(args)
         check_loss_arguments(args)
+        check_drop_arguments(args)
         if args.resume is not None:
             check_average_resume(args)
             world = os.environ.get('WORLD_SIZE')        # a rank under a launcher: the group's size, whatever --gpus says
-            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS_WITH_RA)
+            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS_WITH_DROP)
     except ValueError as e:
         parser.error(str(e))
     return args
@@ -531,6 +556,12 @@ def check_loss_arguments(args):
         raise ValueError('--bce-target-thresh / --bce-sum belong to --loss bce')
 
 
+def check_drop_arguments(args):
+    """ValueError for a --drop-path that is no probability below 1"""
+    if not 0.0 <= args.drop_path < 1.0:
+        raise ValueError('--drop-path is the largest drop probability of a residual unit: it must lie in [0, 1), got %r' % args.drop_path)
+
+
 AVERAGE_RESUME = {False: '--resume: the checkpoint was written without --ema-decay and holds no weight average: resume it without the option',
                   True: '--resume: the checkpoint was written with --ema-decay %g and holds a weight average: resume it with the option'}
 
@@ -562,9 +593,12 @@ RESUME_DEFAULTS_WITH_CLIP = dict(RESUME_DEFAULTS_WITH_LAMB, **RESUME_DEFAULTS_CL
 # ... and for --loss / --bce-target-thresh / --bce-sum
 RESUME_DEFAULTS_LOSS = {name: getattr(Arguments, name) for name in Arguments._LOSS}
 RESUME_DEFAULTS_WITH_LOSS = dict(RESUME_DEFAULTS_WITH_CLIP, **RESUME_DEFAULTS_LOSS)
-# ... and for --rand-augment / --trivial-augment / --ra-fill / --ra-seed; this is the table --resume uses
+# ... and for --rand-augment / --trivial-augment / --ra-fill / --ra-seed
 RESUME_DEFAULTS_RA = {name: getattr(Arguments, name) for name in Arguments._RA}
 RESUME_DEFAULTS_WITH_RA = dict(RESUME_DEFAULTS_WITH_LOSS, **RESUME_DEFAULTS_RA)
+# ... and for --drop-path / --drop-path-seed; this is the table --resume uses
+RESUME_DEFAULTS_DROP = {name: getattr(Arguments, name) for name in Arguments._DROP}
+RESUME_DEFAULTS_WITH_DROP = dict(RESUME_DEFAULTS_WITH_RA, **RESUME_DEFAULTS_DROP)
 
 
 def cache_budgets(total_bytes, n_train, n_validation):
@@ -694,6 +728,8 @@ def run(args, log=print):
     # ... and the _RA options
     ra_given = any((tuple(v) if isinstance(v, (list, tuple)) else v) != getattr(Arguments, name)
                    for name, v in ((name, getattr(args, name)) for name in Arguments._RA))
+    # ... and the _DROP options
+    drop_given = any(getattr(args, name) != getattr(Arguments, name) for name in Arguments._DROP)
     args.gpus = comm.size
     check_cache_arguments(args)
     check_mix_arguments(args)
@@ -704,6 +740,7 @@ def run(args, log=print):
     check_lamb_arguments(args)
     check_clip_arguments(args)
     check_loss_arguments(args)
+    check_drop_arguments(args)
     chief = comm.rank == 0                     # prints, logs and writes snapshots
 
     # --augment rrc: the iterators hand out (frames, labels) already resident on the device
@@ -767,6 +804,10 @@ def run(args, log=print):
         model.set_precision('bf16', 'bf16')
     model.to_gpu(args.gpu)
     comm.bcast_data(model)
+    drop = None
+    if args.drop_path > 0:
+        # every rank drops samples of its own batch, with draws of its own: the stream of --drop-path-seed + 7919 r
+        drop = localizer.set_drop_path(args.drop_path, None if args.drop_path_seed is None else args.drop_path_seed + 7919 * comm.rank)
 
     if args.optimizer == 'lars':
         optimizer, rate_name = loans_amd.LARS(lr=args.learning_rate, momentum=args.momentum, weight_decay_rate=args.weight_decay,
@@ -834,7 +875,7 @@ def run(args, log=print):
         # the run continues in the checkpoint's log directory: no new <time>_<name>
         check_average_resume(args)
         resumed, changed = checkpoint.resolve_resume(args, RESUME_FIXED, log if chief else (lambda line: None), world=comm.size,
-                                                     defaults=RESUME_DEFAULTS_WITH_RA)
+                                                     defaults=RESUME_DEFAULTS_WITH_DROP)
         args.log_dir = os.path.dirname(os.path.abspath(args.resume))
         for line in changed if chief else ():
             log(line)
@@ -854,6 +895,8 @@ def run(args, log=print):
             continue
         if argument in Arguments._RA and not ra_given:
             continue
+        if argument in Arguments._DROP and not drop_given:
+            continue
         if argument in Arguments._LARS and args.optimizer != 'lars':
             continue        # a run with another optimiser logs what it always logged
         if argument in Arguments._LAMB and args.optimizer != 'lamb':
@@ -868,6 +911,8 @@ def run(args, log=print):
     state = dict(models={'model': model}, optimizers={'main': optimizer}, iterators={'main': train_iter}, comm=comm)
     if average is not None:
         state['optimizers']['ema'] = average    # the shape of an optimiser's record: class, t, hyperparam, state
+    if drop is not None:
+        state['iterators']['drop_path'] = drop  # the shape of an iterator's record: a rank's own draw stream
 
     def snapshot_path(it, tag=''):
         return os.path.join(args.log_dir, '%s_%s%d.npz' % (localizer.__class__.__name__, tag, it))
