@@ -52,6 +52,8 @@ NO_DGRAD = ('pw512', 'pw576', 'cin4')
 TILES = (1, 2, 3, 4, 17, 18, 19, 20)           # 128x128, 128x64, 64x64, 256x64; + 16 = LOANS_TILE_DMA
 BOUND = 2e-6
 
+FINE_TAIL_GEOM = (3, 96, 11, 11, 3072, 3, 1, 1)     # B, Cin, H, W, Cout, k, stride, pad of test_conv_tap_loop_fine_tail
+
 _cache = {}
 
 
@@ -183,7 +185,7 @@ def test_conv_tap_loop_fine_tail():
     K slices.  363 rows x 3072 channels are 288 tiles: on 256 CUs 240 at full K and 48 in slices of 27 chunks' fifth or
     sixth, which start inside a tap of three chunks.  With bias and statistics, as the tuned forward launches it."""
     from loans_amd import ops
-    B, Cin, H, W, Cout, k, s, p = 3, 96, 11, 11, 3072, 3, 1, 1
+    B, Cin, H, W, Cout, k, s, p = FINE_TAIL_GEOM
     rng = np.random.RandomState(77)
     x = rng.standard_normal((B, Cin, H, W)).astype(np.float32)
     w = (rng.standard_normal((Cout, Cin, k, k)) / np.sqrt(Cin * k * k)).astype(np.float32)

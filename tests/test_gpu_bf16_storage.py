@@ -1,7 +1,13 @@
 """-m gpu: the bf16 STORAGE arm (BASELINE configs 3 / 5) -- every kernel that reads or writes bf16 tensors, through the
 C ABI, against the CPU oracle evaluated on the bf16-rounded operands.  A bf16 result is the fp32 result rounded once
 (relative 2^-9 at most), so comparisons of bf16 outputs use 2^-8; fp32 outputs (weight gradients, statistics) keep
-fp32-accumulation tolerances."""
+fp32-accumulation tolerances.
+
+That bound cannot tell one round-to-nearest-even from a truncation, a round-half-away or a second rounding, nor statistics
+taken from the fp32 accumulators from statistics of the stored bf16.  "Rounded once" -- and "from the accumulators", the
+ROUNDED g of LOANS_F_BNSUMS, the bit identity of the tiles -- is ENFORCED in tests/conv_exact/test_gpu_bf16_storage.py, on
+integer operands whose exact result is known to the bit; the case lists of this file are module-level
+names because that package imports them."""
 import numpy as np
 import pytest
 import torch
@@ -110,8 +116,11 @@ def test_conv_bf16_storage(case, tile):
         assert rel_err(dw.cpu().numpy().transpose(0, 3, 1, 2), gwr_ref) < 1e-5
 
 
-@pytest.mark.parametrize("case", [(3, 64, 14, 14, 64), (2, 128, 20, 33, 128), (2, 64, 9, 50, 256), (1, 192, 8, 16, 64),
-                                  (5, 64, 17, 12, 128), (2, 256, 32, 32, 256)])
+WGHALO_CASES = [(3, 64, 14, 14, 64), (2, 128, 20, 33, 128), (2, 64, 9, 50, 256), (1, 192, 8, 16, 64),
+                (5, 64, 17, 12, 128), (2, 256, 32, 32, 256)]
+
+
+@pytest.mark.parametrize("case", WGHALO_CASES)
 @pytest.mark.parametrize("tile", [38, 39])
 def test_weight_gradient_halo_tiles(case, tile):
     """LOANS_TILE_WGHALO_64 / _128 (csrc/wgrad_halo_bf16.hip): a block holds all nine taps of a stride-1 3x3 weight gradient
@@ -148,9 +157,12 @@ def test_weight_gradient_halo_tiles(case, tile):
 
 
 
-@pytest.mark.parametrize("case", [(3, 64, 14, 14, 64, 3, 1, 1, 38), (2, 128, 20, 33, 128, 3, 1, 1, 39), (2, 128, 20, 33, 128, 3, 1, 1, 1),
-                                  (4, 64, 16, 16, 256, 1, 1, 0, 1), (2, 64, 15, 13, 128, 3, 2, 1, 3), (2, 256, 8, 8, 256, 3, 1, 1, 9),
-                                  (3, 128, 9, 9, 128, 4, 2, 1, 5)])
+SLAB_CASES = [(3, 64, 14, 14, 64, 3, 1, 1, 38), (2, 128, 20, 33, 128, 3, 1, 1, 39), (2, 128, 20, 33, 128, 3, 1, 1, 1),
+              (4, 64, 16, 16, 256, 1, 1, 0, 1), (2, 64, 15, 13, 128, 3, 2, 1, 3), (2, 256, 8, 8, 256, 3, 1, 1, 9),
+              (3, 128, 9, 9, 128, 4, 2, 1, 5)]
+
+
+@pytest.mark.parametrize("case", SLAB_CASES)
 @pytest.mark.parametrize("splits", [0, 1, 7])
 def test_weight_gradient_slabs_are_deterministic_and_equal_the_atomic_form(case, splits, monkeypatch):
     """loans_wgrad_bf16s_ws (round 5): blocks store raw partial tiles into workspace slabs, loans_fold_slabs_f32 adds them to dw in a
@@ -317,7 +329,10 @@ def test_region_boundaries_bf16_storage():
         ops.set_compute_dtype('f32')
 
 
-@pytest.mark.parametrize("case", [(3, 96, 96), (2, 64, 160), (5, 32, 32), (1, 224, 224), (300, 32, 64)])
+STEM_WGRAD_CASES = [(3, 96, 96), (2, 64, 160), (5, 32, 32), (1, 224, 224), (300, 32, 64)]
+
+
+@pytest.mark.parametrize("case", STEM_WGRAD_CASES)
 def test_stem_weight_gradient_direct_bf16(case, monkeypatch):
     """LOANS_TILE_STEM of loans_wgrad_bf16s (csrc/stem.hip: stem7_wgrad_bf16_kernel, round 5): conv1's weight gradient from the bf16
     frame buffer and a bf16 gradient as a direct, persistent kernel, against the implicit-GEMM tile on the same operands (fp32 sums of
@@ -475,9 +490,12 @@ def test_conv_halo_tiles_bf16_storage(case, tile):
     same(gx3, ops.conv_dgrad(gyd, wd, geo, addend=d16(_nhwc(addx)), addend_mask_ref=d16(_nhwc(ref_t)), tile=1), exact_d)
 
 
-@pytest.mark.parametrize("case", [(2, 64, 16, 16, 256), (3, 64, 7, 9, 256), (1, 64, 5, 5, 64), (2, 128, 12, 20, 512), (3, 128, 3, 11, 128),
-                                  (1, 64, 1, 1, 512), (2, 64, 33, 47, 192), (4, 128, 64, 64, 512),
-                                  (2, 256, 8, 8, 1024), (3, 256, 5, 7, 256), (1, 256, 3, 3, 128), (5, 256, 32, 32, 1024)])
+POINTWISE_CASES = [(2, 64, 16, 16, 256), (3, 64, 7, 9, 256), (1, 64, 5, 5, 64), (2, 128, 12, 20, 512), (3, 128, 3, 11, 128),
+                   (1, 64, 1, 1, 512), (2, 64, 33, 47, 192), (4, 128, 64, 64, 512),
+                   (2, 256, 8, 8, 1024), (3, 256, 5, 7, 256), (1, 256, 3, 3, 128), (5, 256, 32, 32, 1024)]
+
+
+@pytest.mark.parametrize("case", POINTWISE_CASES)
 def test_conv_pointwise_tile_bf16_storage(case):
     """LOANS_TILE_PW (csrc/pw_bf16.hip): the short-K 1 x 1 convolutions (ResNet-50's res2 / res3 expansions) with the operands
     fed global -> VGPR and the weights in fragment order -- against the oracle on the bf16-rounded operands, and BIT FOR BIT
@@ -577,8 +595,11 @@ def test_conv_pointwise_tile_more_strips_than_waves():
         np.testing.assert_allclose(s_p.sum(0).cpu().numpy(), s_g.sum(0).cpu().numpy(), rtol=1e-5, atol=1e-2)
 
 
-@pytest.mark.parametrize("case", [(2, 256, 7, 7, 512, 3, 2, 1), (3, 512, 4, 4, 512, 3, 1, 1), (2, 128, 9, 9, 128, 4, 2, 1),
-                                  (2, 512, 8, 8, 64, 3, 1, 1)])
+SPLIT_K_CASES = [(2, 256, 7, 7, 512, 3, 2, 1), (3, 512, 4, 4, 512, 3, 1, 1), (2, 128, 9, 9, 128, 4, 2, 1),
+                 (2, 512, 8, 8, 64, 3, 1, 1)]
+
+
+@pytest.mark.parametrize("case", SPLIT_K_CASES)
 @pytest.mark.parametrize("tile", [3 | (2 << 8), 3 | (4 << 8), 2 | (8 << 8)])
 def test_conv_split_k_bf16_storage(case, tile):
     """split-K on bf16 storage (loans_igemm_bf16s_splitk + loans_igemm_finalize_bf16): raw fp32 partial tiles added into a
@@ -642,7 +663,10 @@ def test_ws64_persistent_blocks_walk_many_tiles(wtile):
     assert torch.equal(ops.conv_dgrad(gy, w, geo, mask_ref=ref, tile=wtile), ops.conv_dgrad(gy, w, geo, mask_ref=ref, tile=1))
 
 
-@pytest.mark.parametrize("case", [(2, 32, 32), (3, 64, 64), (2, 96, 80), (1, 130, 66), (2, 224, 224), (1, 512, 512), (2, 50, 34), (1, 22, 30)])
+STEM_DIRECT_CASES = [(2, 32, 32), (3, 64, 64), (2, 96, 80), (1, 130, 66), (2, 224, 224), (1, 512, 512), (2, 50, 34), (1, 22, 30)]
+
+
+@pytest.mark.parametrize("case", STEM_DIRECT_CASES)
 def test_stem_direct_bf16(case):
     """LOANS_TILE_STEM on the bf16 MFMA (csrc/stem.hip, stem7_bf16_kernel): conv1 with bias and BN statistics as a persistent
     direct convolution, from the fp32 frame buffer (loans_igemm_bf16_f32, operands rounded while staged) and from the bf16 one
@@ -692,7 +716,10 @@ def test_stem_direct_bf16(case):
 
 
 
-@pytest.mark.parametrize("case", [(2, 64, 15, 13, 128, 3, 2, 1), (3, 128, 12, 12, 256, 3, 2, 1), (2, 64, 9, 9, 64, 1, 2, 0), (5, 32, 8, 8, 96, 3, 2, 1)])
+PAIR_CASES = [(2, 64, 15, 13, 128, 3, 2, 1), (3, 128, 12, 12, 256, 3, 2, 1), (2, 64, 9, 9, 64, 1, 2, 0), (5, 32, 8, 8, 96, 3, 2, 1)]
+
+
+@pytest.mark.parametrize("case", PAIR_CASES)
 @pytest.mark.parametrize("tile", [0, 1, 2, 3, 7, 9, 43, 44, 33, 35])
 def test_conv_pair_bf16_storage(case, tile):
     """loans_igemm_pair_bf16s: a unit's first convolution and its conv shortcut as ONE GEMM with the weights stacked along N.
@@ -729,10 +756,13 @@ def test_conv_pair_bf16_storage(case, tile):
     assert torch.equal(y2a, ya) and torch.equal(y2b, yb)
 
 
+BNSUMS_CASES = [(3, 64, 14, 14, 64, 3), (2, 128, 20, 33, 128, 3), (2, 256, 9, 12, 64, 3), (5, 64, 17, 12, 256, 1),
+                (2, 512, 6, 7, 128, 1)]
+
+
 @pytest.mark.parametrize("storage,tiles", [('f32', [0, 1, 2, 3, 4, 6, 17, 18, 19, 20]),
                                            ('bf16', [0, 1, 2, 3, 4, 7, 9, 43, 44, 33, 34, 35, 11, 12, 13, 14, 36, 37, 42])])
-@pytest.mark.parametrize("case", [(3, 64, 14, 14, 64, 3), (2, 128, 20, 33, 128, 3), (2, 256, 9, 12, 64, 3), (5, 64, 17, 12, 256, 1),
-                                  (2, 512, 6, 7, 128, 1)])
+@pytest.mark.parametrize("case", BNSUMS_CASES)
 def test_data_gradient_takes_the_bn_backward_sums(storage, tiles, case):
     """LOANS_F_BNSUMS (round 3): the data gradient that feeds a BatchNormalization followed by its own ReLU
     (sheep/resnet.py:137,157) takes that BN's two backward sums -- sum g m, sum g m (y - mean), m = (y scale + shift > 0) --
@@ -803,8 +833,11 @@ def test_data_gradient_takes_the_bn_backward_sums(storage, tiles, case):
             ops.set_storage_dtype('bf16')
 
 
-@pytest.mark.parametrize("case", [(2, 64, 16, 16, 256), (3, 64, 7, 9, 256), (1, 64, 5, 5, 64), (2, 128, 12, 20, 512), (3, 128, 3, 11, 128),
-                                  (2, 64, 33, 47, 192), (2, 256, 8, 8, 1024), (3, 256, 5, 7, 256), (4, 128, 64, 64, 512)])
+AFFINE_CASES = [(2, 64, 16, 16, 256), (3, 64, 7, 9, 256), (1, 64, 5, 5, 64), (2, 128, 12, 20, 512), (3, 128, 3, 11, 128),
+                (2, 64, 33, 47, 192), (2, 256, 8, 8, 1024), (3, 256, 5, 7, 256), (4, 128, 64, 64, 512)]
+
+
+@pytest.mark.parametrize("case", AFFINE_CASES)
 def test_bn_relu_on_load_pointwise_forward_and_weight_gradient(case):
     """LOANS_F_AFFINE_IN (round 5): a 1 x 1 convolution that reads the INPUT of the BatchNormalization + ReLU in
     front of it and applies them on load -- forward (LOANS_TILE_PW) and weight gradient (every GEMM tile) -- is, BIT FOR BIT, the

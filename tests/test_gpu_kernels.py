@@ -181,7 +181,10 @@ def test_conv_dgrad_class_launch_rejects():
     assert call(stats_flag) == -1
 
 
-@pytest.mark.parametrize("case", [(2, 224, 224), (3, 64, 64), (2, 34, 50), (1, 130, 66), (5, 32, 96), (1, 320, 304)])
+STEM_WGRAD_CASES = [(2, 224, 224), (3, 64, 64), (2, 34, 50), (1, 130, 66), (5, 32, 96), (1, 320, 304)]
+
+
+@pytest.mark.parametrize("case", STEM_WGRAD_CASES)
 def test_stem_wgrad_direct(case):
     """LOANS_TILE_STEM of loans_wgrad_f32 (csrc/stem.hip, stem7_wgrad_kernel): conv1's weight gradient as a persistent direct
     kernel, against the oracle and the implicit-GEMM kernel; even and odd output widths, more units than blocks and fewer,
@@ -316,8 +319,11 @@ def test_conv_fine_tail_tile(case):
     assert ops._igemm_launches(M_, Cout, ops.TILE_FINETAIL, torch.device('cuda', 0), nch) == 2
 
 
-@pytest.mark.parametrize("case", [(2, 64, 14, 14, 64, 3, 1, 1), (2, 64, 15, 13, 128, 3, 2, 1), (3, 256, 7, 7, 64, 1, 1, 0),
-                                  (1, 128, 9, 9, 128, 4, 2, 1)])
+SPLIT_K_CASES = [(2, 64, 14, 14, 64, 3, 1, 1), (2, 64, 15, 13, 128, 3, 2, 1), (3, 256, 7, 7, 64, 1, 1, 0),
+                 (1, 128, 9, 9, 128, 4, 2, 1)]
+
+
+@pytest.mark.parametrize("case", SPLIT_K_CASES)
 @pytest.mark.parametrize("splits", [2, 4, 16])
 def test_conv_split_k(case, splits):
     """LOANS_TILE_SPLITK: blocks contract slices of K and add raw partial tiles; loans_igemm_finalize_f32 applies bias /
@@ -358,7 +364,10 @@ def test_conv_split_k(case, splits):
     assert rel_err(ak.cpu().numpy(), a1.cpu().numpy()) < 2e-6
 
 
-@pytest.mark.parametrize("case", [(3, 64, 14, 14, 128, 128, 3, 2, 1), (2, 256, 9, 9, 64, 256, 1, 2, 0), (2, 64, 12, 12, 64, 200, 3, 1, 1)])
+PAIR_CASES = [(3, 64, 14, 14, 128, 128, 3, 2, 1), (2, 256, 9, 9, 64, 256, 1, 2, 0), (2, 64, 12, 12, 64, 200, 3, 1, 1)]
+
+
+@pytest.mark.parametrize("case", PAIR_CASES)
 @pytest.mark.parametrize("tile", [0, 1, 2, 3, 4, 17, 18, 19])
 def test_conv_fprop_pair(case, tile):
     """loans_igemm_pair_f32: two convolutions of one input (BasicA's conv1 + conv shortcut; a bottleneck's conv1 + conv4,
@@ -399,8 +408,11 @@ def test_prep_images_dense_exact():
         assert not border.any()
 
 
-@pytest.mark.parametrize("case", [(2, 32, 32, 64, 7, 2, 3), (3, 17, 23, 64, 7, 2, 3), (2, 12, 12, 128, 3, 1, 1),
-                                  (1, 40, 36, 64, 7, 2, 3)])
+DENSE_ROWS_CASES = [(2, 32, 32, 64, 7, 2, 3), (3, 17, 23, 64, 7, 2, 3), (2, 12, 12, 128, 3, 1, 1),
+                    (1, 40, 36, 64, 7, 2, 3)]
+
+
+@pytest.mark.parametrize("case", DENSE_ROWS_CASES)
 @pytest.mark.parametrize("tile", [0, 1, 2, 3, 4, 5, 17, 18, 19, 20])
 def test_conv_dense_rows(case, tile):
     """LOANS_F_DENSE: the RGB stem on packed 3-channel rows of a zero-padded frame (K = kh x 24 instead of kh*kw x 4)"""
@@ -436,7 +448,10 @@ def test_conv_dense_rows(case, tile):
         assert not got[:, :, k:].any()          # window-padding columns carry no gradient
 
 
-@pytest.mark.parametrize("case", [(2, 224, 224), (3, 64, 64), (2, 32, 32), (1, 128, 128), (2, 64, 96), (1, 256, 64)])
+STEM_DIRECT_CASES = [(2, 224, 224), (3, 64, 64), (2, 32, 32), (1, 128, 128), (2, 64, 96), (1, 256, 64)]
+
+
+@pytest.mark.parametrize("case", STEM_DIRECT_CASES)
 def test_conv_stem_direct(case):
     """LOANS_TILE_STEM (csrc/stem.hip): conv1 7x7 / 2, 3 -> 64 with bias and BN statistics as a direct convolution from an
     LDS-staged image, against the oracle convolution and the implicit-GEMM dense-row kernel; frame sizes with 1 ... 7
@@ -823,8 +838,11 @@ def _bf16_round(a):
     return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(torch.bfloat16).to(torch.float32).numpy()
 
 
-@pytest.mark.parametrize("case", [(2, 64, 15, 13, 128, 3, 2, 1), (3, 128, 9, 9, 128, 4, 2, 1), (2, 3, 32, 32, 64, 7, 2, 3),
-                                  (2, 256, 7, 7, 512, 3, 1, 1), (2, 64, 9, 10, 128, 1, 2, 0)])
+BF16_COMPUTE_CASES = [(2, 64, 15, 13, 128, 3, 2, 1), (3, 128, 9, 9, 128, 4, 2, 1), (2, 3, 32, 32, 64, 7, 2, 3),
+                      (2, 256, 7, 7, 512, 3, 1, 1), (2, 64, 9, 10, 128, 1, 2, 0)]
+
+
+@pytest.mark.parametrize("case", BF16_COMPUTE_CASES)
 @pytest.mark.parametrize("tile", [0, 1, 2, 3, 4])
 def test_conv_bf16_compute_fprop_dgrad(case, tile):
     """bf16 compute arm: operands rounded to bf16 (RNE), products exact in fp32, fp32 accumulation -- so the
@@ -860,7 +878,10 @@ def test_conv_bf16_compute_fprop_dgrad(case, tile):
         ops.set_compute_dtype('f32')
 
 
-@pytest.mark.parametrize("shape", [(2, 75, 75), (3, 16, 16), (2, 19, 23), (1, 33, 17), (2, 28, 24)])
+CROP_DGRAD_SHAPES = [(2, 75, 75), (3, 16, 16), (2, 19, 23), (1, 33, 17), (2, 28, 24)]
+
+
+@pytest.mark.parametrize("shape", CROP_DGRAD_SHAPES)
 @pytest.mark.parametrize("g16", [False, True])
 def test_crop_dgrad_one_launch(shape, g16):
     """loans_crop_dgrad (csrc/cropgrad.hip): the gradient w.r.t. the 4-channel crops through r0.c0 (3x3 / 1) AND r0.cs
