@@ -10,72 +10,53 @@
 // 0 * inf there.  c = +inf means "measure only".
 // Three launches: grad_sumsq_kernel (one pass over g, one fp64 partial per unit of 4096 floats), grad_clip_fold_kernel (one wave:
 // partials -> N, k), grad_scale_dev_kernel (g *= k, or nothing).  No atomic, nothing synchronised with the host: two runs on the same
-// inputs give the same bits.  This file shares no code with lars.hip; what it needs of it is restated here.
-#include "common.h"
+// inputs give the same bits.
+#include "arena.h"
 
 namespace {
 
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ f32x4 ldnt4(const float* p) { return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p)); }
-__device__ __forceinline__ void stnt4(float* p, f32x4 v) { __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p)); }
-
-constexpr int CLIP_UNIT = LOANS_LARS_UNIT;
 constexpr int64_t CLIP_MAX_N = LOANS_GRAD_CLIP_MAX_N;
 
 // ---- pass 1: per-unit partial sums of squares -------------------------------------------------------------------------------------
-// lars_partials_kernel without the segment table: unit u is floats [4096 u, min(n, 4096 (u + 1))), one block per unit and trip, the
-// grid capped by grid_for -- a block takes units u, u + gridDim.x, .. -- and the partial of a unit lands in ws[u] whichever block
-// summed it, so the result does not depend on the grid.  A full unit is sixteen floats per thread, its four float4 loads issued
-// before the first use; the last, short unit takes float4 while they fit and single floats for the n & 3 behind them.  g is read
-// non-temporally: the clipped copy, if any, is written by the third launch from a second read.  Every element is converted to
-// double and squared -- exact, 24 + 24 bits in 53 --, only the additions round; 1e-25 does not vanish and 1e25 does not overflow.
-// Order of the additions, fixed: a thread's elements (float4 k ascending, lane e ascending), the xor butterfly 32, 16 .. 1 inside the
-// wave, waves 0..3 through LDS.
+// arena_walk's three arms and visiting order (arena.h) over g alone, without a segment table: unit u is floats [4096 u,
+// min(n, 4096 (u + 1))), the partial of a unit lands in ws[u] whichever block summed it, so the result does not depend on the grid.
+// tests/arena_kernels/test_gpu_kernels.py holds the two walks to one order.  g is read non-temporally: the clipped copy, if any,
+// is written by the third launch from a second read.  Every element is converted to double and squared -- exact, 24 + 24 bits in
+// 53 --, only the additions round; 1e-25 does not vanish and 1e25 does not overflow.
 __global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, int64_t n, int64_t units,
                                                          double* __restrict__ ws) {
     __shared__ double sh[4];
     for (int64_t u = blockIdx.x; u < units; u += gridDim.x) {
-        const int64_t off = u * CLIP_UNIT;
+        const int64_t off = u * ARENA_UNIT;
         const int64_t left = n - off;
-        double s = 0.0;
-        if (left >= CLIP_UNIT) {
+        double s[1] = {0.0};
+        auto sum4 = [&](f32x4 gg) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const double a = (double)gg[e];
+                s[0] += a * a;
+            }
+        };
+        if (left >= ARENA_UNIT) {
             f32x4 gg[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) gg[k] = ldnt4(g + off + (k * 256 + threadIdx.x) * 4);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const double a = (double)gg[k][e];
-                    s += a * a;
-                }
-            }
+            for (int k = 0; k < 4; ++k) sum4(gg[k]);
         } else if (left > 0) {
             const int m = (int)left, m4 = m & ~3;
-            for (int k = threadIdx.x * 4; k < m4; k += 1024) {
-                const f32x4 gg = ldnt4(g + off + k);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const double a = (double)gg[e];
-                    s += a * a;
-                }
-            }
+            for (int k = threadIdx.x * 4; k < m4; k += 1024) sum4(ldnt4(g + off + k));
             if ((int)threadIdx.x < (m & 3)) {
                 const double a = (double)g[off + m4 + threadIdx.x];
-                s += a * a;
+                s[0] += a * a;
             }
         }
-        s = wave_sum_d(s);
-        __syncthreads();            // the previous trip's sh has been read
-        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) ws[u] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+        arena_block_sums(s, sh, ws + u);
     }
 }
 
 // ---- pass 2: the partials -> N and k ----------------------------------------------------------------------------------------------
-// One wave.  A single chain over the partials, as lars_fold_kernel walks a segment's, puts one dependent fp64 addition per unit on
+// One wave.  A single chain over the partials, as arena_fold_segment walks a segment's, puts one dependent fp64 addition per unit on
 // the critical path (576 units: 14 to 17 us there) and ResNet-50's arena is ~6.3 k units, so this is a tree: lane l sums partials
 // l, l + 64, l + 128, .. in ascending order -- ceil(units / 64) additions deep -- and the 64 lane sums meet in the xor butterfly.
 // The loads are not on that chain: a lane fetches FOLD_BATCH of its partials at a time, all of them in flight together, and the next
@@ -147,7 +128,7 @@ int clip_hint() {
     return CLIP_HINT;
 }
 
-inline int64_t clip_units(int64_t n) { return (n + CLIP_UNIT - 1) / CLIP_UNIT; }
+inline int64_t clip_units(int64_t n) { return (n + ARENA_UNIT - 1) / ARENA_UNIT; }
 
 }  // namespace
 

@@ -19,7 +19,7 @@
 //     m'  = fmaf(omb1, g^ - m, m)
 //     v'  = fmaf(omb2, fmaf(g^, g^, -v), v)
 //     u   = fmaf(wd_s, p, a)
-//     p'  = fmaf(-rate_s, u, p)          with rate_s = fl(lr32 * r_s), ONE fp32 product as in lars_update_kernel
+//     p'  = fmaf(-rate_s, u, p)          with rate_s = fl(lr32 * r_s), ONE fp32 product as in LARS's update (sgd.hip)
 // sqrtf and / are what the Makefile's flags make of them; no fast-math intrinsic.  (v = g^2 overflows fp32 beyond |g gs| ~ 1e19:
 // that is Adam's own limit, not this file's.)
 //
@@ -27,19 +27,10 @@
 // per parameter); lamb_fold_kernel folds them per segment into r; lamb_update_kernel reads p, m', v', RECOMPUTES u through the
 // same lamb_u and writes p' (16 bytes per parameter).  Pass 1 leaves p alone, so the norm and the update see the same u bit for
 // bit, and no fourth arena-sized buffer is needed.  Nothing is synchronised with the host, no floating-point atomic is used:
-// two runs on the same inputs give the same bits.  lars.hip is not edited and shares no code with this file; what is needed of it
-// is restated here.
-#include "common.h"
+// two runs on the same inputs give the same bits.  The fold and the segment cursor are arena.h's; pass 1 says why it is not.
+#include "arena.h"
 
 namespace {
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ f32x4 ldnt4(const float* p) { return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p)); }
-__device__ __forceinline__ void stnt4(float* p, f32x4 v) { __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p)); }
-
-constexpr int LAMB_UNIT = LOANS_LARS_UNIT;
-constexpr int LAMB_MAX_SEGMENTS = LOANS_LARS_MAX_SEGMENTS;
 
 struct LambHyper { float omb1, omb2, c1, c2, eps, wd, gscale; };
 
@@ -59,23 +50,19 @@ __device__ __forceinline__ float lamb_u(float p, float m, float v, const LambHyp
 }
 
 // ---- pass 1: moments, and per-unit partial sums of p^2 and u^2 ---------------------------------------------------------------------
-// Work is cut per segment into units of LAMB_UNIT floats exactly as lars_partials_kernel cuts it: unit u belongs to the segment
-// with the largest first_unit <= u (uniform per block), so a unit never straddles a boundary and wd_s is one value per block and
-// trip.  A full unit is four float4 of p, g, m and v per thread, all sixteen loads issued before the first use; a segment's last,
-// short unit takes float4 while they fit and single floats for the n & 3 behind them (only the last segment can have those).
-// p is cacheable and NOT written here (pass 3, the bf16 cast and the re-packs read it next); g, m, v are read once and m', v'
-// written once in this pass, and more than the Infinity Cache holds passes through before pass 3 reads them back: non-temporal,
-// adam_kernel's choice.  Squares and sums are fp64 in lars_partials_kernel's fixed order: a thread's elements (float4 k
-// ascending, lane e ascending), the xor butterfly 32, 16 .. 1, waves 0..3 through LDS; thread 0 stores the unit's two sums with
-// one 16-byte vector store.
-typedef double LambPartial __attribute__((ext_vector_type(2)));     // [0] the sum of p^2, [1] of u^2
-
+// arena_walk's units, three arms and visiting order (arena.h) over p, g, m and v, written out: on arena_walk itself this kernel
+// compiled to 86 VGPRs for 108 and ran 101.0 us for 96.8 on ResNet-50's arena (profiles/arena_kernels_ab.txt), so it keeps its
+// own statement; tests/arena_kernels/test_gpu_kernels.py holds its sums of p^2 to the bits of LARS's.  A full unit is sixteen
+// float4 loads issued before the first use; wd_s is one value per block and trip.  p is cacheable and NOT written here (pass 3,
+// the bf16 cast and the re-packs read it next); g, m, v are read once and m', v' written once in this pass, and more than the
+// Infinity Cache holds passes through before pass 3 reads them back: non-temporal, adam_kernel's choice.  Squares and sums are
+// fp64; thread 0 stores the unit's two sums, [p^2, u^2], with one 16-byte vector store.
 __global__ __launch_bounds__(256) void lamb_moments_kernel(const float* __restrict__ p, const float* __restrict__ g,
                                                            float* __restrict__ m, float* __restrict__ v, LambHyper h,
                                                            const int64_t* __restrict__ seg_end,
                                                            const uint8_t* __restrict__ seg_flags,
                                                            const int64_t* __restrict__ seg_first_unit, int nseg, int64_t units,
-                                                           LambPartial* __restrict__ ws) {
+                                                           f64x2* __restrict__ ws) {
     __shared__ double sh[8];
     const float wd = h.wd;
     for (int64_t u = blockIdx.x; u < units; u += gridDim.x) {
@@ -85,12 +72,12 @@ __global__ __launch_bounds__(256) void lamb_moments_kernel(const float* __restri
             if (seg_first_unit[mid] <= u) lo = mid; else hi = mid - 1;
         }
         const int64_t start = lo ? seg_end[lo - 1] : 0;
-        const int64_t off = start + (u - seg_first_unit[lo]) * LAMB_UNIT;
+        const int64_t off = start + (u - seg_first_unit[lo]) * ARENA_UNIT;
         int64_t left = seg_end[lo] - off;
         if (off < start) left = 0;          // (a first_unit table that does not belong to these ends: touch nothing)
         h.wd = (seg_flags[lo] & 1) ? 0.f : wd;
         double sp = 0.0, su = 0.0;
-        if (left >= LAMB_UNIT) {
+        if (left >= ARENA_UNIT) {
             f32x4 pp[4], gg[4], mm[4], vv[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -143,7 +130,7 @@ __global__ __launch_bounds__(256) void lamb_moments_kernel(const float* __restri
         if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = sp; sh[4 + (threadIdx.x >> 6)] = su; }
         __syncthreads();
         if (threadIdx.x == 0) {
-            LambPartial out;
+            f64x2 out;
             out[0] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
             out[1] = ((sh[4] + sh[5]) + sh[6]) + sh[7];
             ws[u] = out;
@@ -151,36 +138,16 @@ __global__ __launch_bounds__(256) void lamb_moments_kernel(const float* __restri
     }
 }
 
-// ---- pass 2: a segment's partials in ascending unit order, then the ratio, formed in double and rounded to fp32 once ----------------
-// lars_fold_kernel's structure: one wave per segment, 64 partials fetched at a time (one 16-byte load per lane), the next 64
-// before the current ones are added, passed through LDS to an unrolled loop -- the order of the additions is the units', the loads
-// are not on that chain.
-__global__ __launch_bounds__(64) void lamb_fold_kernel(const LambPartial* __restrict__ ws, const int64_t* __restrict__ seg_end,
+// ---- pass 2: a segment's partials, then the ratio, formed in double and rounded to fp32 once ----------------------------------------
+__global__ __launch_bounds__(64) void lamb_fold_kernel(const f64x2* __restrict__ ws, const int64_t* __restrict__ seg_end,
                                                        const int64_t* __restrict__ seg_first_unit,
-                                                       const uint8_t* __restrict__ seg_flags, int nseg, int64_t units,
+                                                       const uint8_t* __restrict__ seg_flags, int64_t units,
                                                        float* __restrict__ ratios, double* __restrict__ norms) {
-    __shared__ LambPartial sh[64];
-    const int s = blockIdx.x, lane = threadIdx.x;
-    const int64_t start = s ? seg_end[s - 1] : 0;
-    const int64_t first = seg_first_unit[s];
-    int64_t count = (seg_end[s] - start + LAMB_UNIT - 1) / LAMB_UNIT;
-    if (first < 0 || first + count > units) count = 0;          // (a first_unit table that does not belong to these ends)
-    const LambPartial zero = {0.0, 0.0};
-    double sp = 0.0, su = 0.0;
-    LambPartial next = lane < count ? ws[first + lane] : zero;
-    for (int64_t base = 0; base < count; base += 64) {
-        sh[lane] = next;
-        next = base + 64 + lane < count ? ws[first + base + 64 + lane] : zero;
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 64; ++k) {          // every lane carries the same chain (broadcast reads, no divergence); slots behind the
-            sp += sh[k][0];                     // segment's last unit hold +0.0, which changes no bit of a non-negative sum
-            su += sh[k][1];
-        }
-        __syncthreads();
-    }
-    if (lane != 0) return;
-    const double W = sqrt(sp), U = sqrt(su);
+    __shared__ f64x2 sh[64];
+    const f64x2 sum = arena_fold_segment(ws, seg_end, seg_first_unit, units, sh);
+    if (threadIdx.x != 0) return;
+    const int s = blockIdx.x;
+    const double W = sqrt(sum[0]), U = sqrt(sum[1]);
     double r = 1.0;
     if (!(seg_flags[s] & 2) && W > 0.0 && U > 0.0) r = W / U;
     ratios[s] = (float)r;
@@ -188,34 +155,26 @@ __global__ __launch_bounds__(64) void lamb_fold_kernel(const LambPartial* __rest
 }
 
 // ---- pass 3: p' = p - (lr r_s) u ------------------------------------------------------------------------------------------------------
-// lars_update_kernel's structure: the first trip's loads go out before the table is fetched; ends, flags and ratios sit in LDS
-// (8 + 1 + 4 KB); a thread bisects once and carries a forward-only cursor.  p cacheable, the moments non-temporal (read once,
-// nothing of them is left in the Infinity Cache by now).  u is lamb_u on the stored m', v' and the p pass 1 saw.
+// A grid-stride loop behind arena.h's segment cursor, ends, flags and ratios in LDS (8 + 1 + 4 KB).  p cacheable, the moments
+// non-temporal (read once, nothing of them is left in the Infinity Cache by now).  u is lamb_u on the stored m', v' and the p pass 1
+// saw.
 __global__ __launch_bounds__(256) void lamb_update_kernel(float* p, const float* __restrict__ m, const float* __restrict__ v,
                                                           int64_t n, LambHyper h, float lr, const int64_t* __restrict__ seg_end,
                                                           const uint8_t* __restrict__ seg_flags, const float* __restrict__ seg_ratio,
                                                           int nseg) {
-    __shared__ int64_t ends[LAMB_MAX_SEGMENTS];
-    __shared__ float ratio[LAMB_MAX_SEGMENTS];
-    __shared__ uint8_t flags[LAMB_MAX_SEGMENTS];
+    __shared__ int64_t ends[SEG_MAX_SEGMENTS];
+    __shared__ float ratio[SEG_MAX_SEGMENTS];
+    __shared__ uint8_t flags[SEG_MAX_SEGMENTS];
     const int64_t n4 = n >> 2, stride = (int64_t)gridDim.x * blockDim.x;
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     f32x4 pp = {0.f, 0.f, 0.f, 0.f}, mm = pp, vv = pp;
     if (i < n4) { pp = ld4(p + i * 4); mm = ldnt4(m + i * 4); vv = ldnt4(v + i * 4); }
-    for (int s = threadIdx.x; s < nseg; s += 256) { ends[s] = seg_end[s]; flags[s] = seg_flags[s]; ratio[s] = seg_ratio[s]; }
+    seg_load(ends, flags, ratio, seg_end, seg_flags, seg_ratio, nseg);
     __syncthreads();
     const float wd = h.wd;
-    int seg = 0;
-    if (i < n4) {           // the first segment whose end lies behind float i * 4
-        int lo = 0, hi = nseg - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (ends[mid] > i * 4) hi = mid; else lo = mid + 1;
-        }
-        seg = lo;
-    }
+    int seg = i < n4 ? seg_find(ends, nseg, i * 4) : 0;
     while (i < n4) {
-        while (seg < nseg - 1 && ends[seg] <= i * 4) ++seg;         // (the last end is n > i * 4)
+        seg = seg_advance(ends, nseg, seg, i * 4);
         h.wd = (flags[seg] & 1) ? 0.f : wd;
         const float rate = lr * ratio[seg];
 #pragma unroll
@@ -230,21 +189,6 @@ __global__ __launch_bounds__(256) void lamb_update_kernel(float* p, const float*
         const float rate = lr * ratio[nseg - 1];
         p[t] = fmaf(-rate, lamb_u(p[t], m[t], v[t], h), p[t]);
     }
-}
-
-// lars.hip's lars_units, restated: ascending, no empty segment, float4-aligned boundaries, the last one at n; the number of
-// units, or -1
-int64_t lamb_units(const int64_t* seg_end_host, int32_t nseg, int64_t n) {
-    if (!seg_end_host || nseg <= 0 || nseg > LAMB_MAX_SEGMENTS) return -1;
-    int64_t prev = 0, units = 0;
-    for (int s = 0; s < nseg; ++s) {
-        const int64_t e = seg_end_host[s];
-        if (e <= prev || (s < nseg - 1 && (e & 3))) return -1;
-        units += (e - prev + LAMB_UNIT - 1) / LAMB_UNIT;
-        prev = e;
-    }
-    if (prev != n) return -1;
-    return units;
 }
 
 // beta in [0, 1), c >= 1, eps >= 0; a NaN fails every comparison
@@ -265,13 +209,13 @@ extern "C" int loans_lamb_moments_f32(const float* p, const float* g, float* m, 
         (((uintptr_t)seg_end_dev | (uintptr_t)seg_first_unit_dev) & 7))
         return LOANS_EINVAL;
     if (!lamb_scalars_ok(beta1, beta2, c1, c2, eps)) return LOANS_EINVAL;
-    const int64_t units = lamb_units(seg_end_host, nseg, n);
-    if (units < 0 || workspace_bytes < units * (int64_t)sizeof(LambPartial)) return LOANS_EINVAL;
+    const int64_t units = seg_table_units(seg_end_host, nseg, n, ARENA_UNIT);
+    if (units < 0 || workspace_bytes < units * (int64_t)sizeof(f64x2)) return LOANS_EINVAL;
     LambHyper h;
     h.omb1 = (float)(1.0 - beta1); h.omb2 = (float)(1.0 - beta2); h.c1 = (float)c1; h.c2 = (float)c2; h.eps = (float)eps;
     h.wd = (float)weight_decay_rate; h.gscale = (float)grad_scale;
     hipLaunchKernelGGL(lamb_moments_kernel, dim3(grid_for(units, 1)), dim3(256), 0, as_stream(stream), p, g, m, v, h, seg_end_dev,
-                       seg_flags_dev, seg_first_unit_dev, nseg, units, static_cast<LambPartial*>(workspace));
+                       seg_flags_dev, seg_first_unit_dev, nseg, units, static_cast<f64x2*>(workspace));
     LOANS_LAUNCH_CHECK();
     return LOANS_OK;
 }
@@ -285,10 +229,10 @@ extern "C" int loans_lamb_ratios_f32(int64_t n, const int64_t* seg_end_dev, cons
     if (((uintptr_t)workspace & 15) || (((uintptr_t)seg_end_dev | (uintptr_t)seg_first_unit_dev | (uintptr_t)norms_dev) & 7) ||
         ((uintptr_t)ratios_dev & 3))
         return LOANS_EINVAL;
-    const int64_t units = lamb_units(seg_end_host, nseg, n);
-    if (units < 0 || workspace_bytes < units * (int64_t)sizeof(LambPartial)) return LOANS_EINVAL;
-    hipLaunchKernelGGL(lamb_fold_kernel, dim3(nseg), dim3(64), 0, as_stream(stream), static_cast<const LambPartial*>(workspace),
-                       seg_end_dev, seg_first_unit_dev, seg_flags_dev, nseg, units, ratios_dev, norms_dev);
+    const int64_t units = seg_table_units(seg_end_host, nseg, n, ARENA_UNIT);
+    if (units < 0 || workspace_bytes < units * (int64_t)sizeof(f64x2)) return LOANS_EINVAL;
+    hipLaunchKernelGGL(lamb_fold_kernel, dim3(nseg), dim3(64), 0, as_stream(stream), static_cast<const f64x2*>(workspace),
+                       seg_end_dev, seg_first_unit_dev, seg_flags_dev, units, ratios_dev, norms_dev);
     LOANS_LAUNCH_CHECK();
     return LOANS_OK;
 }
@@ -301,7 +245,7 @@ extern "C" int loans_lamb_update_f32(float* p, const float* m, const float* v, i
     if ((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) || ((uintptr_t)seg_end_dev & 7) || ((uintptr_t)ratios_dev & 3))
         return LOANS_EINVAL;
     if (!lamb_scalars_ok(0.0, 0.0, c1, c2, eps)) return LOANS_EINVAL;
-    if (lamb_units(seg_end_host, nseg, n) < 0) return LOANS_EINVAL;
+    if (seg_table_units(seg_end_host, nseg, n, ARENA_UNIT) < 0) return LOANS_EINVAL;
     LambHyper h;
     h.omb1 = 0.f; h.omb2 = 0.f; h.c1 = (float)c1; h.c2 = (float)c2; h.eps = (float)eps; h.wd = (float)weight_decay_rate;
     h.gscale = 0.f;

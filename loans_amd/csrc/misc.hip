@@ -1,15 +1,10 @@
 // Small kernels around the conv stacks: preprocessing, GAP, Linear heads, rotation-dropout
-// multiply, spatial transformer (grid + bilinear sampler), losses, the fused Adam-AMSGrad and momentum SGD (plain and with
-// per-segment weight decay), the job-table streaming kernel of the weight average.
+// multiply, spatial transformer (grid + bilinear sampler), losses, the fused Adam-AMSGrad, the job-table streaming kernel of the
+// weight average.
 // None of them is GEMM-shaped; they are coalesced streaming / wave-shuffle reduction kernels.
-#include "common.h"
+#include "arena.h"      // (ld4, st4, ldnt4, stnt4)
 
 namespace {
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ f32x4 ldnt4(const float* p) { return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p)); }
-__device__ __forceinline__ void stnt4(float* p, f32x4 v) { __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p)); }
 
 // block-wide sum for 256-thread blocks; result valid in every thread
 __device__ __forceinline__ float block_sum(float v, float* sh /* >= 4 floats */) {
@@ -473,90 +468,6 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, flo
     }
 }
 
-// ---- momentum SGD (Chainer 4.1 MomentumSGDRule, the WeightDecay hook applied to the gradient first) --------------------------
-struct SgdHyper { float lr, momentum, wd, gscale; };
-
-__device__ __forceinline__ void sgd1(float& p, float g, float& v, const SgdHyper& h) {
-    g = g * h.gscale + h.wd * p;
-    v = h.momentum * v - h.lr * g;
-    p += v;
-}
-
-// the structure of adam_kernel: g read once, v read and written once per step -- non-temporal; p stays cacheable for the same
-// reason as there (the bf16 cast and the re-packs of the next step read it).  20 bytes per parameter against plain Adam's 28.
-__global__ __launch_bounds__(256) void momentum_sgd_kernel(float* p, const float* g, float* v, int64_t n, SgdHyper h,
-                                                           const float* lr_dev) {
-    if (lr_dev) h.lr = *lr_dev;         // read from device memory: the launch can live in a hipGraph
-    const int64_t n4 = n >> 2;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        f32x4 pp = ld4(p + i * 4), gg = ldnt4(g + i * 4), vv = ldnt4(v + i * 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float a = pp[e], b = vv[e];
-            sgd1(a, gg[e], b, h);
-            pp[e] = a; vv[e] = b;
-        }
-        st4(p + i * 4, pp); stnt4(v + i * 4, vv);
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-        const int64_t i = n4 * 4 + threadIdx.x;
-        sgd1(p[i], g[i], v[i], h);
-    }
-}
-
-// ---- momentum SGD with per-segment weight decay ---------------------------------------------------------------------------------
-// momentum_sgd_kernel with h.wd replaced by 0 inside the segments whose flag has bit 0 set (BN gamma / beta, biases).  The table --
-// exclusive ends, ascending, every end but the last a multiple of 4, so that no float4 straddles a boundary -- is copied into LDS once
-// per block; a thread bisects it once for its first float4 and from there carries a cursor along the grid-stride loop: the indices
-// only grow, so the cursor only moves forward -- at most SGD_MAX_SEGMENTS LDS reads per thread over the whole launch, none of them
-// on the path of the loads: a trip's loads are issued before the lookup of the trip in front of it is used.
-constexpr int SGD_MAX_SEGMENTS = 1024;      // 8 KB of ends + 1 KB of flags in LDS
-
-__global__ __launch_bounds__(256) void momentum_sgd_seg_kernel(float* p, const float* g, float* v, int64_t n, SgdHyper h,
-                                                               const float* lr_dev, const int64_t* __restrict__ seg_end,
-                                                               const uint8_t* __restrict__ seg_flags, int nseg) {
-    __shared__ int64_t ends[SGD_MAX_SEGMENTS];
-    __shared__ uint8_t flags[SGD_MAX_SEGMENTS];
-    const int64_t n4 = n >> 2, stride = (int64_t)gridDim.x * blockDim.x;
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    // the first trip's loads go out BEFORE the table is fetched: the grid is one wave of blocks, so a prologue of a global load, a
-    // barrier and a bisection in front of every block's first load is time the plain kernel does not spend (1.3 us of 79 at the
-    // ResNet-50 arena, profiles/imagenet_ema.txt)
-    f32x4 pp = {0.f, 0.f, 0.f, 0.f}, gg = pp, vv = pp;
-    if (i < n4) { pp = ld4(p + i * 4); gg = ldnt4(g + i * 4); vv = ldnt4(v + i * 4); }
-    for (int s = threadIdx.x; s < nseg; s += 256) { ends[s] = seg_end[s]; flags[s] = seg_flags[s]; }
-    if (lr_dev) h.lr = *lr_dev;
-    __syncthreads();
-    const float wd = h.wd;
-    int seg = 0;
-    if (i < n4) {           // the first segment whose end lies behind float i * 4
-        int lo = 0, hi = nseg - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (ends[mid] > i * 4) hi = mid; else lo = mid + 1;
-        }
-        seg = lo;
-    }
-    while (i < n4) {
-        while (seg < nseg - 1 && ends[seg] <= i * 4) ++seg;         // (the last end is n > i * 4)
-        h.wd = (flags[seg] & 1) ? 0.f : wd;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float a = pp[e], b = vv[e];
-            sgd1(a, gg[e], b, h);
-            pp[e] = a; vv[e] = b;
-        }
-        st4(p + i * 4, pp); stnt4(v + i * 4, vv);
-        i += stride;
-        if (i < n4) { pp = ld4(p + i * 4); gg = ldnt4(g + i * 4); vv = ldnt4(v + i * 4); }
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {         // the last segment's ragged end
-        const int64_t t = n4 * 4 + threadIdx.x;
-        h.wd = (flags[nseg - 1] & 1) ? 0.f : wd;
-        sgd1(p[t], g[t], v[t], h);
-    }
-}
-
 // ---- weight average: a table of (dst, src, n) jobs in one launch ------------------------------------------------------------------
 // Work is cut into units of AVG_UNIT floats; unit u belongs to the job with the largest first_unit <= u (bisection over the table: u
 // is the same for the whole block, so the table is read with scalar loads).  A full unit is four float4 per thread, all loads issued
@@ -876,39 +787,6 @@ extern "C" int loans_adam_f32(float* p, const float* g, float* m, float* v, int6
     LOANS_LAUNCH_CHECK();
     return LOANS_OK;
 }
-
-extern "C" int loans_momentum_sgd_f32(float* p, const float* g, float* v, int64_t n, double lr, const float* lr_dev,
-                                      double momentum, double weight_decay_rate, double grad_scale, void* stream) {
-    if (!p || !g || !v || n <= 0) return LOANS_EINVAL;
-    SgdHyper h;
-    h.lr = (float)lr; h.momentum = (float)momentum; h.wd = (float)weight_decay_rate; h.gscale = (float)grad_scale;
-    hipLaunchKernelGGL(momentum_sgd_kernel, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, as_stream(stream), p, g, v, n, h, lr_dev);
-    LOANS_LAUNCH_CHECK();
-    return LOANS_OK;
-}
-
-extern "C" int loans_momentum_sgd_seg_f32(float* p, const float* g, float* v, int64_t n, double lr, const float* lr_dev, double momentum,
-                                          double weight_decay_rate, double grad_scale, const int64_t* seg_end_dev,
-                                          const uint8_t* seg_flags_dev, const int64_t* seg_end_host, int32_t nseg, void* stream) {
-    if (!p || !g || !v || n <= 0 || !seg_end_dev || !seg_flags_dev || !seg_end_host) return LOANS_EINVAL;
-    if (nseg <= 0 || nseg > SGD_MAX_SEGMENTS) return LOANS_EINVAL;
-    if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)v) & 15) || ((uintptr_t)seg_end_dev & 7)) return LOANS_EINVAL;
-    int64_t prev = 0;
-    for (int s = 0; s < nseg; ++s) {        // ascending, no empty segment, float4-aligned boundaries, the last one at n
-        const int64_t e = seg_end_host[s];
-        if (e <= prev || (s < nseg - 1 && (e & 3))) return LOANS_EINVAL;
-        prev = e;
-    }
-    if (prev != n) return LOANS_EINVAL;
-    SgdHyper h;
-    h.lr = (float)lr; h.momentum = (float)momentum; h.wd = (float)weight_decay_rate; h.gscale = (float)grad_scale;
-    hipLaunchKernelGGL(momentum_sgd_seg_kernel, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, as_stream(stream), p, g, v, n, h, lr_dev,
-                       seg_end_dev, seg_flags_dev, nseg);
-    LOANS_LAUNCH_CHECK();
-    return LOANS_OK;
-}
-
-extern "C" int loans_momentum_sgd_max_segments(void) { return SGD_MAX_SEGMENTS; }
 
 extern "C" int loans_average_jobs_f32(const loans_avg_job* jobs_dev, const loans_avg_job* jobs_host, int32_t njobs, int64_t units,
                                       int32_t mode, float omd, void* stream) {

@@ -21,7 +21,7 @@
 // is safe IN PLACE (out == x); the job is uniform over a block and loaded once per image, the order code selects the path without
 // lane divergence; the erase box is handled per 16-byte unit (all inside: nothing is read; none inside; mixed).  The partials of an
 // image are folded in ascending block order -- one chain of fp64 additions -- by photo_fold_kernel, a small launch of one wave per
-// image behind the grey pass (as lars.hip folds), which leaves one fp32 mean per image behind the partials; an apply block reads
+// image behind the grey pass (as arena.h folds), which leaves one fp32 mean per image behind the partials; an apply block reads
 // that one float.  The other form -- every apply block folding its image's partials in its prologue, one launch fewer -- was timed
 // against it and lost: at 256 x 3 x 224 x 224 (49 partials per image) the apply pass took 71.7 us with the fold in its prologue and
 // 49.5 us behind the fold launch, which adds 4 us to the grey entry (profiles/imagenet_photo.txt); it is kept under

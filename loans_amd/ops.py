@@ -2907,13 +2907,19 @@ def adam_amsgrad(p, g, m, v, vhat, lr_t, beta1, beta2, eps, eta, weight_decay_ra
           'loans_adam_amsgrad_f32')
 
 
+def _rate(lr):
+    """(value, device pointer) of a rate given as a Python float or as a 1-element fp32 device tensor: one of the two is 0"""
+    if not torch.is_tensor(lr):
+        return lr, 0
+    assert lr.dtype == torch.float32 and lr.numel() == 1 and lr.is_cuda
+    return 0.0, _ptr(lr)
+
+
 def momentum_sgd(p, g, v, lr, momentum, weight_decay_rate, grad_scale=1.0):
     """lr: a Python float, or a 1-element device tensor read by the kernel when it runs (graph-capturable)."""
     if CLASS_COUNT is not None: _acct('optimizer', 0, _nbytes(p, g, v), _nbytes(p, v))
-    dev_lr = torch.is_tensor(lr)
-    if dev_lr:
-        assert lr.dtype == torch.float32 and lr.numel() == 1 and lr.is_cuda
-    check(_lib.load().loans_momentum_sgd_f32(_ptr(p), _ptr(g), _ptr(v), p.numel(), 0.0 if dev_lr else lr, _ptr(lr) if dev_lr else 0,
+    lr, lr_dev = _rate(lr)
+    check(_lib.load().loans_momentum_sgd_f32(_ptr(p), _ptr(g), _ptr(v), p.numel(), lr, lr_dev,
                                              momentum, weight_decay_rate, grad_scale, _stream()), 'loans_momentum_sgd_f32')
 
 
@@ -2953,10 +2959,8 @@ def momentum_sgd_seg(p, g, v, lr, momentum, weight_decay_rate, table, grad_scale
     """``momentum_sgd`` with ``weight_decay_rate`` counted as 0 inside the segments of ``table`` (a ``SegmentTable`` over exactly
     ``p.numel()`` floats) whose flag says so."""
     if CLASS_COUNT is not None: _acct('optimizer', 0, _nbytes(p, g, v), _nbytes(p, v))
-    dev_lr = torch.is_tensor(lr)
-    if dev_lr:
-        assert lr.dtype == torch.float32 and lr.numel() == 1 and lr.is_cuda
-    check(_lib.load().loans_momentum_sgd_seg_f32(_ptr(p), _ptr(g), _ptr(v), p.numel(), 0.0 if dev_lr else lr, _ptr(lr) if dev_lr else 0,
+    lr, lr_dev = _rate(lr)
+    check(_lib.load().loans_momentum_sgd_seg_f32(_ptr(p), _ptr(g), _ptr(v), p.numel(), lr, lr_dev,
                                                  momentum, weight_decay_rate, grad_scale, _ptr(table.ends), _ptr(table.flags),
                                                  table.ends_host.ctypes.data, len(table), _stream()), 'loans_momentum_sgd_seg_f32')
 
@@ -3009,10 +3013,8 @@ def lars_ratios(p, g, weight_decay_rate, eta, eps, table, grad_scale=1.0):
 def lars_update(p, g, v, lr, momentum, weight_decay_rate, table, grad_scale=1.0):
     """``momentum_sgd_seg`` with the rate of a segment = fl(fl(lr) * table.ratios[s]), one fp32 product"""
     if CLASS_COUNT is not None: _acct('optimizer', 0, _nbytes(p, g, v), _nbytes(p, v))
-    dev_lr = torch.is_tensor(lr)
-    if dev_lr:
-        assert lr.dtype == torch.float32 and lr.numel() == 1 and lr.is_cuda
-    check(_lib.load().loans_lars_update_f32(_ptr(p), _ptr(g), _ptr(v), p.numel(), 0.0 if dev_lr else lr, _ptr(lr) if dev_lr else 0,
+    lr, lr_dev = _rate(lr)
+    check(_lib.load().loans_lars_update_f32(_ptr(p), _ptr(g), _ptr(v), p.numel(), lr, lr_dev,
                                             momentum, weight_decay_rate, grad_scale, _ptr(table.ends), _ptr(table.flags),
                                             _ptr(table.ratios), table.ends_host.ctypes.data, len(table), _stream()),
           'loans_lars_update_f32')

@@ -1,5 +1,5 @@
-"""Case grid, float64 reference, derived bounds and NumPy restatements for the LARS kernels (csrc/lars.hip: lars_partials_kernel,
-lars_fold_kernel, lars_update_kernel); not collected by pytest.  The same functions run on the restatement (test_cases_cpu.py, before
+"""Case grid, float64 reference, derived bounds and NumPy restatements for the LARS kernels (csrc/sgd.hip: lars_partials_kernel,
+lars_fold_kernel, momentum_sgd_seg_kernel<true>); not collected by pytest.  The same functions run on the restatement (test_cases_cpu.py, before
 any GPU run) and on the kernels (test_gpu_kernels.py, test_gpu_model.py).
 
 THE RULE, per segment s of the flat buffer with flag byte f:
@@ -309,12 +309,12 @@ def ratios_numpy(p, g, ends, flags, wd, gs, eta=ETA, eps=EPS):
 
 
 def segment_rate(lr, r32):
-    """the rate lars_update_kernel applies in a segment: ONE fp32 product of the rate as the kernel holds it"""
+    """the rate momentum_sgd_seg_kernel<true> applies in a segment: ONE fp32 product of the rate as the kernel holds it"""
     return float(F32(lr) * F32(r32))
 
 
 def update_numpy(p, g, v, ratios32, ends, flags, lr, momentum, wd, gs):
-    """lars_update_kernel in NumPy float32, every product rounded (no contraction): (p', v')"""
+    """momentum_sgd_seg_kernel<true> (LARS's update) in NumPy float32, every product rounded (no contraction): (p', v')"""
     p1, v1 = p[:ends[-1]].copy(), v[:ends[-1]].copy()
     lo = 0
     with np.errstate(all='ignore'):

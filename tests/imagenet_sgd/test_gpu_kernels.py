@@ -1,4 +1,4 @@
-"""-m gpu: the momentum-SGD kernel (loans_amd/csrc/misc.hip) and the label-smoothed loss with top-k accuracy
+"""-m gpu: the momentum-SGD kernel (loans_amd/csrc/sgd.hip) and the label-smoothed loss with top-k accuracy
 (loans_amd/csrc/classify.hip) through ``ops`` against float64 NumPy, held to the bounds tests/imagenet_sgd/reference.py derives
 and the CPU test establishes on the fp32 restatements."""
 import numpy as np

@@ -1,5 +1,5 @@
 """Case grid, fp64 reference, derived bound and an fp32 NumPy restatement for the job-table kernel of the weight average
-(csrc/misc.hip: average_jobs_kernel) and the case grid of the segmented momentum SGD (momentum_sgd_seg_kernel); not collected by
+(csrc/misc.hip: average_jobs_kernel) and the case grid of the segmented momentum SGD (csrc/sgd.hip: momentum_sgd_seg_kernel); not collected by
 pytest.  The same functions run on the restatement (test_cases_cpu.py, before any GPU run) and on the kernels
 (test_gpu_kernels.py).
 
