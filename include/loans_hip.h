@@ -797,6 +797,20 @@ int loans_grad_norm_f32(const float* g, int64_t n, double grad_scale, double max
                         float* record_dev /* [0] = N, [1] = k */, void* stream);
 int loans_grad_clip_apply_f32(float* g, int64_t n, const float* record_dev, void* stream);
 
+/* Gradient accumulation (train_imagenet.py --accum-steps K): the gradients of K micro-batches summed in an accumulator the size of
+ * the gradient arena, one launch per micro-batch over the first n floats of both buffers:
+ *   LOANS_ACCUM_STORE:  acc_i = g_i                   the first micro-batch (acc needs no initialisation; g is not written)
+ *   LOANS_ACCUM_ADD:    acc_i = fl32(acc_i + g_i)     micro-batches 2 .. K - 1 (g is not written)
+ *   LOANS_ACCUM_CLOSE:  g_i   = fl32(acc_i + g_i)     the last one: the sum lands in g, acc is not written
+ * The closed gradient is ((g1 + g2) + g3) + .. + gK: one IEEE fp32 addition per element and micro-batch, in that order -- the bits
+ * of torch.add, NaN, inf, signed zeros and subnormals included.  No scaling, no fp64, no atomic; floats behind n are not touched.
+ * LOANS_EINVAL, and no launch: a null pointer, acc or g off a 16-byte boundary, n <= 0, an unknown mode.  LOANS_ERANGE:
+ * n > LOANS_GRAD_CLIP_MAX_N. */
+#define LOANS_ACCUM_STORE 0
+#define LOANS_ACCUM_ADD 1
+#define LOANS_ACCUM_CLOSE 2
+int loans_grad_accum_f32(float* acc, float* g, int64_t n, int32_t mode, void* stream);
+
 /* A table of streaming jobs over float ranges in ONE launch: the exponential moving average of a model's weights
  * (loans_amd/runtime/average.py) -- job 0 the whole parameter arena, the others the ~100 small BN statistics tensors.
  *   LOANS_AVG_UPDATE:  dst += omd * (src - dst)      (omd = 1 - decay; exactly nothing where dst == src)

@@ -53,6 +53,7 @@ class AvgJob(C.Structure):
 
 
 AVG_UNIT, AVG_UPDATE, AVG_SWAP = 4096, 0, 1
+ACCUM_STORE, ACCUM_ADD, ACCUM_CLOSE = 0, 1, 2   # LOANS_ACCUM_*
 LARS_UNIT, LARS_MAX_SEGMENTS = 4096, 1024      # LOANS_LARS_UNIT, LOANS_LARS_MAX_SEGMENTS
 
 
@@ -193,6 +194,7 @@ SIGNATURES = {
     'loans_grad_clip_workspace_bytes': [_i64],
     'loans_grad_norm_f32': [_p, _i64, _f64, _f64, _p, _i64, _p, _p],
     'loans_grad_clip_apply_f32': [_p, _i64, _p, _p],
+    'loans_grad_accum_f32': [_p, _p, _i64, _i32, _p],
     'loans_average_jobs_f32': [_p, _p, _i32, _i64, _i32, _f32, _p],
     'loans_photo_workspace_bytes': [_i32, _i32, _i32],
     'loans_photo_grey_means_f32': [_p, _i32, _i32, _i32, _i32, _p, _p, _p, _i64, _p],

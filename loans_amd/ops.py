@@ -3081,6 +3081,22 @@ def grad_clip_apply(g, state):
     check(_lib.load().loans_grad_clip_apply_f32(_ptr(g), g.numel(), _ptr(state.record), _stream()), 'loans_grad_clip_apply_f32')
 
 
+ACCUM_MODES = {'store': _lib.ACCUM_STORE, 'add': _lib.ACCUM_ADD, 'close': _lib.ACCUM_CLOSE}
+
+
+def grad_accum(acc, g, mode):
+    """One micro-batch of an accumulated step over two float32 buffers of equal size, one launch: ``mode`` 'store' -- ``acc = g``,
+    the first --, 'add' -- ``acc = fl32(acc + g)`` -- or 'close' -- ``g = fl32(acc + g)``, the last: the sum lands where the optimiser
+    reads it and ``acc`` stays.  One fp32 addition per element, ``torch.add``'s bits; the other operand is not written"""
+    if mode not in ACCUM_MODES:
+        raise ValueError("the mode of grad_accum is 'store', 'add' or 'close', got %r" % (mode,))
+    _chk(acc, 'acc'); _chk(g, 'g')
+    if acc.numel() != g.numel() or acc.device != g.device:
+        raise ValueError('acc and g differ in size or device: %d and %d floats' % (acc.numel(), g.numel()))
+    if CLASS_COUNT is not None: _acct('optimizer', 0, _nbytes(g) if mode == 'store' else _nbytes(acc, g), _nbytes(g))
+    check(_lib.load().loans_grad_accum_f32(_ptr(acc), _ptr(g), g.numel(), ACCUM_MODES[mode], _stream()), 'loans_grad_accum_f32')
+
+
 class AverageJobs:
     """The job table of ``average_jobs``: pairs of float32 device tensors ``(dst, src)`` of equal size, kept alive here; the
     table is built and uploaded once."""

@@ -34,6 +34,9 @@ class GradientMethod:
         self._state = None
         self._hooks = {}
         self._pending, self._exchanged_from, self._plan = [], None, None      # staged gradient exchange (data parallel)
+        # gradient accumulation: (arena, accumulator) once accumulate() has run, the micro-batches summed since the last step, the
+        # active prefix they covered, and whether accumulate() is inside its backward
+        self._accum, self._accum_count, self._accum_numel, self._accumulating = None, 0, None, False
 
     def setup(self, link):
         self.target = link
@@ -65,7 +68,68 @@ class GradientMethod:
             self._state = tuple(self._new_state(lambda: torch.zeros(arena.numel, device=arena.device, dtype=torch.float32)))
         return arena
 
+    # ---- gradient accumulation (train_imagenet.py --accum-steps K) ------------------------------------------------------------
+    def _accum_buffer(self, arena):
+        """the accumulator's first ``arena.active_numel`` floats: one buffer the size of the arena, allocated on first use -- an
+        optimiser that never accumulates holds none -- and the prefix held to the one the step's first micro-batch covered"""
+        n = arena.active_numel
+        if self._accum_count == 0:
+            self._accum_numel = n
+        elif n != self._accum_numel:
+            raise RuntimeError('the active parameter prefix changed from %d to %d floats between the micro-batches of one accumulated '
+                               'step' % (self._accum_numel, n))
+        if self._accum is None or self._accum[0] is not arena:
+            self._accum = (arena, torch.empty(arena.numel, device=arena.device, dtype=torch.float32))
+        return self._accum[1][:n]
+
+    def _refuse_mid_step(self, what):
+        if self._accum_count:
+            raise RuntimeError('%s in the middle of an accumulated step (%d micro-batches since the last update()): a checkpoint lies '
+                               'between steps' % (what, self._accum_count))
+
+    def accumulate(self, lossfun, *args, **kwds):
+        """The first half of ``update(lossfun, ...)`` for all micro-batches of a step but the last: evaluate, clear, differentiate,
+        wait for the weight gradients -- then add the gradient arena's active prefix into the accumulator (``ops.grad_accum``: it is
+        stored by the first call since the last step and added by the later ones, one fp32 addition per element) and count the call.
+        Nothing is exchanged, no hook runs, no parameter moves and ``t`` stands still.  The ``update(lossfun, ...)`` of the last
+        micro-batch closes the step: the sum ``((g1 + g2) + ..) + gK`` lands in the gradient arena, is exchanged once, and the
+        step is taken with ``grad_scale = 1 / (K * world size)``.  BN statistics are those of each micro-batch."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('accumulate() launches once per micro-batch from the host: not inside a captured step')
+        self._accumulating = True       # the backward's stage boundaries start no exchange: the arena holds one micro-gradient
+        try:
+            loss = lossfun(*args, **kwds)
+            self.target.cleargrads()
+            loss.backward()
+            del loss
+        finally:
+            self._accumulating = False
+        if not any(p.update_rule.enabled for p in self.target.params()):
+            return
+        arena = self._ensure_state()
+        ops.join_side_stream(arena.device)      # all weight gradients of this micro-batch have landed
+        acc = self._accum_buffer(arena)
+        ops.grad_accum(acc, arena.grad[:acc.numel()], 'add' if self._accum_count else 'store')
+        self._accum_count += 1
+
+    def _close_accumulated(self, arena):
+        """the closing ``update()``: the accumulated sum into the gradient arena, ONE exchange of the whole active prefix behind it
+        (the staged overlap is given up under accumulation: during the closing backward the arena held only the last
+        micro-gradient), and the scale that makes the step the mean over micro-batches and ranks, formed in double"""
+        ops.join_side_stream(arena.device)
+        acc = self._accum_buffer(arena)
+        ops.grad_accum(acc, arena.grad[:acc.numel()], 'close')
+        world = 1
+        if self.comm is not None and getattr(self.comm, 'active', self.comm.size > 1):
+            self.comm.allreduce_grad(arena)
+            world = self.comm.size
+        grad_scale = 1.0 / ((self._accum_count + 1) * world)
+        self._accum_count = 0
+        return grad_scale
+
     def update(self, lossfun=None, *args, **kwds):
+        if self._accum_count and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('an accumulated step is closed from the host: not inside a captured step')
         if lossfun is not None:
             # chainer.GradientMethod.update(lossfun, *args): evaluate, clear, differentiate, then the step below
             # (the LoANs updater calls update() bare, sheep_updater.py:52,66)
@@ -77,7 +141,9 @@ class GradientMethod:
             return
         arena = self._ensure_state()
         grad_scale = 1.0
-        if self._exchanged_from is not None:    # stage_done() / update_begin() already started the exchange of this step
+        if self._accum_count:                   # accumulate() ran since the last step: this backward's was the last micro-batch
+            grad_scale = self._close_accumulated(arena)
+        elif self._exchanged_from is not None:  # stage_done() / update_begin() already started the exchange of this step
             if self._exchanged_from > 0:
                 self._exchange(arena, 0)        # what the stage boundaries left (stem .. res3, or everything below the last one)
             for work in self._pending:
@@ -123,6 +189,8 @@ class GradientMethod:
         self._step(arena, n, self._state, lr, grad_scale)
 
     def _exchange_active(self):
+        if self._accumulating or self._accum_count:
+            return False        # under accumulation stage_done() / update_begin() start nothing: the closing update() exchanges the sum once
         return self.comm is not None and getattr(self.comm, 'active', self.comm.size > 1) and \
             any(p.update_rule.enabled for p in self.target.params())
 
@@ -199,7 +267,9 @@ class GradientMethod:
         dict), ``stepped_cold`` (None before the first step, else the cold links -- res6 / res7, fc6 -- the stepped prefix has
         reached) and ``state``: every state buffer cut per parameter, in the parameter's Chainer layout, under
         ``<param path>/<buffer name>`` with the paths ``state_dict_chainer()`` uses.  Full length: parameters behind the active
-        prefix are included."""
+        prefix are included.  Nothing of a gradient accumulator: a checkpoint lies between steps, where it holds nothing that has to
+        survive -- in the middle of an accumulated step this is a RuntimeError."""
+        self._refuse_mid_step('state_dict()')
         arena = self._ensure_state()
         named = {id(p): k[1:] for k, p in self.target.namedparams()}
         state = {}
@@ -217,6 +287,7 @@ class GradientMethod:
         naming the first offending field or key where the class, ``amsgrad``, the parameter paths or a shape differ; nothing is
         changed then.  The buffers are written in place, so a captured step keeps reading them, and the device copy of the rate
         a captured step reads is republished for the restored ``t``."""
+        self._refuse_mid_step('load_state_dict()')
         if sd['class'] != type(self).__name__:
             raise ValueError('class: the checkpoint holds %s, this optimiser is %s' % (sd['class'], type(self).__name__))
         hp = dict(sd['hyperparam'])

@@ -398,7 +398,12 @@ class Evaluator:
 
 class StandardUpdater:
 
-    def __init__(self, iterator, optimizer, converter=concat_examples, device=None, comm=None):
+    def __init__(self, iterator, optimizer, converter=concat_examples, device=None, comm=None, accum_steps=1):
+        """``accum_steps=K`` > 1: gradient accumulation -- an ``update()`` draws K batches from ``main``, the first K - 1 go through
+        ``optimizer.accumulate``, the last through ``optimizer.update``, which steps once on their summed gradients (``update_core``)."""
+        if isinstance(accum_steps, bool) or not isinstance(accum_steps, (int, np.integer)) or accum_steps < 1:
+            raise ValueError('accum_steps is the number of micro-batches of one optimiser step: an integer >= 1, got %r' % (accum_steps,))
+        self.accum_steps = int(accum_steps)
         if not isinstance(iterator, dict):
             iterator = {'main': iterator}
         if not isinstance(optimizer, dict):
@@ -421,7 +426,10 @@ class StandardUpdater:
 
     @property
     def is_new_epoch(self):
-        return self._iterators['main'].is_new_epoch
+        """Under ``accum_steps`` > 1: whether ANY of the last step's micro-batches crossed the epoch boundary -- a boundary on the
+        first of three would otherwise never log or validate.  (``epoch`` and ``epoch_detail`` stay the iterator's.)"""
+        crossed = self.__dict__.get('_crossed')
+        return self._iterators['main'].is_new_epoch if crossed is None else crossed
 
     def get_optimizer(self, name):
         return self._optimizers[name]
@@ -440,6 +448,8 @@ class StandardUpdater:
         """chainer.training.StandardUpdater: one batch of the ``main`` iterator through ``optimizer.update(target, *arrays)``
         -- forward, cleargrads, backward, step -- inside one step workspace.  Runs in the target's own precision."""
         from .. import ops
+        if self.accum_steps > 1:
+            return self._update_core_accumulated()
         optimizer = self._optimizers['main']
         loss_func = getattr(self, 'loss_func', None) or optimizer.target
         with torch.cuda.device(self.device):
@@ -456,3 +466,45 @@ class StandardUpdater:
                         optimizer.update(loss_func, in_arrays)
                 finally:
                     ops.end_step()
+
+    def _micro_step(self, call):
+        """one batch of the ``main`` iterator through ``call(loss_func, *arrays)`` inside a step workspace of its own, in the
+        target's own precision -- what ``update_core`` does with ``optimizer.update``"""
+        from .. import ops
+        optimizer = self._optimizers['main']
+        loss_func = getattr(self, 'loss_func', None) or optimizer.target
+        with torch.cuda.device(self.device):
+            in_arrays = self.converter(next(self._iterators['main']), self.device)
+            want = optimizer.target.__dict__.get('precision') or ops.current_precision()
+            with ops.precision(*want):
+                ops.begin_step(torch.device('cuda', torch.cuda.current_device()))
+                try:
+                    if isinstance(in_arrays, tuple):
+                        call(loss_func, *in_arrays)
+                    elif isinstance(in_arrays, dict):
+                        call(loss_func, **in_arrays)
+                    else:
+                        call(loss_func, in_arrays)
+                finally:
+                    ops.end_step()
+
+    def _update_core_accumulated(self):
+        """``accum_steps`` = K > 1: K batches of ``main``, the first K - 1 through ``optimizer.accumulate``, the last through
+        ``optimizer.update`` -- one optimiser step on the sum of their gradients, scaled by 1 / K in the optimiser's kernel.
+        ``is_new_epoch`` is true where any of the K crossed the boundary, and what the target reported per micro-batch (``loss``,
+        ``accuracy``, top-k) is reported once more as the mean over the K: sums of device scalars, nothing returns to the host.
+        Every condition here depends on K and on the iterator's position alone, the same on every rank."""
+        from .core import reporter
+        optimizer, iterator = self._optimizers['main'], self._iterators['main']
+        crossed, sums = False, {}
+        for micro in range(self.accum_steps):
+            before = dict(reporter.observation)
+            self._micro_step(optimizer.update if micro == self.accum_steps - 1 else optimizer.accumulate)
+            crossed = crossed or bool(iterator.is_new_epoch)
+            for k, v in reporter.observation.items():
+                if before.get(k) is not v:
+                    v = getattr(v, 'data', v)
+                    v = v.detach().reshape(()).to(torch.float64) if torch.is_tensor(v) else float(v)
+                    sums[k] = sums[k] + v if k in sums else v
+        self._crossed = crossed
+        reporter.report({k: v / self.accum_steps for k, v in sums.items()})

@@ -166,6 +166,25 @@ and the stream's state is part of the checkpoint.
         --cutmix-alpha 1.0 --color-jitter 0.4 0.4 0.4 --random-erase-prob 0.25 --rand-augment 2 9 --ema-decay 0.9999 \
         --clip-grad-norm 1.0 --loss bce --bce-target-thresh 0.2 --drop-path 0.05
 
+``--accum-steps K`` (an integer >= 1; default 1: off) is gradient accumulation, the way to the global batches the ``lars`` and
+``lamb`` lines are tuned for on fewer GPUs: an iteration draws K micro-batches of ``-b`` frames per GPU, sums their gradients -- one
+streaming launch per micro-batch into an accumulator the size of the gradient arena (csrc/accum.hip; ``GradientMethod.accumulate``),
+``((g1 + g2) + ..) + gK`` in fp32 -- and steps once on their mean, so a step sees ``--gpus`` x K x b frames.  ``-b`` stays the batch per
+GPU and micro-batch; ``--lr``, ``--iterations``, the log, snapshot and checkpoint intervals and the warm-up count optimiser steps and
+epochs as before, and nothing is scaled automatically, as for ``--gpus``.  The logged ``loss`` and accuracies of an iteration are
+the means over its K micro-batches, and an iteration is logged and validated as an epoch's last where any of its micro-batches
+crossed the boundary.  Works with every ``--optimizer``, ``--dtype``, ``--loss``, the mixes, ``--drop-path`` (draws per micro-batch),
+``--ema-decay`` (one update per optimiser step), ``--clip-grad-norm`` (the norm of the averaged accumulated gradient) and ``--gpus N``
+(one all-reduce per step, of the sum, behind the last micro-batch: the overlap of the exchange with the backward is given up).  The
+BN statistics are taken per micro-batch, as everywhere else, so an accumulated step is NOT the step of one batch of K x b frames:
+the gradients differ wherever a batch norm lies in front of them, and the running statistics move K times per step.  The option
+is logged as ``accum_steps`` where given and is fixed on resume, like ``-b`` (a checkpoint from before the option ran at 1); a
+checkpoint lies between steps and holds nothing of the accumulator.  Not built: accumulation inside a captured step, and
+``train_sheep_localizer.py`` (two optimisers in one joint step).  The LARS line on one GPU:
+
+    python train_imagenet.py train.tsv val.tsv -b 512 --accum-steps 8 --dtype bf16 --optimizer lars --lr 10 --weight-decay 5e-5 \
+        --no-decay-1d --lr-schedule cosine --warmup-epochs 5 --num-epoch 90 --label-smoothing 0.1 --augment rrc
+
 ``--checkpoint-interval N`` writes a full-state checkpoint, ``checkpoint_<iteration>.npz`` in the log directory, after every
 N-th iteration and after the last one (default 0: none; ``--checkpoint-keep K``, default 2, keeps the newest K): the model with
 its BN statistics, the optimiser's buffers and step count, the training iterator as of the batch the step consumed (shuffle
@@ -175,7 +194,7 @@ stream, order, position, the crop / mirror draw stream, the RandAugment, the pho
 its log directory: the ``log`` file is read back and appended to, ``elapsed_time`` and the snapshot names count on.  Fixed on
 resume (one error lists every one that differs): the architecture, ``--dtype``, ``--optimizer``, ``-b``, ``--gpus``,
 ``--image-size``, the dataset files or the synthetic sizes, classes and ``--data-seed``, ``--no-shuffle``, ``--augment`` /
-``--rrc-*`` / ``--val-crop-pct`` / ``--augment-seed``, ``--mixup-alpha`` / ``--cutmix-alpha`` / ``--mix-*``, ``--color-jitter`` / ``--lighting-std`` / ``--random-erase-*`` / ``--photo-seed``, ``--rand-augment`` / ``--trivial-augment`` / ``--ra-fill`` / ``--ra-seed``, ``--drop-path`` / ``--drop-path-seed``, ``--ema-decay`` (a checkpoint from
+``--rrc-*`` / ``--val-crop-pct`` / ``--augment-seed``, ``--mixup-alpha`` / ``--cutmix-alpha`` / ``--mix-*``, ``--color-jitter`` / ``--lighting-std`` / ``--random-erase-*`` / ``--photo-seed``, ``--rand-augment`` / ``--trivial-augment`` / ``--ra-fill`` / ``--ra-seed``, ``--drop-path`` / ``--drop-path-seed``, ``--accum-steps``, ``--ema-decay`` (a checkpoint from
 before these options existed ran at their defaults), ``--seed``.  Taken from the new command line (each one that differs is
 printed once): ``--num-epoch``, ``--iterations``, the log, snapshot and checkpoint intervals, ``--loader-threads``, the frame
 cache options, ``--lr``, ``--weight-decay``, ``--momentum``, ``--lr-drop-*``, ``--lr-schedule``, ``--lr-min``, ``--no-decay-1d``, ``--lars-eta``, ``--lars-eps``, ``--lamb-beta1``, ``--lamb-beta2``, ``--lamb-eps``, ``--clip-grad-norm``, ``--warmup-*``, ``--label-smoothing``, ``--topk``, ``--loss``, ``--bce-target-thresh``, ``--bce-sum``.  The
@@ -220,7 +239,7 @@ RESUME_FIXED = ('use_resnet_18', 'dtype', 'optimizer', 'batch_size', 'gpus', 'im
                 'validation_size', 'synthetic_classes', 'data_seed', 'no_shuffle', 'augment', 'rrc_scale', 'rrc_ratio', 'val_crop_pct',
                 'augment_seed', 'seed', 'mixup_alpha', 'cutmix_alpha', 'mix_prob', 'mix_switch_prob', 'mix_seed', 'ema_decay',
                 'color_jitter', 'lighting_std', 'random_erase_prob', 'random_erase_scale', 'random_erase_ratio', 'random_erase_value',
-                'photo_seed', 'rand_augment', 'trivial_augment', 'ra_fill', 'ra_seed', 'drop_path', 'drop_path_seed')
+                'photo_seed', 'rand_augment', 'trivial_augment', 'ra_fill', 'ra_seed', 'drop_path', 'drop_path_seed', 'accum_steps')
 
 
 class SyntheticClasses:
@@ -328,6 +347,10 @@ class Arguments(argparse.Namespace):
     drop_path_seed = None
     _DROP = ('drop_path', 'drop_path_seed')
 
+    # --accum-steps: gradient accumulation (loans_amd/runtime/optimizers.py: GradientMethod.accumulate); 1: off, logged only where given
+    accum_steps = 1
+    _ACCUM = ('accum_steps',)
+
 
 def parse_args(argv=None):
     parser = argparse.ArgumentParser(description="ImageNet pre-training of a localizer backbone (MI355X-native)")
@@ -416,6 +439,8 @@ def parse_args(argv=None):
     # stochastic depth
     parser.add_argument("--drop-path", type=float, default=argparse.SUPPRESS, metavar='P', help="stochastic depth: in training, residual unit l of L drops its main branch per sample with probability P l / (L - 1) and scales the kept ones by 1 / (1 - p), P in [0, 1) (default 0: off)")
     parser.add_argument("--drop-path-seed", type=int, default=argparse.SUPPRESS, help="seed of the stochastic depth draws (a stream of their own)")
+    # gradient accumulation
+    parser.add_argument("--accum-steps", type=int, default=argparse.SUPPRESS, metavar='K', help="gradient accumulation: sum the gradients of K micro-batches of -b frames per GPU and step once on their mean; iterations, intervals, --lr and the warm-up count optimiser steps (default 1: off)")
     checkpoint.add_arguments(parser, argparse.SUPPRESS)
     args = parser.parse_args(argv, namespace=Arguments())
     try:
@@ -429,10 +454,11 @@ def parse_args(argv=None):
         check_clip_arguments(args)
         check_loss_arguments(args)
         check_drop_arguments(args)
+        check_accum_arguments(args)
         if args.resume is not None:
             check_average_resume(args)
             world = os.environ.get('WORLD_SIZE')        # a rank under a launcher: the group's size, whatever --gpus says
-            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS_WITH_DROP)
+            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS_WITH_ACCUM)
     except ValueError as e:
         parser.error(str(e))
     return args
@@ -562,6 +588,13 @@ def check_drop_arguments(args):
         raise ValueError('--drop-path is the largest drop probability of a residual unit: it must lie in [0, 1), got %r' % args.drop_path)
 
 
+def check_accum_arguments(args):
+    """ValueError for an --accum-steps that is no number of micro-batches"""
+    k = args.accum_steps
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError('--accum-steps is the number of micro-batches of one optimiser step: it must be an integer >= 1, got %r' % (k,))
+
+
 AVERAGE_RESUME = {False: '--resume: the checkpoint was written without --ema-decay and holds no weight average: resume it without the option',
                   True: '--resume: the checkpoint was written with --ema-decay %g and holds a weight average: resume it with the option'}
 
@@ -596,9 +629,12 @@ RESUME_DEFAULTS_WITH_LOSS = dict(RESUME_DEFAULTS_WITH_CLIP, **RESUME_DEFAULTS_LO
 # ... and for --rand-augment / --trivial-augment / --ra-fill / --ra-seed
 RESUME_DEFAULTS_RA = {name: getattr(Arguments, name) for name in Arguments._RA}
 RESUME_DEFAULTS_WITH_RA = dict(RESUME_DEFAULTS_WITH_LOSS, **RESUME_DEFAULTS_RA)
-# ... and for --drop-path / --drop-path-seed; this is the table --resume uses
+# ... and for --drop-path / --drop-path-seed
 RESUME_DEFAULTS_DROP = {name: getattr(Arguments, name) for name in Arguments._DROP}
 RESUME_DEFAULTS_WITH_DROP = dict(RESUME_DEFAULTS_WITH_RA, **RESUME_DEFAULTS_DROP)
+# ... and for --accum-steps (a checkpoint from before the option ran at 1); this is the table --resume uses
+RESUME_DEFAULTS_ACCUM = {name: getattr(Arguments, name) for name in Arguments._ACCUM}
+RESUME_DEFAULTS_WITH_ACCUM = dict(RESUME_DEFAULTS_WITH_DROP, **RESUME_DEFAULTS_ACCUM)
 
 
 def cache_budgets(total_bytes, n_train, n_validation):
@@ -741,6 +777,7 @@ def run(args, log=print):
     check_clip_arguments(args)
     check_loss_arguments(args)
     check_drop_arguments(args)
+    check_accum_arguments(args)
     chief = comm.rank == 0                     # prints, logs and writes snapshots
 
     # --augment rrc: the iterators hand out (frames, labels) already resident on the device
@@ -829,7 +866,9 @@ def run(args, log=print):
         optimizer.add_hook(clipping)
     topk ='accuracy_top%d' % model.topk if model.topk is not None else None
     train_keys = ('loss', 'accuracy') + ((topk,) if topk else ())
-    updater = training.StandardUpdater(train_iter, optimizer, converter=train_converter, device=args.gpu, comm=comm)
+    # --accum-steps K: an update() draws K batches and steps once (1: the updater as it always was)
+    updater = training.StandardUpdater(train_iter, optimizer, converter=train_converter, device=args.gpu, comm=comm,
+                                       **({'accum_steps': args.accum_steps} if args.accum_steps > 1 else {}))
     # every rank keeps its own average: the parameters agree on all ranks (built after bcast_data), the BN statistics are local
     average = loans_amd.WeightAverage(model, args.ema_decay) if args.ema_decay > 0 else None
 
@@ -875,7 +914,7 @@ def run(args, log=print):
         # the run continues in the checkpoint's log directory: no new <time>_<name>
         check_average_resume(args)
         resumed, changed = checkpoint.resolve_resume(args, RESUME_FIXED, log if chief else (lambda line: None), world=comm.size,
-                                                     defaults=RESUME_DEFAULTS_WITH_DROP)
+                                                     defaults=RESUME_DEFAULTS_WITH_ACCUM)
         args.log_dir = os.path.dirname(os.path.abspath(args.resume))
         for line in changed if chief else ():
             log(line)
@@ -897,6 +936,8 @@ def run(args, log=print):
             continue
         if argument in Arguments._DROP and not drop_given:
             continue
+        if argument in Arguments._ACCUM and 'accum_steps' not in vars(args):
+            continue        # logged where it is given
         if argument in Arguments._LARS and args.optimizer != 'lars':
             continue        # a run with another optimiser logs what it always logged
         if argument in Arguments._LAMB and args.optimizer != 'lamb':
