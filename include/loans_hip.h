@@ -598,6 +598,23 @@ int loans_softmax_xent_mix_fwd_f32(const float* z, const int32_t* ta, const int3
 int loans_sigmoid_bce_fwd_f32(const float* z, const int32_t* ta, const int32_t* tb, float lam, float oml,
                               float* gz, float* row_loss, float* row_hit, float* row_hitk, float* out /* [3] */,
                               int32_t B, int32_t N, double eps, int32_t k, float thresh, int32_t sum_classes, void* stream);
+/* Knowledge distillation: the two-label loss above mixed with the KL divergence from a frozen teacher's logits zt [B][N] at the
+ * temperature T (Hinton's convention; torch's kl_div(log_softmax(z / T), softmax(zt / T), reduction='batchmean') * T * T).  With
+ * invT = fl((float)(1 / T)), the rounded products zs = z invT, zts = zt invT, p = softmax(zts), s = softmax(zs), y = softmax(z):
+ *   hard = lse(z) - sum_i q_i z_i (the mix entry's row loss),  kl = sum_i p_i ((zts_i - lse(zts)) - (zs_i - lse(zs))),
+ *   row_kl = T^2 kl,  row_loss = (1 - alpha) hard + alpha row_kl,  gz = ((1 - alpha)(y - q) + alpha T (s - p)) / count.
+ * kl is formed from shifted logits, never from log(p): finite for every finite pair of rows.  Rows that count, row_hit, row_hitk
+ * (on z) and out[0..2] as for loans_softmax_xent_mix_fwd_f32; row_thit[b] = (argmax zt_b == the dominant label), first index on a
+ * tie; out[3] = sum(row_kl) / count, out[4] = sum(row_thit) / B.  A row that does not count has zeros everywhere.  The weights
+ * (1, 0) / (0, 1) are the one-label loss on ta / on tb: the label of weight zero is not read and does not decide whether a row
+ * counts.  alpha == 0 runs loans_softmax_xent_mix_fwd_f32 itself -- its bits in gz, row_loss, row_hit, row_hitk, out[0..2] -- does
+ * not read zt (which may be NULL) and writes zeros to row_kl, row_thit, out[3], out[4].  No atomics: two runs give the same bits.
+ * Limits as above; LOANS_EINVAL also for a non-finite weight, alpha outside [0, 1], T outside [2^-6, 2^6] (a NaN too), and a
+ * NULL zt at alpha > 0. */
+int loans_softmax_distill_fwd_f32(const float* z, const float* zt, const int32_t* ta, const int32_t* tb, float lam, float oml,
+                                  float* gz, float* row_loss, float* row_hit, float* row_hitk, float* row_kl, float* row_thit,
+                                  float* out /* [5] */, int32_t B, int32_t N, double eps, int32_t k, double alpha, double T,
+                                  void* stream);
 /* Evaluation: the plain loss (eps = 0), the top-1 and the top-k hit of every row as defined above, summed into running totals;
  * no gradient is written.  rows: 3 * B floats of scratch (row loss, hit, top-k hit).  acc[5], doubles, read-modify-write:
  * acc[0] += sum of row losses, acc[1] += top-1 hits, acc[2] += top-k hits, acc[3] += rows not ignored, acc[4] += B.  The five sums

@@ -167,6 +167,7 @@ SIGNATURES = {
     'loans_softmax_xent_ls_fwd_f32': [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _f64, _i32, _p],
     'loans_softmax_xent_mix_fwd_f32': [_p, _p, _p, _f32, _f32, _p, _p, _p, _p, _p, _i32, _i32, _f64, _i32, _p],
     'loans_sigmoid_bce_fwd_f32': [_p, _p, _p, _f32, _f32, _p, _p, _p, _p, _p, _i32, _i32, _f64, _i32, _f32, _i32, _p],
+    'loans_softmax_distill_fwd_f32': [_p, _p, _p, _p, _f32, _f32, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _f64, _i32, _f64, _f64, _p],
     'loans_softmax_xent_eval_f32': [_p, _p, _p, _p, _i32, _i32, _i32, _p],
     'loans_scale_by_scalar_f32': [_p, _p, _p, _i64, _p],
     'loans_mul_f32': [_p, _p, _p, _i64, _p],

@@ -106,7 +106,9 @@ __device__ __forceinline__ int block_count_256(int v, int* sh) {
 }
 
 // ---- one row of logits, shared by the three row kernels below (256 threads, the row kept in LDS) -----------------------------
-// stage zr[0 .. N) into row[] and leave its maximum and the first index that holds it in every thread
+// stage zr[0 .. N) into row[] (STAGE; without it the row is only read) and leave its maximum and the first index that holds it
+// in every thread
+template <bool STAGE = true>
 __device__ __forceinline__ void row_stage_argmax(const float* __restrict__ zr, float* row, int N, float* shf, int* shi,
                                                  float& m, int& am) {
     const int tid = threadIdx.x;
@@ -114,7 +116,7 @@ __device__ __forceinline__ void row_stage_argmax(const float* __restrict__ zr, f
     am = 0x7fffffff;
     for (int i = tid; i < N; i += 256) {
         const float v = zr[i];
-        row[i] = v;
+        if (STAGE) row[i] = v;
         if (v > m || am == 0x7fffffff) { m = v; am = i; }       // strictly greater: the earlier index stays on a tie
     }
 #pragma unroll
@@ -451,6 +453,146 @@ __global__ __launch_bounds__(256) void sigmoid_bce_reduce_kernel(const float* __
     if (tid == 0) { out[0] = L / bce_denom(count, N, sum_classes); out[1] = A / (float)B; out[2] = AK / (float)B; }
 }
 
+// Knowledge distillation against a frozen teacher's logits (loans_softmax_distill_fwd_f32; Hinton's convention, torch's
+// kl_div(log_softmax(z / T), softmax(zt / T), 'batchmean') T^2 beside the mix kernel's hard loss).  With invT = fl(1 / T) from
+// the host and the ROUNDED products zs = fl(z invT), zts = fl(zt invT)  (mul_rounded: never contracted into the subtraction that
+// follows, so the scaled logits are the same numbers wherever they are used, and the maximum of a scaled row is the scaled
+// maximum, rounding being monotone):
+//   y = softmax(z), s = softmax(zs), p = softmax(zts),   hard = the mix kernel's row loss, by its expressions
+//   kl = sum_i p_i (((zts_i - mts) - log St) - ((zs_i - ms) - log Ss))        shifted logits and lse, never log(p): finite for
+//                                                                              every finite pair; p_i == 0 gives 0 * finite = 0
+//   row_kl = T2 kl,   row_loss = oma hard + alpha row_kl,   gz = (oma (y - q) + aT (s - p)) / count
+// oma = fl(1 - alpha), alpha, T2 = fl(T^2), aT = fl(alpha T) are rounded once on the host.  Every other multiply-add is plain C++:
+// a contraction removes the rounding of a product and adds none, and the bound of tests/imagenet_distill/reference.py covers both
+// codes (as for the BCE kernel).  The student row is staged in LDS (N floats, as in every kernel here); the teacher row is read
+// from memory three times -- argmax, sum, gradient -- 4 KB at N = 1000 that stays in the vector cache, which keeps LDS at 32 KB for
+// N = 8192 and the occupancy of the siblings.  Three sums (S, Ss, St) and the mean come from ONE pass over the LDS row, kl from
+// the second.  Bound by launch latency and its eight block reductions, not by bandwidth: 3 MB move at B = 256, N = 1000.
+// A row counts when both labels lie in [0, N); the launcher hands a one-label call the same array twice (as for the BCE kernel).
+// row_thit: the teacher's argmax (first index on a tie, on zt itself) against the dominant label.
+struct Distill { XentMix mx; float invT, oma, alpha, T2, aT; };
+
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
+__global__ __launch_bounds__(256) void softmax_distill_rows_kernel(const float* __restrict__ z, const float* __restrict__ zt,
+                                                                   const int* __restrict__ ta, const int* __restrict__ tb,
+                                                                   float* __restrict__ gz, float* __restrict__ row_loss,
+                                                                   float* __restrict__ row_hit, float* __restrict__ row_hitk,
+                                                                   float* __restrict__ row_kl, float* __restrict__ row_thit,
+                                                                   int B, int N, Distill ds) {
+    extern __shared__ __attribute__((aligned(16))) float row[];
+    __shared__ float shf[4];
+    __shared__ int shi[4];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const float* zr = z + (int64_t)b * N;
+    const float* tr = zt + (int64_t)b * N;
+    float* gr = gz + (int64_t)b * N;
+    const XentMix& mx = ds.mx;
+
+    int valid = 0;
+    for (int i = tid; i < B; i += 256) valid += ((unsigned)ta[i] < (unsigned)N) & ((unsigned)tb[i] < (unsigned)N);
+    const int count = max(block_count_256(valid, shi), 1);
+
+    const int la = ta[b], lb = tb[b];
+    if ((unsigned)la >= (unsigned)N || (unsigned)lb >= (unsigned)N) {       // ignored row (uniform per block)
+        for (int i = tid; i < N; i += 256) gr[i] = 0.f;
+        if (tid == 0) { row_loss[b] = 0.f; row_hit[b] = 0.f; row_hitk[b] = 0.f; row_kl[b] = 0.f; row_thit[b] = 0.f; }
+        return;
+    }
+    float m, mt;
+    int am, amt;
+    row_stage_argmax(zr, row, N, shf, shi, m, am);
+    row_stage_argmax<false>(tr, nullptr, N, shf, shi, mt, amt);
+
+    const int label = mx.lam >= mx.oml ? la : lb;
+    if (tid == 0) { row_hit[b] = (am == label) ? 1.f : 0.f; row_thit[b] = (amt == label) ? 1.f : 0.f; }
+    const int rank = row_rank(row, N, label, row[label], shi);
+    if (tid == 0) row_hitk[b] = (rank < mx.ls.k) ? 1.f : 0.f;
+
+    const float ms = mul_rounded(m, ds.invT), mts = mul_rounded(mt, ds.invT);
+    float s = 0.f, ss = 0.f, st = 0.f, zsum = 0.f;
+    for (int i = tid; i < N; i += 256) {
+        const float v = row[i];
+        s += expf(v - m);
+        ss += expf(mul_rounded(v, ds.invT) - ms);
+        st += expf(mul_rounded(tr[i], ds.invT) - mts);
+        zsum += v;
+    }
+    const float S = block_sum_256(s, shf);
+    const float Ss = block_sum_256(ss, shf);
+    const float St = block_sum_256(st, shf);
+    const float zmix = mx.lam * row[la] + mx.oml * row[lb];
+    float hard;
+    if (mx.ls.eps == 0.f) {
+        hard = (m + logf(S)) - zmix;
+    } else {
+        const float mean = block_sum_256(zsum, shf) / (float)N;
+        hard = ((m + logf(S)) - mx.ls.omeps * zmix) - mx.ls.eps * mean;
+    }
+    const float Ls = logf(Ss), Lt = logf(St);
+    const float fc = (float)count;
+    float kl = 0.f;
+    for (int i = tid; i < N; i += 256) {
+        const float v = row[i];
+        const float y = expf(v - m) / S;
+        const float dz = mul_rounded(v, ds.invT) - ms;
+        const float dt = mul_rounded(tr[i], ds.invT) - mts;
+        const float sp = expf(dz) / Ss;
+        const float p = expf(dt) / St;
+        kl += p * ((dt - Lt) - (dz - Ls));
+        const float w = (i == la ? mx.lam : 0.f) + (i == lb ? mx.oml : 0.f);
+        const float h = y - (mx.ls.omeps * w + mx.ls.q_off);
+        gr[i] = (ds.oma * h + ds.aT * (sp - p)) / fc;
+    }
+    const float KL = block_sum_256(kl, shf);
+    if (tid == 0) {
+        const float rk = ds.T2 * KL;
+        row_kl[b] = rk;
+        row_loss[b] = ds.oma * hard + ds.alpha * rk;
+    }
+}
+
+// softmax_xent_mix_reduce_kernel with the two sums more: out[3] = (sum_b row_kl[b]) / count, out[4] = (sum_b row_thit[b]) / B
+__global__ __launch_bounds__(256) void softmax_distill_reduce_kernel(const float* __restrict__ row_loss, const float* __restrict__ row_hit,
+                                                                     const float* __restrict__ row_hitk, const float* __restrict__ row_kl,
+                                                                     const float* __restrict__ row_thit, const int* __restrict__ ta,
+                                                                     const int* __restrict__ tb, float* __restrict__ out, int B, int N) {
+    __shared__ float shf[4];
+    __shared__ int shi[4];
+    const int tid = threadIdx.x;
+    int valid = 0;
+    float l = 0.f, a = 0.f, ak = 0.f, kl = 0.f, at = 0.f;
+    for (int i = tid; i < B; i += 256) {
+        valid += ((unsigned)ta[i] < (unsigned)N) & ((unsigned)tb[i] < (unsigned)N);
+        l += row_loss[i];
+        a += row_hit[i];
+        ak += row_hitk[i];
+        kl += row_kl[i];
+        at += row_thit[i];
+    }
+    const int count = max(block_count_256(valid, shi), 1);
+    const float L = block_sum_256(l, shf);
+    const float A = block_sum_256(a, shf);
+    const float AK = block_sum_256(ak, shf);
+    const float KL = block_sum_256(kl, shf);
+    const float AT = block_sum_256(at, shf);
+    if (tid == 0) {
+        out[0] = L / (float)count; out[1] = A / (float)B; out[2] = AK / (float)B;
+        out[3] = KL / (float)count; out[4] = AT / (float)B;
+    }
+}
+
+// alpha == 0: the mix entry has written everything else; the teacher's outputs are zeros
+__global__ __launch_bounds__(256) void softmax_distill_zero_kernel(float* __restrict__ row_kl, float* __restrict__ row_thit,
+                                                                   float* __restrict__ out, int B) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < B) { row_kl[i] = 0.f; row_thit[i] = 0.f; }
+    if (i < 2) out[3 + i] = 0.f;
+}
+
 // Evaluation (loans_softmax_xent_eval_f32): the plain loss, the top-1 and the top-k hit of every row -- the eps == 0 expressions
 // of softmax_xent_ls_rows_kernel on the same row code -- and no gradient.  rows: [0, B) loss, [B, 2B) hit, [2B, 3B) top-k hit.
 __global__ __launch_bounds__(256) void softmax_xent_eval_rows_kernel(const float* __restrict__ z, const int* __restrict__ t,
@@ -636,6 +778,41 @@ extern "C" int loans_sigmoid_bce_fwd_f32(const float* z, const int32_t* ta, cons
     LOANS_LAUNCH_CHECK();
     hipLaunchKernelGGL(sigmoid_bce_reduce_kernel, dim3(1), dim3(256), 0, st, row_loss, row_hit, row_hitk, ta, tb, out, B, N,
                        bc.sum_classes);
+    LOANS_LAUNCH_CHECK();
+    return LOANS_OK;
+}
+
+extern "C" int loans_softmax_distill_fwd_f32(const float* z, const float* zt, const int32_t* ta, const int32_t* tb, float lam,
+                                             float oml, float* gz, float* row_loss, float* row_hit, float* row_hitk,
+                                             float* row_kl, float* row_thit, float* out, int32_t B, int32_t N, double eps,
+                                             int32_t k, double alpha, double T, void* stream) {
+    if (!z || !ta || !tb || !gz || !row_loss || !row_hit || !row_hitk || !row_kl || !row_thit || !out || B <= 0 || N <= 0)
+        return LOANS_EINVAL;
+    if (!(eps >= 0.0 && eps < 1.0) || k < 1 || !__builtin_isfinite(lam) || !__builtin_isfinite(oml)) return LOANS_EINVAL;
+    if (!(alpha >= 0.0 && alpha <= 1.0) || !(T >= 0.015625 && T <= 64.0)) return LOANS_EINVAL;        // (a NaN too)
+    if (alpha > 0.0 && !zt) return LOANS_EINVAL;
+    if (N > XENT_MAX_N || B > XENT_MAX_B) return LOANS_ERANGE;
+    hipStream_t st = as_stream(stream);
+    if (alpha == 0.0) {         // the mix entry itself -- its bits -- and zeros; zt is not read
+        if (int rc = loans_softmax_xent_mix_fwd_f32(z, ta, tb, lam, oml, gz, row_loss, row_hit, row_hitk, out, B, N, eps, k, stream))
+            return rc;
+        hipLaunchKernelGGL(softmax_distill_zero_kernel, dim3((B + 255) / 256), dim3(256), 0, st, row_kl, row_thit, out, B);
+        LOANS_LAUNCH_CHECK();
+        return LOANS_OK;
+    }
+    // one label per row: the array that carries the whole weight in both places, so the other one is not read
+    if (lam == 1.f && oml == 0.f) tb = ta;
+    if (lam == 0.f && oml == 1.f) ta = tb;
+    Distill ds;
+    ds.mx.ls.eps = (float)eps; ds.mx.ls.omeps = (float)(1.0 - eps); ds.mx.ls.q_off = (float)(eps / N);
+    ds.mx.ls.q_on = ds.mx.ls.omeps + ds.mx.ls.q_off; ds.mx.ls.k = k; ds.mx.lam = lam; ds.mx.oml = oml;
+    ds.invT = (float)(1.0 / T); ds.oma = (float)(1.0 - alpha); ds.alpha = (float)alpha; ds.T2 = (float)(T * T);
+    ds.aT = (float)(alpha * T);
+    hipLaunchKernelGGL(softmax_distill_rows_kernel, dim3(B), dim3(256), (size_t)N * sizeof(float), st, z, zt, ta, tb, gz, row_loss,
+                       row_hit, row_hitk, row_kl, row_thit, B, N, ds);
+    LOANS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(softmax_distill_reduce_kernel, dim3(1), dim3(256), 0, st, row_loss, row_hit, row_hitk, row_kl, row_thit, ta,
+                       tb, out, B, N);
     LOANS_LAUNCH_CHECK();
     return LOANS_OK;
 }

@@ -197,6 +197,32 @@ class SigmoidBCE(SoftmaxCrossEntropyTopK):
         return out[0], out[1], out[2]
 
 
+DISTILL_T_MIN, DISTILL_T_MAX = 2.0 ** -6, 2.0 ** 6       # the temperatures loans_softmax_distill_fwd_f32 takes
+
+
+class SoftmaxDistill(SoftmaxCrossEntropyTopK):
+    """The target of ``SoftmaxCrossEntropyMixed`` mixed with the KL divergence from a frozen teacher's logits at a temperature
+    (Hinton's convention): inputs (x, teacher logits, t_a, t_b), outputs (loss, accuracy, accuracy_topk, distill_loss,
+    teacher_accuracy) with loss = (1 - alpha) hard + alpha T^2 KL.  The teacher logits are a constant: no gradient flows to them.
+    The backward is the parent's: the forward leaves the whole gradient with respect to ``x`` behind."""
+
+    def __init__(self, lam32, oml32, label_smoothing, topk, alpha, temperature):
+        super().__init__(label_smoothing, topk)
+        self.lam32, self.oml32 = float(lam32), float(oml32)
+        self.alpha, self.temperature = float(alpha), float(temperature)
+
+    def forward(self, inputs):
+        x, zt, ta, tb = (a.contiguous() for a in inputs)
+        out, self.gz = ops.softmax_distill_fwd(x, zt, ta, tb, self.lam32, self.oml32, self.label_smoothing, self.topk,
+                                               self.alpha, self.temperature)[:2]
+        return out[0], out[1], out[2], out[3], out[4]
+
+    def backward(self, inputs, gys):
+        if gys[0] is None:
+            return None, None, None, None
+        return ops.scale_by_scalar(self.gz, gys[0].reshape(1).contiguous()), None, None, None
+
+
 def _as_labels(x, t):
     import numpy as np
     if isinstance(t, Variable):
@@ -239,6 +265,25 @@ def sigmoid_binary_cross_entropy(x, t, label_smoothing=0.0, topk=1, target_thres
         return SigmoidBCE(t.lam32, t.oml32, label_smoothing, topk, target_threshold, sum_classes)(
             x, _as_labels(x, t.t_a.reshape(-1)), _as_labels(x, t.t_b.reshape(-1)))
     return SigmoidBCE(1.0, 0.0, label_smoothing, topk, target_threshold, sum_classes)(x, _as_labels(x, t))
+
+
+def softmax_cross_entropy_distilled(x, teacher_logits, t, label_smoothing=0.0, topk=1, alpha=0.5, temperature=1.0):
+    """(loss, accuracy, accuracy_topk, distill_loss, teacher_accuracy) of the student logits ``x`` against the labels ``t`` (a
+    label array or a ``MixedLabels``) and the logits of a frozen teacher: loss = (1 - alpha) CE(x, smoothed / mixed target)
+    + alpha T^2 KL(softmax(teacher / T) || softmax(x / T)), the mean over the rows with a label.  ``distill_loss`` is the T^2 KL
+    term alone, ``teacher_accuracy`` the teacher's top-1 accuracy against each row's (dominant) label.  The teacher logits are
+    data: whatever graph made them is not walked."""
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError('alpha must be in [0, 1]')
+    if not DISTILL_T_MIN <= temperature <= DISTILL_T_MAX:
+        raise ValueError('temperature must be in [2^-6, 2^6]')
+    zt = teacher_logits.data if isinstance(teacher_logits, Variable) else teacher_logits
+    zt = Variable(zt, requires_grad=False)
+    if isinstance(t, MixedLabels):
+        return SoftmaxDistill(t.lam32, t.oml32, label_smoothing, topk, alpha, temperature)(
+            x, zt, _as_labels(x, t.t_a.reshape(-1)), _as_labels(x, t.t_b.reshape(-1)))
+    labels = _as_labels(x, t)
+    return SoftmaxDistill(1.0, 0.0, label_smoothing, topk, alpha, temperature)(x, zt, labels, labels)
 
 
 def softmax_cross_entropy(x, t, ignore_label=-1):

@@ -2571,6 +2571,30 @@ def sigmoid_bce_fwd(z, ta, tb, lam, oml, eps, k, thresh=None, sum_classes=False)
     return out, gz, row_loss, row_hit, row_hitk
 
 
+def softmax_distill_fwd(z, zt, ta, tb, lam, oml, eps, k, alpha, T):
+    """softmax_xent_mix_fwd mixed with the KL divergence from the teacher logits ``zt`` at the temperature ``T``: per row
+    (1 - alpha) hard + alpha T^2 KL(softmax(zt / T) || softmax(z / T)), gz = ((1 - alpha)(softmax(z) - q) + alpha T (softmax(z / T)
+    - softmax(zt / T))) / count -> (out, gz, row_loss, row_hit, row_hitk, row_kl, row_thit); out[3] the mean of T^2 KL over the rows
+    that count, out[4] the teacher's top-1 accuracy.  alpha == 0 gives softmax_xent_mix_fwd's bits and does not read ``zt`` (which
+    may be None).  No host synchronisation."""
+    assert z.dtype == torch.float32 and z.dim() == 2 and z.is_contiguous(), 'logits must be a contiguous (B, N) fp32 array'
+    for t in (ta, tb):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == z.shape[0] and t.device == z.device, \
+            'labels must be int32, one per row, on the logits\' device'
+    assert zt is None or (zt.dtype == torch.float32 and zt.shape == z.shape and zt.is_contiguous() and zt.device == z.device), \
+        'teacher logits must be a contiguous fp32 array of the logits\' shape on their device'
+    B, N = z.shape
+    gz = _empty_like(z)
+    row_loss, row_hit, row_hitk, row_kl, row_thit = (_empty((B,), device=z.device, dtype=torch.float32) for _ in range(5))
+    out = _empty((5,), device=z.device, dtype=torch.float32)
+    if CLASS_COUNT is not None: _acct('heads', 0, _nbytes(z, zt), _nbytes(gz))
+    check(_lib.load().loans_softmax_distill_fwd_f32(_ptr(z), _ptr(zt), _ptr(ta), _ptr(tb), float(lam), float(oml), _ptr(gz),
+                                                    _ptr(row_loss), _ptr(row_hit), _ptr(row_hitk), _ptr(row_kl), _ptr(row_thit),
+                                                    _ptr(out), B, N, float(eps), int(k), float(alpha), float(T), _stream()),
+          'loans_softmax_distill_fwd_f32')
+    return out, gz, row_loss, row_hit, row_hitk, row_kl, row_thit
+
+
 def batch_mix(x, shift, lam, oml, box=(0, 0, 0, 0), out=None):
     """mixup / CutMix of the device batch x [B][C][H][W] fp32 with itself shifted by ``shift`` rows, one launch on the current
     stream: inside ``box`` = (y0, x0, y1, x1) row b is row (b - shift) % B, outside it lam * x[b] + oml * x[partner] (oml == 0: x[b]

@@ -185,6 +185,31 @@ checkpoint lies between steps and holds nothing of the accumulator.  Not built: 
     python train_imagenet.py train.tsv val.tsv -b 512 --accum-steps 8 --dtype bf16 --optimizer lars --lr 10 --weight-decay 5e-5 \
         --no-decay-1d --lr-schedule cosine --warmup-epochs 5 --num-epoch 90 --label-smoothing 0.1 --augment rrc
 
+``--teacher PATH`` is knowledge distillation: the model is trained against the logits of a frozen, larger one as well as against
+the labels (Hinton et al. 2015), ``loss = (1 - A) CE + A T^2 KL(softmax(teacher / T) || softmax(student / T))`` -- torch's
+``kl_div(log_softmax(z / T), softmax(zt / T), reduction='batchmean') * T * T`` beside the cross-entropy.  ``PATH`` is a snapshot
+as this script writes it, the ``_ema_`` one included; ``--teacher-arch {resnet18,resnet50}`` (default ``resnet50``) names the
+localizer that wrote it, ``--teacher-dtype {fp32,bf16}`` the arithmetic of its forward (default: the run's ``--dtype``),
+``--distill-alpha A`` (``0 < A <= 1``, default 0.5) the weight of the KL term and ``--distill-temperature T`` (``2^-6 <= T <= 2^6``,
+default 1) the temperature.  Every rank loads the file itself, strictly (a file that lacks a parameter or a BN statistic of the
+architecture is refused).  In a training step the teacher runs first, in test mode and without backprop, on the very batch the
+student sees -- mixed by mixup / CutMix where those are on -- then the student, then one loss launch over both logit matrices
+(csrc/classify.hip, ``loans_softmax_distill_fwd_f32``).  ``--label-smoothing`` smooths the hard part only, ``--drop-path`` drops in
+the student only, the weight average is the student's.  The teacher is no part of the model: it has an arena of its own, takes
+no gradient, and joins neither the optimiser, the data-parallel exchange, the weight average, the snapshots nor the
+checkpoints.  Every log entry gains ``distill_loss`` (the ``T^2 KL`` term, the mean over the rows with a label) and
+``teacher_accuracy`` (the teacher's top-1 accuracy on the training batches, against the dominant label of a mixed row); ``loss`` is
+the whole training loss, and validation is what it always was -- the plain softmax cross-entropy of the student, the teacher not
+run.  The five options are logged in the first entry where ``--teacher`` is given and are not fixed on resume: a checkpoint
+holds nothing of the teacher, and ``--resume`` needs ``--teacher`` again if the run is to go on distilling.  Works with every
+``--optimizer``, ``--gpus N``, ``--accum-steps`` (the means over the micro-batches are logged) and ``--ema-decay``; not with
+``--loss bce``.  Not built: feature / hint losses, several teachers, teacher logits cached on disk, a teacher in
+``train_sheep_localizer.py`` or in a captured step.  A ResNet-18 student under the averaged ResNet-50 of an earlier run:
+
+    python train_imagenet.py train.tsv val.tsv --use-resnet-18 -b 256 --dtype bf16 --optimizer sgd --lr 0.1 --weight-decay 5e-5 \
+        --no-decay-1d --lr-schedule cosine --warmup-epochs 5 --num-epoch 100 --augment rrc --label-smoothing 0.1 --ema-decay 0.9999 \
+        --teacher imagenet_logs/<time>_r50/Resnet50SheepLocalizer_ema_<iteration>.npz --distill-alpha 0.5 --distill-temperature 4
+
 ``--checkpoint-interval N`` writes a full-state checkpoint, ``checkpoint_<iteration>.npz`` in the log directory, after every
 N-th iteration and after the last one (default 0: none; ``--checkpoint-keep K``, default 2, keeps the newest K): the model with
 its BN statistics, the optimiser's buffers and step count, the training iterator as of the batch the step consumed (shuffle
@@ -197,7 +222,7 @@ resume (one error lists every one that differs): the architecture, ``--dtype``, 
 ``--rrc-*`` / ``--val-crop-pct`` / ``--augment-seed``, ``--mixup-alpha`` / ``--cutmix-alpha`` / ``--mix-*``, ``--color-jitter`` / ``--lighting-std`` / ``--random-erase-*`` / ``--photo-seed``, ``--rand-augment`` / ``--trivial-augment`` / ``--ra-fill`` / ``--ra-seed``, ``--drop-path`` / ``--drop-path-seed``, ``--accum-steps``, ``--ema-decay`` (a checkpoint from
 before these options existed ran at their defaults), ``--seed``.  Taken from the new command line (each one that differs is
 printed once): ``--num-epoch``, ``--iterations``, the log, snapshot and checkpoint intervals, ``--loader-threads``, the frame
-cache options, ``--lr``, ``--weight-decay``, ``--momentum``, ``--lr-drop-*``, ``--lr-schedule``, ``--lr-min``, ``--no-decay-1d``, ``--lars-eta``, ``--lars-eps``, ``--lamb-beta1``, ``--lamb-beta2``, ``--lamb-eps``, ``--clip-grad-norm``, ``--warmup-*``, ``--label-smoothing``, ``--topk``, ``--loss``, ``--bce-target-thresh``, ``--bce-sum``.  The
+cache options, ``--lr``, ``--weight-decay``, ``--momentum``, ``--lr-drop-*``, ``--lr-schedule``, ``--lr-min``, ``--no-decay-1d``, ``--lars-eta``, ``--lars-eps``, ``--lamb-beta1``, ``--lamb-beta2``, ``--lamb-eps``, ``--clip-grad-norm``, ``--warmup-*``, ``--label-smoothing``, ``--topk``, ``--loss``, ``--bce-target-thresh``, ``--bce-sum``, ``--teacher`` with ``--teacher-arch``, ``--teacher-dtype``, ``--distill-alpha`` and ``--distill-temperature``.  The
 frame caches start empty after a resume and refill during the first epoch.
 
     python train_imagenet.py train.tsv val.tsv -b 256 --optimizer sgd --lr 0.1 --lr-drop-epochs 30 60 90 --checkpoint-interval 500
@@ -351,6 +376,16 @@ class Arguments(argparse.Namespace):
     accum_steps = 1
     _ACCUM = ('accum_steps',)
 
+    # --teacher: knowledge distillation from a frozen snapshot (loans_amd/classifier.py, csrc/classify.hip:
+    # loans_softmax_distill_fwd_f32); None: nothing is loaded, launched or logged.  teacher_dtype None: the run's --dtype;
+    # distill_alpha None: 0.5 with a teacher
+    teacher = None
+    teacher_arch = 'resnet50'
+    teacher_dtype = None
+    distill_alpha = None
+    distill_temperature = 1.0
+    _DISTILL = ('teacher', 'teacher_arch', 'teacher_dtype', 'distill_alpha', 'distill_temperature')
+
 
 def parse_args(argv=None):
     parser = argparse.ArgumentParser(description="ImageNet pre-training of a localizer backbone (MI355X-native)")
@@ -441,6 +476,12 @@ def parse_args(argv=None):
     parser.add_argument("--drop-path-seed", type=int, default=argparse.SUPPRESS, help="seed of the stochastic depth draws (a stream of their own)")
     # gradient accumulation
     parser.add_argument("--accum-steps", type=int, default=argparse.SUPPRESS, metavar='K', help="gradient accumulation: sum the gradients of K micro-batches of -b frames per GPU and step once on their mean; iterations, intervals, --lr and the warm-up count optimiser steps (default 1: off)")
+    # knowledge distillation
+    parser.add_argument("--teacher", default=argparse.SUPPRESS, metavar='PATH', help="distil from this frozen snapshot (a <Localizer>_<it>.npz or _ema_ file as this script writes it): loss = (1 - A) CE + A T^2 KL(teacher || student); every rank loads it itself (default: off)")
+    parser.add_argument("--teacher-arch", default=argparse.SUPPRESS, choices=['resnet18', 'resnet50'], help="with --teacher: the localizer the snapshot was written by (default resnet50)")
+    parser.add_argument("--teacher-dtype", default=argparse.SUPPRESS, choices=['fp32', 'f32', 'bf16'], help="with --teacher: the arithmetic of the teacher's forward (default: the run's --dtype)")
+    parser.add_argument("--distill-alpha", type=float, default=argparse.SUPPRESS, metavar='A', help="with --teacher: the weight of the distillation term, A in (0, 1] (default 0.5)")
+    parser.add_argument("--distill-temperature", type=float, default=argparse.SUPPRESS, metavar='T', help="with --teacher: the temperature both logit rows are divided by, T in [2^-6, 2^6] (default 1)")
     checkpoint.add_arguments(parser, argparse.SUPPRESS)
     args = parser.parse_args(argv, namespace=Arguments())
     try:
@@ -455,6 +496,7 @@ def parse_args(argv=None):
         check_loss_arguments(args)
         check_drop_arguments(args)
         check_accum_arguments(args)
+        check_distill_arguments(args)
         if args.resume is not None:
             check_average_resume(args)
             world = os.environ.get('WORLD_SIZE')        # a rank under a launcher: the group's size, whatever --gpus says
@@ -595,6 +637,55 @@ def check_accum_arguments(args):
         raise ValueError('--accum-steps is the number of micro-batches of one optimiser step: it must be an integer >= 1, got %r' % (k,))
 
 
+DISTILL_T_RANGE = (2.0 ** -6, 2.0 ** 6)     # the temperatures loans_softmax_distill_fwd_f32 takes
+
+
+def check_distill_arguments(args):
+    """ValueError for a distillation option without --teacher, for a weight or a temperature outside the loss's limits, and for
+    --loss bce with a teacher (not built)"""
+    if args.teacher is None:
+        given = [name for name in Arguments._DISTILL[1:] if name in vars(args)]
+        if given:
+            raise ValueError('--%s belongs to --teacher: give the snapshot to distil from' % given[0].replace('_', '-'))
+        return
+    if args.loss == 'bce':
+        raise ValueError('--teacher with --loss bce is not built: distillation mixes the softmax cross-entropy with the KL term')
+    if args.teacher_arch not in ('resnet18', 'resnet50'):
+        raise ValueError('--teacher-arch is resnet18 or resnet50, got %r' % (args.teacher_arch,))
+    if args.teacher_dtype not in (None, 'fp32', 'f32', 'bf16'):
+        raise ValueError('--teacher-dtype is fp32 or bf16, got %r' % (args.teacher_dtype,))
+    a = args.distill_alpha
+    if a is not None and not 0.0 < a <= 1.0:
+        raise ValueError('--distill-alpha is the weight of the distillation term: it must lie in (0, 1] (0 is a run without '
+                         '--teacher), got %r' % a)
+    t = args.distill_temperature
+    if not DISTILL_T_RANGE[0] <= t <= DISTILL_T_RANGE[1]:
+        raise ValueError('--distill-temperature must lie in [2^-6, 2^6], got %r' % t)
+
+
+def distill_options(args):
+    """(alpha, temperature, the teacher's dtype as --dtype spells it) of a run with --teacher, the defaults resolved"""
+    dtype = args.dtype if args.teacher_dtype is None else {'fp32': 'f32'}.get(args.teacher_dtype, args.teacher_dtype)
+    return (0.5 if args.distill_alpha is None else float(args.distill_alpha)), float(args.distill_temperature), dtype
+
+
+def build_teacher(args):
+    """the frozen teacher of --teacher: the localizer of --teacher-arch in its ``train_imagenet`` form with the snapshot's values,
+    loaded strictly (every parameter and BN statistic of the architecture must be in the file); host side only"""
+    localizer_class = loans_amd.SheepLocalizer if args.teacher_arch == 'resnet18' else loans_amd.Resnet50SheepLocalizer
+    state = np.random.get_state()           # the initialisers' draws are overwritten: the student's --seed stream stays as it was
+    try:
+        teacher = localizer_class((75, 75), train_imagenet=True)
+        loans_amd.Classifier(teacher).materialize()
+    finally:
+        np.random.set_state(state)
+    try:
+        loans_amd.load_npz(args.teacher, teacher, strict=True)
+    except (KeyError, AssertionError) as e:
+        raise ValueError('--teacher %s is no snapshot of a %s localizer: %r' % (args.teacher, args.teacher_arch, e))
+    return teacher
+
+
 AVERAGE_RESUME = {False: '--resume: the checkpoint was written without --ema-decay and holds no weight average: resume it without the option',
                   True: '--resume: the checkpoint was written with --ema-decay %g and holds a weight average: resume it with the option'}
 
@@ -686,8 +777,14 @@ def build_model(args):
     if args.seed is not None:
         np.random.seed(args.seed)
     localizer_class = loans_amd.SheepLocalizer if args.use_resnet_18 else loans_amd.Resnet50SheepLocalizer
+    distill = {}
+    if args.teacher is not None:
+        alpha, temperature, teacher_dtype = distill_options(args)
+        teacher = build_teacher(args)
+        teacher.set_precision(*(('bf16', 'bf16') if teacher_dtype == 'bf16' else ('f32', 'f32')))
+        distill = dict(teacher=teacher, distill_alpha=alpha, distill_temperature=temperature)
     model = loans_amd.Classifier(localizer_class((75, 75), train_imagenet=True), label_smoothing=args.label_smoothing,
-                                 topk=resolved_topk(args), **loss_options(args))
+                                 topk=resolved_topk(args), **loss_options(args), **distill)
     model.materialize()         # the ResNet-18 variant's lazily sized fc
     return model
 
@@ -778,6 +875,10 @@ def run(args, log=print):
     check_loss_arguments(args)
     check_drop_arguments(args)
     check_accum_arguments(args)
+    check_distill_arguments(args)
+    if args.teacher is not None:                # the values this run distils with, logged in the first entry
+        args.distill_alpha, args.distill_temperature, args.teacher_dtype = distill_options(args)
+        args.teacher_arch = args.teacher_arch
     chief = comm.rank == 0                     # prints, logs and writes snapshots
 
     # --augment rrc: the iterators hand out (frames, labels) already resident on the device
@@ -866,6 +967,8 @@ def run(args, log=print):
         optimizer.add_hook(clipping)
     topk ='accuracy_top%d' % model.topk if model.topk is not None else None
     train_keys = ('loss', 'accuracy') + ((topk,) if topk else ())
+    if args.teacher is not None:
+        train_keys += ('distill_loss', 'teacher_accuracy')
     # --accum-steps K: an update() draws K batches and steps once (1: the updater as it always was)
     updater = training.StandardUpdater(train_iter, optimizer, converter=train_converter, device=args.gpu, comm=comm,
                                        **({'accum_steps': args.accum_steps} if args.accum_steps > 1 else {}))
@@ -946,6 +1049,8 @@ def run(args, log=print):
             continue
         if argument in Arguments._LOSS and not any(name in vars(args) for name in Arguments._LOSS):
             continue        # logged where one of them is given
+        if argument in Arguments._DISTILL and args.teacher is None:
+            continue        # logged with a teacher only
         # (an entry's ``loss`` is the training loss: the option of that name is logged as ``loss_function``)
         data_to_log['loss_function' if argument == 'loss' else argument] = getattr(args, argument)
     log_entries = []
