@@ -1028,6 +1028,56 @@ int loans_bn_bwd_apply_rows_bf16(const void* gy, const uint8_t* signbits, const 
                                  const float* k2, const float* k3, void* gx, const void* x2, const float* k1b, const float* k2b,
                                  const float* k3b, void* gx2, int32_t B, int64_t rows_per_sample, int32_t C, void* stream);
 
+/* ---- squeeze-and-excitation at a residual unit's junction (csrc/se.hip; Hu et al. 2018).  The tensors are [B][rows_per_sample][C]
+ *      (NHWC, P = rows_per_sample = Ho * Wo); q = mean_p bn(x), h = relu(W1 q + b1), s = sigmoid(W2 h + b2) with W1 [hidden][C],
+ *      W2 [C][hidden]; y = relu(s[b][c] (x scale + shift) + second).  Gate tables and sums are fp32 / fp64 whatever the storage.
+ *      loans_se_slabs: the partial records per sample of the two reductions for this shape (elt_bytes 4 / 2), or an error.
+ *      loans_se_squeeze_*: S[B][C] = sum_p x (the squeeze is linear: q = scale S / P + shift).  partial: B * slabs * C floats
+ *      (may be null where slabs == 1).
+ *      loans_se_excite_fwd_f32: q, h, s from S and the BN coefficients; writes s[B][C], h[B][hidden], q[B][C].
+ *      loans_bn_apply_gate_*: loans_bn_apply_rows_* with s[b][c] in place of r[b]; modes 1 / 2, sign bits always.
+ *      loans_se_bwd_reduce_*: with g = gy * bit, G0 = sum_p g, G1 = sum_p g x, and with x2 G2 = sum_p g x2, each [B][C] fp32.
+ *      partial: B * slabs * (x2 ? 3 : 2) * C doubles.
+ *      loans_se_excite_bwd_f32: ds = scale G1 + shift G0, da2 = ds s (1 - s), dh = (W2^T da2)(h > 0), dq = W1^T dh; writes
+ *      t[B][C] = dq / P; ADDS the batch sums to gW1 / gb1 / gW2 / gb2; writes replica 0 of sums (fp64 [replicas][2][C], with G2
+ *      [replicas][4][C]: loans_bn_bwd_reduce_rows_*'s layout, the other replicas stay as the caller zeroed them) =
+ *      [sum gz | sum gz xhat] of gz = s g + t, then [sum g | sum g xhat2], for loans_bn_bwd_coeffs_rep_f32 (centred = 0).
+ *      Scratch da2: B * C floats, dh: B * hidden floats, u: B * 2 * C doubles.
+ *      loans_bn_bwd_apply_gate_*: gx = k1 (s[b][c] g + t[b][c]) + k2 x + k3, and with x2: gx2 = k1b g + k2b x2 + k3b.
+ *      LOANS_EINVAL for null or misaligned pointers, non-positive sizes, C / V units per row (V = 4 fp32 / 8 bf16 channels) neither a
+ *      divisor nor a multiple of 256, C > 2048 or hidden < 4, > 512 or not a multiple of 4 in the excitation; LOANS_ERANGE for
+ *      a sample of 2^30 units or more or B > 65535.  No floating-point atomics: two runs give the same bits.  Nothing waits for
+ *      the host. ---- */
+int loans_se_slabs(int32_t B, int64_t rows_per_sample, int32_t C, int32_t elt_bytes);
+int loans_se_squeeze_f32(const float* x, float* S, float* partial, int32_t B, int64_t rows_per_sample, int32_t C, void* stream);
+int loans_se_squeeze_bf16(const void* x, float* S, float* partial, int32_t B, int64_t rows_per_sample, int32_t C, void* stream);
+int loans_se_excite_fwd_f32(const float* S, const float* scale, const float* shift, const float* W1, const float* b1,
+                            const float* W2, const float* b2, float* s, float* h, float* q, int32_t B, int64_t rows_per_sample,
+                            int32_t C, int32_t hidden, void* stream);
+int loans_bn_apply_gate_f32(const float* x, const float* scale, const float* shift, const float* x2, const float* scale2,
+                            const float* shift2, const float* s, float* y, uint8_t* signbits, int32_t B, int64_t rows_per_sample,
+                            int32_t C, int32_t mode, void* stream);
+int loans_bn_apply_gate_bf16(const void* x, const float* scale, const float* shift, const void* x2, const float* scale2,
+                             const float* shift2, const float* s, void* y, uint8_t* signbits, int32_t B, int64_t rows_per_sample,
+                             int32_t C, int32_t mode, void* stream);
+int loans_se_bwd_reduce_f32(const float* gy, const uint8_t* signbits, const float* x, const float* x2, float* G0, float* G1,
+                            float* G2, double* partial, int32_t B, int64_t rows_per_sample, int32_t C, void* stream);
+int loans_se_bwd_reduce_bf16(const void* gy, const uint8_t* signbits, const void* x, const void* x2, float* G0, float* G1,
+                             float* G2, double* partial, int32_t B, int64_t rows_per_sample, int32_t C, void* stream);
+int loans_se_excite_bwd_f32(const float* G0, const float* G1, const float* G2, const float* S, const float* scale,
+                            const float* shift, const float* mean, const float* rstd, const float* mean2, const float* rstd2,
+                            const float* s, const float* h, const float* q, const float* W1, const float* W2, float* t, float* da2,
+                            float* dh, double* u, float* gW1, float* gb1, float* gW2, float* gb2, double* sums, int32_t B,
+                            int64_t rows_per_sample, int32_t C, int32_t hidden, void* stream);
+int loans_bn_bwd_apply_gate_f32(const float* gy, const uint8_t* signbits, const float* s, const float* t, const float* x,
+                                const float* k1, const float* k2, const float* k3, float* gx, const float* x2, const float* k1b,
+                                const float* k2b, const float* k3b, float* gx2, int32_t B, int64_t rows_per_sample, int32_t C,
+                                void* stream);
+int loans_bn_bwd_apply_gate_bf16(const void* gy, const uint8_t* signbits, const float* s, const float* t, const void* x,
+                                 const float* k1, const float* k2, const float* k3, void* gx, const void* x2, const float* k1b,
+                                 const float* k2b, const float* k3b, void* gx2, int32_t B, int64_t rows_per_sample, int32_t C,
+                                 void* stream);
+
 /* library / build identification */
 const char* loans_hip_version(void);
 

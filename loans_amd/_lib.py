@@ -209,12 +209,23 @@ SIGNATURES = {
     'loans_bn_bwd_reduce_rows_bf16': [_p] * 10 + [_i32, _i32, _i64, _i32, _p],
     'loans_bn_bwd_apply_rows_f32': [_p] * 13 + [_i32, _i64, _i32, _p],
     'loans_bn_bwd_apply_rows_bf16': [_p] * 13 + [_i32, _i64, _i32, _p],
+    'loans_se_slabs': [_i32, _i64, _i32, _i32],
+    'loans_se_squeeze_f32': [_p] * 3 + [_i32, _i64, _i32, _p],
+    'loans_se_squeeze_bf16': [_p] * 3 + [_i32, _i64, _i32, _p],
+    'loans_se_excite_fwd_f32': [_p] * 10 + [_i32, _i64, _i32, _i32, _p],
+    'loans_bn_apply_gate_f32': [_p] * 9 + [_i32, _i64, _i32, _i32, _p],
+    'loans_bn_apply_gate_bf16': [_p] * 9 + [_i32, _i64, _i32, _i32, _p],
+    'loans_se_bwd_reduce_f32': [_p] * 8 + [_i32, _i64, _i32, _p],
+    'loans_se_bwd_reduce_bf16': [_p] * 8 + [_i32, _i64, _i32, _p],
+    'loans_se_excite_bwd_f32': [_p] * 24 + [_i32, _i64, _i32, _i32, _p],
+    'loans_bn_bwd_apply_gate_f32': [_p] * 14 + [_i32, _i64, _i32, _p],
+    'loans_bn_bwd_apply_gate_bf16': [_p] * 14 + [_i32, _i64, _i32, _p],
 }
 
 # every entry point returns int (0 / LOANS_E* / hipError_t) except:
 RESTYPES = {'loans_wgrad_bf16s_ws_floats': C.c_int64, 'loans_crop_band_rows': C.c_int, 'loans_momentum_sgd_max_segments': C.c_int,
             'loans_lars_workspace_bytes': C.c_int64, 'loans_photo_workspace_bytes': C.c_int64,
-            'loans_grad_clip_workspace_bytes': C.c_int64, 'loans_ra_workspace_bytes': C.c_int64}    # (sizes / counts, not a status)
+            'loans_grad_clip_workspace_bytes': C.c_int64, 'loans_ra_workspace_bytes': C.c_int64, 'loans_se_slabs': C.c_int}    # (sizes / counts, not a status)
 
 _lib = None
 

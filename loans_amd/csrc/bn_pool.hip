@@ -4,15 +4,11 @@
 // elements, per-channel coefficients re-read from L1/L2.  Reductions go per-thread (fp32)
 // -> LDS across the block -> one fp64 atomic per channel per block.
 #include "common.h"
+#include "unit16.h"
 
 namespace {
 
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ f32x4 relu4(f32x4 v) {
-    v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-    return v;
-}
 __device__ __forceinline__ f32x4 maskpos4(f32x4 g, f32x4 m) {
     g.x = m.x > 0.f ? g.x : 0.f; g.y = m.y > 0.f ? g.y : 0.f;
     g.z = m.z > 0.f ? g.z : 0.f; g.w = m.w > 0.f ? g.w : 0.f;
@@ -60,17 +56,6 @@ __global__ void bn_eval_coeffs_kernel(int C, float eps, const float* gamma, cons
     const float sc = gamma[c] * rs;
     scale[c] = sc;
     shift[c] = beta[c] - rmean[c] * sc;
-}
-
-// signbits (optional): one byte per four channels, bit e = (y[4i + e] > 0) -- the ReLU mask the backward passes of this BN
-// need, at 1/16 (fp32) or 1/8 (bf16) of the bytes of y
-__device__ __forceinline__ uint8_t posbits4(f32x4 v) {
-    return (uint8_t)((v.x > 0.f ? 1 : 0) | (v.y > 0.f ? 2 : 0) | (v.z > 0.f ? 4 : 0) | (v.w > 0.f ? 8 : 0));
-}
-__device__ __forceinline__ f32x4 maskbits4(f32x4 g, uint8_t m) {
-    g.x = (m & 1) ? g.x : 0.f; g.y = (m & 2) ? g.y : 0.f;
-    g.z = (m & 4) ? g.z : 0.f; g.w = (m & 8) ? g.w : 0.f;
-    return g;
 }
 
 template <int MODE, typename T>
@@ -531,48 +516,11 @@ __global__ __launch_bounds__(256) void igemm_finalize_kernel(float* out, const f
 // count per row U = C / V divides the block size and the grid stride is a multiple of it, ALWAYS THE SAME channels: the
 // coefficients are loaded once into registers, the loop is loads, a few FMAs and stores, two units in flight.  Offered where
 // U <= 256 divides 256 (every BN of both localizers); other channel counts keep the kernels above.
-template <typename T> struct unit16;
-template <> struct unit16<float> {
-    static constexpr int V = 4, NV = 1;
-    typedef f32x4 raw_t;
-    template <bool NT = false> static __device__ __forceinline__ raw_t ldr(const float* p) {
-        if (NT) return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-        return *reinterpret_cast<const f32x4*>(p);
-    }
-    static __device__ __forceinline__ void cvt(raw_t r, f32x4* v) { v[0] = r; }
-    static __device__ __forceinline__ void ld(const float* p, f32x4* v) { v[0] = *reinterpret_cast<const f32x4*>(p); }
-    template <bool NT = false> static __device__ __forceinline__ void st(float* p, const f32x4* v) {
-        if (NT) __builtin_nontemporal_store(v[0], reinterpret_cast<f32x4*>(p));
-        else *reinterpret_cast<f32x4*>(p) = v[0];
-    }
-};
-template <> struct unit16<__bf16> {
-    static constexpr int V = 8, NV = 2;
-    typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-    typedef bf16x8 raw_t;
-    template <bool NT = false> static __device__ __forceinline__ raw_t ldr(const __bf16* p) {
-        if (NT) return __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(p));
-        return *reinterpret_cast<const bf16x8*>(p);
-    }
-    static __device__ __forceinline__ void cvt(raw_t r, f32x4* v) {
-        v[0] = __builtin_convertvector(__builtin_shufflevector(r, r, 0, 1, 2, 3), f32x4);
-        v[1] = __builtin_convertvector(__builtin_shufflevector(r, r, 4, 5, 6, 7), f32x4);
-    }
-    static __device__ __forceinline__ void ld(const __bf16* p, f32x4* v) { cvt(ldr(p), v); }
-    template <bool NT = false> static __device__ __forceinline__ void st(__bf16* p, const f32x4* v) {
-        const loans_bf16x4 a = __builtin_convertvector(v[0], loans_bf16x4), b = __builtin_convertvector(v[1], loans_bf16x4);
-        const bf16x8 r = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-        if (NT) __builtin_nontemporal_store(r, reinterpret_cast<bf16x8*>(p));
-        else *reinterpret_cast<bf16x8*>(p) = r;
-    }
-};
-
 // The units one block streams (round 3, tools/stream_patterns.hip): its own CONTIGUOUS slab, a multiple of 256 units long so
 // that a thread's channel unit stays tid % U, walked 256 units at a time with SLAB_UNR steps in flight.  Two reads + one write
 // of 512 MiB bf16 tensors: 5.3-5.8 TB/s like this against 4.3-4.8 for a grid-stride walk of persistent blocks (the form of
 // the first u16 kernels: every block touching every part of the tensor) -- what an HBM page sees is a dense burst, not a
 // trickle from 4096 blocks.  NT: non-temporal loads and stores (+5 % on tensors far beyond the 256 MB Infinity Cache).
-constexpr int SLAB_UNR = 4;
 struct Slab { int64_t i, end; };
 __device__ __forceinline__ Slab slab_of(int64_t nunits) {
     const int64_t per = ((nunits + gridDim.x - 1) / gridDim.x + 255) & ~(int64_t)255;
@@ -580,23 +528,6 @@ __device__ __forceinline__ Slab slab_of(int64_t nunits) {
     return Slab{lo + threadIdx.x, lo + per < nunits ? lo + per : nunits};
 }
 static inline int slab_grid(int64_t nunits) { return grid_for(nunits, 256 * SLAB_UNR, 8192); }
-// LOANS_BN_NT: 0 never, 1 always, unset: tensors of at least 96 MB (they cannot stay in the Infinity Cache with their partners)
-static inline bool slab_nt(int64_t tensor_bytes) {
-    static const int mode = [] { const char* e = getenv("LOANS_BN_NT"); return e && *e ? atoi(e) : -1; }();
-    constexpr long mb = 96;
-    return mode < 0 ? tensor_bytes >= ((int64_t)mb << 20) : mode != 0;
-}
-
-// one byte of sign bits per four channels: a unit owns NV consecutive bytes
-template <int NV> __device__ __forceinline__ void st_bits(uint8_t* p, const f32x4* v) {
-    if (NV == 1) p[0] = posbits4(v[0]);
-    else *reinterpret_cast<uint16_t*>(p) = (uint16_t)(posbits4(v[0]) | (posbits4(v[1]) << 8));
-}
-template <int NV> __device__ __forceinline__ void ld_bits(const uint8_t* p, uint8_t* b) {
-    if (NV == 1) b[0] = p[0];
-    else { const uint16_t w = *reinterpret_cast<const uint16_t*>(p); b[0] = (uint8_t)(w & 255); b[1] = (uint8_t)(w >> 8); }
-}
-
 template <int MODE, bool BITS, bool NT, typename T>
 __global__ __launch_bounds__(256) void bn_apply_u16_kernel(const T* x, const float* scale, const float* shift, const T* x2,
                                                            const float* scale2, const float* shift2, T* y, int64_t nunits,

@@ -123,10 +123,16 @@ class ResidualUnitFunction(Function):
     ``drop``: stochastic depth -- the unit's device vector r of B floats (functions/drop_path.py: 0 for a sample whose main branch
     is dropped, 1 / (1 - p) for a kept one), or None: the junction becomes relu(r_b * bn_n(c_n) + shortcut), its backward hands
     r_b * g to bn_n and g to the shortcut.  Training only (a unit hands None otherwise: drop_path.unit_vector); everything but the
-    two junction calls is the same.  The rows kernels have the sign-bit form alone, so the bits are written with or without backprop."""
+    two junction calls is the same.  The rows kernels have the sign-bit form alone, so the bits are written with or without backprop.
+    ``se``: squeeze-and-excitation -- the unit's links.SqueezeExcite or None; the inputs then end with its W1, b1, W2, b2 and the
+    junction becomes relu(s[b,c] * bn_n(c_n) + shortcut) with s = sigmoid(W2 relu(W1 mean_p bn_n(c_n) + b1) + b2), in training
+    and in test mode.  Again only the two junction calls change (ops.se_excite / bn_apply_gate / bn_backward_gate).  Not
+    together with ``drop``."""
 
-    def __init__(self, stages, shortcut=None, drop=None):
-        self.stages, self.shortcut, self.drop = list(stages), shortcut, drop
+    def __init__(self, stages, shortcut=None, drop=None, se=None):
+        if se is not None and drop is not None:
+            raise ValueError('squeeze-and-excitation together with stochastic depth is not built: use --se-ratio or --drop-path')
+        self.stages, self.shortcut, self.drop, self.se = list(stages), shortcut, drop, se
 
     def forward(self, inputs):
         x = inputs[0]
@@ -161,14 +167,21 @@ class ResidualUnitFunction(Function):
                 h = self.h[i] = ops.bn_apply(self.c[i], self.st[i], relu=True)
         bits = config.train and config.enable_backprop     # the backward's ReLU mask as sign bits (ops.bn_apply)
         drop = self.drop             # (None outside training: drop_path.unit_vector)
+        if self.se is not None:         # the gate from the conv output's channel sums: bn_n's output is never made
+            W1, b1, W2, b2 = inputs[-4:]
+            self.gate = ops.se_excite(self.c[-1], self.st[-1], W1, b1, W2, b2)
         if self.shortcut is not None:
             W, g, b = inputs[1 + 3 * n:4 + 3 * n]
             if not paired:
                 self.cs, self.sts, self.geos = _ConvBN.forward(x, self.shortcut[0], self.shortcut[1], W, None, g, b)
-            if drop is not None:
+            if self.se is not None:
+                self.out = ops.bn_apply_gate(self.c[-1], self.st[-1], self.gate.s, x2=self.cs, st2=self.sts)
+            elif drop is not None:
                 self.out = ops.bn_apply_rows(self.c[-1], self.st[-1], drop, x2=self.cs, st2=self.sts)
             else:
                 self.out = ops.bn_apply(self.c[-1], self.st[-1], relu=True, x2=self.cs, st2=self.sts, want_bits=bits)
+        elif self.se is not None:
+            self.out = ops.bn_apply_gate(self.c[-1], self.st[-1], self.gate.s, residual=x)
         elif drop is not None:
             self.out = ops.bn_apply_rows(self.c[-1], self.st[-1], drop, residual=x)
         else:
@@ -201,7 +214,18 @@ class ResidualUnitFunction(Function):
         gout = gys[0].contiguous()
         Wl, gl, bl = P[1 + 3 * (n - 1):4 + 3 * (n - 1)]
         gcs = None
-        if self.drop is not None:
+        if self.se is not None:
+            W1, b1, W2, b2 = P[-4:]
+            sea = (W1.data, W2.data, W1.grad_view, b1.grad_view, W2.grad_view, b2.grad_view)
+            if self.shortcut is not None:
+                Ws, gs, bs = P[1 + 3 * n:4 + 3 * n]
+                g, gcs = ops.bn_backward_gate(gout, self.out, self.gate, self.c[-1], self.st[-1], gl.data, gl.grad_view,
+                                              bl.grad_view, *sea, x2=self.cs, st2=self.sts, gamma2=gs.data, ggamma2=gs.grad_view,
+                                              gbeta2=bs.grad_view)
+            else:
+                g = ops.bn_backward_gate(gout, self.out, self.gate, self.c[-1], self.st[-1], gl.data, gl.grad_view, bl.grad_view,
+                                         *sea)
+        elif self.drop is not None:
             if self.shortcut is not None:
                 Ws, gs, bs = P[1 + 3 * n:4 + 3 * n]
                 g, gcs = ops.bn_backward_rows(gout, self.out, self.drop, self.c[-1], self.st[-1], gl.data, gl.grad_view, bl.grad_view,
@@ -249,14 +273,16 @@ class ResidualUnitFunction(Function):
         return (gx,) + (None,) * (len(P) - 1)
 
     def release(self):
-        self.x = self.c = self.h = self.st = self.out = self.cs = None
+        self.x = self.c = self.h = self.st = self.out = self.cs = self.gate = None
 
 
-def residual_unit(x, stages, shortcut=None, drop=None):
+def residual_unit(x, stages, shortcut=None, drop=None, se=None):
     args = [x]
     for conv, bn in list(stages) + ([shortcut] if shortcut is not None else []):
         args += [conv.W, bn.gamma, bn.beta]
-    return ResidualUnitFunction(stages, shortcut, drop)(*args)
+    if se is not None:
+        args += [se.down.W, se.down.b, se.up.W, se.up.b]
+    return ResidualUnitFunction(stages, shortcut, drop, se)(*args)
 
 
 # --------------------------------------------------------------------------- #

@@ -17,7 +17,7 @@ from ..runtime.core import Chain
 
 
 class BottleneckA(Chain):
-    def __init__(self, in_channels, mid_channels, out_channels, stride=2, initialW=None):
+    def __init__(self, in_channels, mid_channels, out_channels, stride=2, initialW=None, se_ratio=None):
         super().__init__()
         with self.init_scope():
             self.conv1 = L.Convolution2D(in_channels, mid_channels, 1, stride, 0, initialW=initialW, nobias=True)
@@ -28,14 +28,15 @@ class BottleneckA(Chain):
             self.bn3 = L.BatchNormalization(out_channels)
             self.conv4 = L.Convolution2D(in_channels, out_channels, 1, stride, 0, initialW=initialW, nobias=True)
             self.bn4 = L.BatchNormalization(out_channels)
+            self.se = L.squeeze_excite(out_channels, se_ratio)
 
     def __call__(self, x):
         return blocks.residual_unit(x, [(self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)],
-                                    (self.conv4, self.bn4), drop=drop_path.unit_vector(self))
+                                    (self.conv4, self.bn4), drop=drop_path.unit_vector(self), se=self.se)
 
 
 class BottleneckB(Chain):
-    def __init__(self, in_channels, mid_channels, initialW=None):
+    def __init__(self, in_channels, mid_channels, initialW=None, se_ratio=None):
         super().__init__()
         with self.init_scope():
             self.conv1 = L.Convolution2D(in_channels, mid_channels, 1, 1, 0, initialW=initialW, nobias=True)
@@ -44,21 +45,22 @@ class BottleneckB(Chain):
             self.bn2 = L.BatchNormalization(mid_channels)
             self.conv3 = L.Convolution2D(mid_channels, in_channels, 1, 1, 0, initialW=initialW, nobias=True)
             self.bn3 = L.BatchNormalization(in_channels)
+            self.se = L.squeeze_excite(in_channels, se_ratio)
 
     def __call__(self, x):
         return blocks.residual_unit(x, [(self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)],
-                                    drop=drop_path.unit_vector(self))
+                                    drop=drop_path.unit_vector(self), se=self.se)
 
 
 class BuildingBlock(Chain):
-    def __init__(self, n_layer, in_channels, mid_channels, out_channels, stride, initialW=None):
+    def __init__(self, n_layer, in_channels, mid_channels, out_channels, stride, initialW=None, se_ratio=None):
         super().__init__()
         with self.init_scope():
-            self.a = BottleneckA(in_channels, mid_channels, out_channels, stride, initialW)
+            self.a = BottleneckA(in_channels, mid_channels, out_channels, stride, initialW, se_ratio)
             self._forward = ["a"]
             for i in range(n_layer - 1):
                 name = 'b{}'.format(i + 1)
-                setattr(self, name, BottleneckB(out_channels, mid_channels, initialW))
+                setattr(self, name, BottleneckB(out_channels, mid_channels, initialW, se_ratio))
                 self._forward.append(name)
 
     def __call__(self, x):
@@ -68,18 +70,19 @@ class BuildingBlock(Chain):
 
 
 class ResNet50Layers(Chain, drop_path.DropPathOwner):
-    def __init__(self, pretrained_model='auto'):
+    def __init__(self, pretrained_model='auto', se_ratio=None):
         super().__init__()
         w = L.HeNormal(scale=1.0)
         with self.init_scope():
             self.conv1 = L.Convolution2D(3, 64, 7, 2, 3, initialW=w, dense_rows=True)
             self.bn1 = L.BatchNormalization(64)
-            self.res2 = BuildingBlock(3, 64, 64, 256, 1, w)
-            self.res3 = BuildingBlock(4, 256, 128, 512, 2, w)
-            self.res4 = BuildingBlock(6, 512, 256, 1024, 2, w)
-            self.res5 = BuildingBlock(3, 1024, 512, 2048, 2, w)
+            self.res2 = BuildingBlock(3, 64, 64, 256, 1, w, se_ratio)
+            self.res3 = BuildingBlock(4, 256, 128, 512, 2, w, se_ratio)
+            self.res4 = BuildingBlock(6, 512, 256, 1024, 2, w, se_ratio)
+            self.res5 = BuildingBlock(3, 1024, 512, 2048, 2, w, se_ratio)
             self.fc6 = L.Linear(2048, 1000)
         self.pretrained_model = pretrained_model
+        self.se_ratio = se_ratio
 
     exchange_stages = ('res4', 'res5')        # see sheep/resnet.py
 

@@ -11,7 +11,7 @@ residual sums ride in the conv kernels' epilogues.
 import numpy as np
 
 from . import ops
-from .runtime.core import Link, Parameter
+from .runtime.core import Chain, Link, Parameter
 
 
 # ---- initialisers (chainer.initializers.HeNormal / Normal / LeCunNormal / Constant) ----
@@ -160,3 +160,25 @@ class Linear(Link):
             if self._arena is not None:
                 raise RuntimeError('Linear initialised after its model was finalised')
             self._initialize(in_size, nhwc_input)
+
+
+class SqueezeExcite(Chain):
+    """The excitation of a squeeze-and-excitation residual unit (Hu et al. 2018): ``down`` = Linear(channels, channels // ratio)
+    behind the squeeze, ``up`` = Linear(channels // ratio, channels) in front of the sigmoid -- snapshot keys ``se/down/W``,
+    ``se/down/b``, ``se/up/W``, ``se/up/b`` under the unit.  It only owns the parameters; the arithmetic is the unit's junction
+    (functions/blocks.py: ResidualUnitFunction(..., se=this link))."""
+
+    def __init__(self, channels, ratio):
+        super().__init__()
+        hidden = channels // ratio if ratio > 0 else 0
+        if ratio <= 0 or channels % ratio or hidden < 4 or hidden % 4:
+            raise ValueError('se_ratio %r leaves %d channels no hidden width that is a multiple of 4' % (ratio, channels))
+        self.channels, self.ratio, self.hidden = channels, ratio, hidden
+        with self.init_scope():
+            self.down = Linear(channels, hidden, initialW=HeNormal())
+            self.up = Linear(hidden, channels)
+
+
+def squeeze_excite(channels, ratio):
+    """the ``se`` child of a residual unit: None for ``ratio`` None / 0 (the unit then has today's parameters and launches)"""
+    return SqueezeExcite(channels, ratio) if ratio else None

@@ -2331,6 +2331,123 @@ def bn_backward_rows(gy, out, r, x, st, gamma, ggamma, gbeta, x2=None, st2=None,
     return (gx, gx2) if dual else gx
 
 
+class SEState:
+    """What the excitation of one residual unit leaves for its junction and its backward: the gate s [B][C], the hidden
+    activations h [B][C / R], the squeezed vector q [B][C] and the channel sums S [B][C] of the conv output (fp32 tables)."""
+    __slots__ = ('s', 'h', 'q', 'S')
+
+
+def _se_shape(x):
+    B, C_ = x.shape[0], x.shape[-1]
+    rps = x.numel() // (B * C_)
+    slabs = _lib.load().loans_se_slabs(B, rps, C_, x.element_size())
+    if slabs < 0:
+        check(slabs, 'loans_se_slabs')
+    return B, rps, C_, slabs
+
+
+def se_squeeze(x):
+    """S[b][c] = sum over the positions of sample b of the NHWC tensor x (fp32, whatever x's storage): one read of x, no atomics"""
+    B, rps, C_, slabs = _se_shape(x)
+    S = _empty((B, C_), device=x.device, dtype=torch.float32)
+    part = _empty((B, slabs, C_), device=x.device, dtype=torch.float32) if slabs > 1 else None
+    if CLASS_COUNT is not None: _acct('bn_fwd', 0, _nbytes(x), _nbytes(S))
+    lib = _lib.load()
+    fn = lib.loans_se_squeeze_bf16 if _is16(x) else lib.loans_se_squeeze_f32
+    check(fn(_ptr(x), _ptr(S), _ptr(part), B, rps, C_, _stream()), 'loans_se_squeeze')
+    return S
+
+
+def se_excite(x, st, W1, b1, W2, b2):
+    """The gate of a squeeze-and-excitation unit from the conv output x and its BN state: q = mean_p bn(x) (taken from the sums
+    of x: the BN output is never made), h = relu(W1 q + b1), s = sigmoid(W2 h + b2).  Returns an SEState."""
+    B, rps, C_, _ = _se_shape(x)
+    hid = W1.shape[0]
+    assert tuple(W1.shape) == (hid, C_) and tuple(W2.shape) == (C_, hid) and b1.numel() == hid and b2.numel() == C_
+    se = SEState()
+    se.S = se_squeeze(x)
+    se.s = _empty((B, C_), device=x.device, dtype=torch.float32)
+    se.h = _empty((B, hid), device=x.device, dtype=torch.float32)
+    se.q = _empty((B, C_), device=x.device, dtype=torch.float32)
+    if CLASS_COUNT is not None: _acct('bn_fwd', 4 * B * C_ * hid, _nbytes(se.S, W1, W2), _nbytes(se.s, se.h, se.q))
+    check(_lib.load().loans_se_excite_fwd_f32(_ptr(se.S), _ptr(st.scale), _ptr(st.shift), _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2),
+                                              _ptr(se.s), _ptr(se.h), _ptr(se.q), B, rps, C_, hid, _stream()),
+          'loans_se_excite_fwd_f32')
+    return se
+
+
+def bn_apply_gate(x, st, s, residual=None, x2=None, st2=None):
+    """bn_apply_rows with a gate per (sample, channel): y = relu(s[b][c] * bn(x) + residual | + bn2(x2)), ``s`` a [B][C] fp32
+    device table.  Always with the sign bits, hung on the result as ``y.relu_bits``."""
+    B, C_ = x.shape[0], x.shape[-1]
+    rps = x.numel() // (B * C_)
+    assert (residual is None) != (x2 is None) and s.dtype == torch.float32 and s.numel() == B * C_
+    mode, second = (1, residual) if residual is not None else (2, x2)
+    assert second.dtype == x.dtype and second.shape == x.shape
+    y = _empty_like(x)
+    bits = _empty(B * rps * (C_ // 4), device=x.device, dtype=torch.uint8)
+    if CLASS_COUNT is not None: _acct('bn_fwd', 0, _nbytes(x, second, s), _nbytes(y, bits))
+    lib = _lib.load()
+    fn = lib.loans_bn_apply_gate_bf16 if _is16(x) else lib.loans_bn_apply_gate_f32
+    check(fn(_ptr(x), _ptr(st.scale), _ptr(st.shift), _ptr(second), _ptr(st2.scale if st2 else None),
+             _ptr(st2.shift if st2 else None), _ptr(s), _ptr(y), _ptr(bits), B, rps, C_, mode, _stream()), 'loans_bn_apply_gate')
+    y.relu_bits = bits
+    return y
+
+
+def bn_backward_gate(gy, out, se, x, st, gamma, ggamma, gbeta, W1, W2, gW1, gb1, gW2, gb2,
+                     x2=None, st2=None, gamma2=None, ggamma2=None, gbeta2=None):
+    """bn_backward for the junction bn_apply_gate made, the gate's own backward included: g = gy * (out > 0) from
+    ``out.relu_bits``; the last BN (x, st) takes s[b][c] g + dq[b][c] / P, the shortcut BN (x2, st2) g.  Accumulates ggamma /
+    gbeta and the four excitation gradients in place, returns gx (and gx2).  One reduction pass to [B][C] tables -> the
+    per-sample excitation backward, which also folds the BN sums out of the tables -> the coefficient launch(es) of
+    bn_backward -> one apply pass."""
+    lib = _lib.load()
+    B, rps, C_, slabs = _se_shape(x)
+    hid = W1.shape[0]
+    rows = B * rps
+    dual = x2 is not None
+    s16 = _is16(x)
+    bits = out.relu_bits
+    dev = x.device
+    assert _is16(gy) == s16 and (x2 is None or _is16(x2) == s16) and bits.numel() == rows * (C_ // 4)
+    if CLASS_COUNT is not None: _acct('bn_bwd', 0, 2 * _nbytes(gy, x, x2, bits), _nbytes(x) * (2 if dual else 1))
+    s = _stream()
+    ns = 4 if dual else 2
+    nt = 3 if dual else 2
+    G = _empty((nt, B, C_), device=dev, dtype=torch.float32)
+    part = _empty((B, slabs, nt, C_), device=dev, dtype=torch.float64)
+    red = lib.loans_se_bwd_reduce_bf16 if s16 else lib.loans_se_bwd_reduce_f32
+    check(red(_ptr(gy), _ptr(bits), _ptr(x), _ptr(x2), _ptr(G[0]), _ptr(G[1]), _ptr(G[2]) if dual else 0, _ptr(part), B, rps, C_, s),
+          'loans_se_bwd_reduce')
+    sums = _zeros_f64((STATS_REPLICAS, ns, C_), dev)
+    t = _empty((B, C_), device=dev, dtype=torch.float32)
+    da2 = _empty((B, C_), device=dev, dtype=torch.float32)
+    dh = _empty((B, hid), device=dev, dtype=torch.float32)
+    u = _empty((B, 2, C_), device=dev, dtype=torch.float64)
+    check(lib.loans_se_excite_bwd_f32(_ptr(G[0]), _ptr(G[1]), _ptr(G[2]) if dual else 0, _ptr(se.S), _ptr(st.scale), _ptr(st.shift),
+                                      _ptr(st.mean), _ptr(st.rstd), _ptr(st2.mean if dual else None),
+                                      _ptr(st2.rstd if dual else None), _ptr(se.s), _ptr(se.h), _ptr(se.q), _ptr(W1), _ptr(W2),
+                                      _ptr(t), _ptr(da2), _ptr(dh), _ptr(u), _ptr(gW1), _ptr(gb1), _ptr(gW2), _ptr(gb2),
+                                      _ptr(sums), B, rps, C_, hid, s), 'loans_se_excite_bwd_f32')
+    k = _empty((6 if dual else 3, C_), device=dev, dtype=torch.float32)
+    check(lib.loans_bn_bwd_coeffs_rep_f32(_ptr(sums), STATS_REPLICAS, ns * C_, 0, C_, rows, _ptr(gamma), _ptr(st.mean),
+                                          _ptr(st.rstd), _ptr(ggamma), _ptr(gbeta), _ptr(k[0]), _ptr(k[1]), _ptr(k[2]), s),
+          'loans_bn_bwd_coeffs_rep_f32')
+    gx = _empty_like(x)
+    gx2 = None
+    if dual:
+        check(lib.loans_bn_bwd_coeffs_rep_f32(_ptr(sums[0, 2]), STATS_REPLICAS, ns * C_, 0, C_, rows, _ptr(gamma2), _ptr(st2.mean),
+                                              _ptr(st2.rstd), _ptr(ggamma2), _ptr(gbeta2), _ptr(k[3]), _ptr(k[4]), _ptr(k[5]), s),
+              'loans_bn_bwd_coeffs_rep_f32')
+        gx2 = _empty_like(x2)
+    app = lib.loans_bn_bwd_apply_gate_bf16 if s16 else lib.loans_bn_bwd_apply_gate_f32
+    check(app(_ptr(gy), _ptr(bits), _ptr(se.s), _ptr(t), _ptr(x), _ptr(k[0]), _ptr(k[1]), _ptr(k[2]), _ptr(gx), _ptr(x2),
+              _ptr(k[3]) if dual else 0, _ptr(k[4]) if dual else 0, _ptr(k[5]) if dual else 0, _ptr(gx2), B, rps, C_, s),
+          'loans_bn_bwd_apply_gate')
+    return (gx, gx2) if dual else gx
+
+
 def bn_backward_from_sums(gy, x, st, sums, gamma, ggamma, gbeta):
     """bn_backward(gy, relu(bn(x)), x, st, ..., mask_is_own_relu=True) with the reduction already done: `sums` are the
     [replicas][2][C] accumulators conv_dgrad(..., bn_sums=(x, st)) filled while gy was in registers.  One pass over the

@@ -16,7 +16,7 @@ from ..runtime.core import Chain, ChainList
 
 class ResNet(Chain, drop_path.DropPathOwner):
 
-    def __init__(self, n_layers, class_labels=None):
+    def __init__(self, n_layers, class_labels=None, se_ratio=None):
         super(ResNet, self).__init__()
         w = L.HeNormal()
         if n_layers == 18:
@@ -30,18 +30,19 @@ class ResNet(Chain, drop_path.DropPathOwner):
         with self.init_scope():
             self.conv1 = L.Convolution2D(3, 64, 7, 2, 3, initialW=w, dense_rows=True)
             self.bn1 = L.BatchNormalization(64)
-            self.res2 = BasicBlock(block[0], 64, 1, in_ch=64)
-            self.res3 = BasicBlock(block[1], 128, in_ch=64)
-            self.res4 = BasicBlock(block[2], 256, in_ch=128)
-            self.res5 = BasicBlock(block[3], 512, in_ch=256)
+            self.res2 = BasicBlock(block[0], 64, 1, in_ch=64, se_ratio=se_ratio)
+            self.res3 = BasicBlock(block[1], 128, in_ch=64, se_ratio=se_ratio)
+            self.res4 = BasicBlock(block[2], 256, in_ch=128, se_ratio=se_ratio)
+            self.res5 = BasicBlock(block[3], 512, in_ch=256, se_ratio=se_ratio)
             if n_layers == 20:
-                self.res6 = BasicBlock(block[4], 512, in_ch=512)
-                self.res7 = BasicBlock(block[5], 512, in_ch=512)
+                self.res6 = BasicBlock(block[4], 512, in_ch=512, se_ratio=se_ratio)
+                self.res7 = BasicBlock(block[5], 512, in_ch=512, se_ratio=se_ratio)
             if class_labels is not None:
                 self.fc = L.Linear(None, class_labels)      # Chainer's default initialiser: LeCunNormal, zero bias
 
         self.n_layers = n_layers
         self.class_labels = class_labels
+        self.se_ratio = se_ratio
 
     # data parallel: the gradient arena is exchanged in three parts, cut in front of these stages -- everything from res5 up
     # (res5 + the head + res6 / res7: 75 % of the bytes at 224 px) as soon as the backward has left res5, res4 (19 %) next,
@@ -81,12 +82,12 @@ class ResNet(Chain, drop_path.DropPathOwner):
 
 class BasicBlock(ChainList):
 
-    def __init__(self, layer, ch, stride=2, in_ch=None):
+    def __init__(self, layer, ch, stride=2, in_ch=None, se_ratio=None):
         super(BasicBlock, self).__init__()
         in_ch = ch if in_ch is None else in_ch      # the reference infers it lazily (Convolution2D(None, ...))
-        self.add_link(BasicA(ch, stride, in_ch))
+        self.add_link(BasicA(ch, stride, in_ch, se_ratio))
         for i in range(layer - 1):
-            self.add_link(BasicB(ch))
+            self.add_link(BasicB(ch, se_ratio))
 
     def __call__(self, x):
         for f in self.children():
@@ -96,7 +97,7 @@ class BasicBlock(ChainList):
 
 class BasicA(Chain):
 
-    def __init__(self, ch, stride, in_ch=None):
+    def __init__(self, ch, stride, in_ch=None, se_ratio=None):
         super(BasicA, self).__init__()
         w = L.HeNormal()
         in_ch = ch if in_ch is None else in_ch
@@ -108,15 +109,16 @@ class BasicA(Chain):
 
             self.conv3 = L.Convolution2D(in_ch, ch, 3, stride, 1, initialW=w, nobias=True)
             self.bn3 = L.BatchNormalization(ch)
+            self.se = L.squeeze_excite(ch, se_ratio)        # (None: no child, no parameters -- the reference's unit)
 
     def __call__(self, x):
         return blocks.residual_unit(x, [(self.conv1, self.bn1), (self.conv2, self.bn2)], (self.conv3, self.bn3),
-                                    drop=drop_path.unit_vector(self))
+                                    drop=drop_path.unit_vector(self), se=self.se)
 
 
 class BasicB(Chain):
 
-    def __init__(self, ch):
+    def __init__(self, ch, se_ratio=None):
         super(BasicB, self).__init__()
         w = L.HeNormal()
         with self.init_scope():
@@ -124,6 +126,8 @@ class BasicB(Chain):
             self.bn1 = L.BatchNormalization(ch)
             self.conv2 = L.Convolution2D(ch, ch, 3, 1, 1, initialW=w, nobias=True)
             self.bn2 = L.BatchNormalization(ch)
+            self.se = L.squeeze_excite(ch, se_ratio)
 
     def __call__(self, x):
-        return blocks.residual_unit(x, [(self.conv1, self.bn1), (self.conv2, self.bn2)], drop=drop_path.unit_vector(self))
+        return blocks.residual_unit(x, [(self.conv1, self.bn1), (self.conv2, self.bn2)], drop=drop_path.unit_vector(self),
+                                    se=self.se)

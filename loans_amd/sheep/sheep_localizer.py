@@ -34,13 +34,14 @@ def _as_device_batch(images, device):
 
 class SheepLocalizer(Chain, DropPathOwner):
 
-    def __init__(self, out_size, transform_rois_to_grayscale=False, train_imagenet=False):
+    def __init__(self, out_size, transform_rois_to_grayscale=False, train_imagenet=False, se_ratio=None):
         super().__init__()
         with self.init_scope():
-            self.feature_extractor = ResNet(18, class_labels=1000 if train_imagenet else None)
+            # se_ratio: squeeze-and-excitation in every residual unit (links.SqueezeExcite); None / 0 builds the reference's model
+            self.feature_extractor = ResNet(18, class_labels=1000 if train_imagenet else None, se_ratio=se_ratio)
             if not train_imagenet:
-                self.res6 = BasicBlock(2, 512, in_ch=512)
-                self.res7 = BasicBlock(2, 512, in_ch=512)
+                self.res6 = BasicBlock(2, 512, in_ch=512, se_ratio=se_ratio)
+                self.res7 = BasicBlock(2, 512, in_ch=512, se_ratio=se_ratio)
                 self.param_predictor = L.Linear(512, 6)
 
                 transform_bias = self.param_predictor.b.host
@@ -54,6 +55,7 @@ class SheepLocalizer(Chain, DropPathOwner):
         self.out_size = tuple(out_size)
         self.transform_rois_to_grayscale = transform_rois_to_grayscale
         self.train_imagenet = train_imagenet
+        self.se_ratio = se_ratio
 
     def drop_path_stages(self):
         """the backbone's stages, then res6 / res7 where the localizer has them (``set_drop_path`` counts the units of all of
@@ -158,17 +160,17 @@ class Resnet50SheepLocalizer(SheepLocalizer):
     (taps ``res5`` / ``pool5``), chainercv ``ResBlock`` stages res6 / res7 on frames taller than 224 / 300 px,
     ``Linear(2048, 6)``, the same STN tail."""
 
-    def __init__(self, out_size, transform_rois_to_grayscale=False, train_imagenet=False):
+    def __init__(self, out_size, transform_rois_to_grayscale=False, train_imagenet=False, se_ratio=None):
         super(SheepLocalizer, self).__init__()
         initialW = L.HeNormal(scale=1., fan_option='fan_out')
         keys_to_remove = ['fc6', 'prob'] if not train_imagenet else ['prob']
         with self.init_scope():
-            self.feature_extractor = MyResNet50Layers(keys_to_remove=keys_to_remove, pretrained_model='auto')
+            self.feature_extractor = MyResNet50Layers(keys_to_remove=keys_to_remove, pretrained_model='auto', se_ratio=se_ratio)
             if not train_imagenet:
                 self.param_predictor = L.Linear(2048, 6)
 
-                self.res6 = ResBlock(2, 2048, 1024, 2048, 2, initialW=initialW)
-                self.res7 = ResBlock(2, 2048, 1024, 2048, 2, initialW=initialW)
+                self.res6 = ResBlock(2, 2048, 1024, 2048, 2, initialW=initialW, se_ratio=se_ratio)
+                self.res7 = ResBlock(2, 2048, 1024, 2048, 2, initialW=initialW, se_ratio=se_ratio)
 
                 transform_bias = self.param_predictor.b.host
                 transform_bias[[0, 4]] = 0.8
@@ -180,6 +182,7 @@ class Resnet50SheepLocalizer(SheepLocalizer):
         self.out_size = tuple(out_size)
         self.transform_rois_to_grayscale = transform_rois_to_grayscale
         self.train_imagenet = train_imagenet
+        self.se_ratio = se_ratio
 
     def __call__(self, images):
         self.visual_backprop_anchors.clear()

@@ -6,6 +6,7 @@ say what the head costs: the flop counts of the three head GEMMs against the bac
     python tools/imagenet_step.py -b 256 --resnet-50 --loss bce --bce-target-thresh 0.2
         (the ResNet-50 localizer, the sigmoid binary cross-entropy on the label-smoothed target: tools/bce_bench.py)
     python tools/imagenet_step.py -b 256 --resnet-50 --drop-path 0.05     (stochastic depth: tools/droppath_bench.py)
+    python tools/imagenet_step.py -b 256 --resnet-50 --se-ratio 16        (squeeze-and-excitation: tools/se_bench.py)
     python tools/imagenet_step.py -b 256 --teacher-arch resnet50           (a ResNet-18 student under a frozen ResNet-50 teacher)
     python tools/imagenet_step.py -b 256 --resnet-50 --forward-only        (the test-mode forward alone: what a teacher costs;
         tools/distill_bench.py)
@@ -39,6 +40,7 @@ def main(argv=None):
     ap.add_argument('--bce-target-thresh', type=float, default=None)
     ap.add_argument('--label-smoothing', type=float, default=0.0)
     ap.add_argument('--drop-path', type=float, default=0.0, help='stochastic depth at this rate (tools/droppath_bench.py)')
+    ap.add_argument('--se-ratio', type=int, default=0, help='squeeze-and-excitation at this reduction ratio (tools/se_bench.py)')
     ap.add_argument('--teacher-arch', default=None, choices=['resnet18', 'resnet50'], help='distil from a frozen teacher of this architecture (random weights: the time does not depend on them)')
     ap.add_argument('--teacher-dtype', default=None, choices=['f32', 'bf16'], help='the teacher\'s arithmetic (default: --dtype)')
     ap.add_argument('--distill-alpha', type=float, default=0.5)
@@ -57,7 +59,7 @@ def main(argv=None):
         want = a.teacher_dtype or a.dtype
         teacher.set_precision(want, want)
         options.update(teacher=teacher, distill_alpha=a.distill_alpha, distill_temperature=a.distill_temperature)
-    model = loans_amd.Classifier(localizer((75, 75), train_imagenet=True), label_smoothing=a.label_smoothing, **options)
+    model = loans_amd.Classifier(localizer((75, 75), train_imagenet=True, **({'se_ratio': a.se_ratio} if a.se_ratio else {})), label_smoothing=a.label_smoothing, **options)
     if a.drop_path > 0:
         model.predictor.set_drop_path(a.drop_path, seed=0)
     if a.dtype == 'bf16':

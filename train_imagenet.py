@@ -185,6 +185,13 @@ checkpoint lies between steps and holds nothing of the accumulator.  Not built: 
     python train_imagenet.py train.tsv val.tsv -b 512 --accum-steps 8 --dtype bf16 --optimizer lars --lr 10 --weight-decay 5e-5 \
         --no-decay-1d --lr-schedule cosine --warmup-epochs 5 --num-epoch 90 --label-smoothing 0.1 --augment rrc
 
+``--se-ratio R`` (default 0: off; SENet's value is 16) builds the backbone with squeeze-and-excitation in every residual unit
+(Hu et al. 2018): the residual branch is scaled per sample and channel by ``sigmoid(W2 relu(W1 q + b1) + b2)``, ``q`` the spatial
+mean of the unit's last BN output, ``W1`` of shape (C / R, C) -- loans_amd/links.py: SqueezeExcite, csrc/se.hip.  The option is
+logged in the first entry where given and fixed on ``--resume``; ``train_sheep_localizer.py --se-ratio R`` loads the snapshot with
+``--rl``.  ``--teacher`` models are built without it unless ``--teacher-se-ratio R`` says otherwise.  Not together with
+``--drop-path``.
+
 ``--teacher PATH`` is knowledge distillation: the model is trained against the logits of a frozen, larger one as well as against
 the labels (Hinton et al. 2015), ``loss = (1 - A) CE + A T^2 KL(softmax(teacher / T) || softmax(student / T))`` -- torch's
 ``kl_div(log_softmax(z / T), softmax(zt / T), reduction='batchmean') * T * T`` beside the cross-entropy.  ``PATH`` is a snapshot
@@ -264,7 +271,7 @@ RESUME_FIXED = ('use_resnet_18', 'dtype', 'optimizer', 'batch_size', 'gpus', 'im
                 'validation_size', 'synthetic_classes', 'data_seed', 'no_shuffle', 'augment', 'rrc_scale', 'rrc_ratio', 'val_crop_pct',
                 'augment_seed', 'seed', 'mixup_alpha', 'cutmix_alpha', 'mix_prob', 'mix_switch_prob', 'mix_seed', 'ema_decay',
                 'color_jitter', 'lighting_std', 'random_erase_prob', 'random_erase_scale', 'random_erase_ratio', 'random_erase_value',
-                'photo_seed', 'rand_augment', 'trivial_augment', 'ra_fill', 'ra_seed', 'drop_path', 'drop_path_seed', 'accum_steps')
+                'photo_seed', 'rand_augment', 'trivial_augment', 'ra_fill', 'ra_seed', 'drop_path', 'drop_path_seed', 'accum_steps', 'se_ratio')
 
 
 class SyntheticClasses:
@@ -386,6 +393,12 @@ class Arguments(argparse.Namespace):
     distill_temperature = 1.0
     _DISTILL = ('teacher', 'teacher_arch', 'teacher_dtype', 'distill_alpha', 'distill_temperature')
 
+    # --se-ratio: squeeze-and-excitation in every residual unit (loans_amd/links.py: SqueezeExcite, csrc/se.hip); 0: the model
+    # without, logged only where given.  teacher_se_ratio: the same for the model of --teacher
+    se_ratio = 0
+    teacher_se_ratio = 0
+    _SE = ('se_ratio', 'teacher_se_ratio')
+
 
 def parse_args(argv=None):
     parser = argparse.ArgumentParser(description="ImageNet pre-training of a localizer backbone (MI355X-native)")
@@ -477,6 +490,8 @@ def parse_args(argv=None):
     # gradient accumulation
     parser.add_argument("--accum-steps", type=int, default=argparse.SUPPRESS, metavar='K', help="gradient accumulation: sum the gradients of K micro-batches of -b frames per GPU and step once on their mean; iterations, intervals, --lr and the warm-up count optimiser steps (default 1: off)")
     # knowledge distillation
+    parser.add_argument("--se-ratio", type=int, default=argparse.SUPPRESS, metavar='R', help="squeeze-and-excitation in every residual unit of the backbone, with C / R hidden units at C channels (SENet: 16; default 0: off)")
+    parser.add_argument("--teacher-se-ratio", type=int, default=argparse.SUPPRESS, metavar='R', help="with --teacher: the --se-ratio the teacher's snapshot was trained with (default 0)")
     parser.add_argument("--teacher", default=argparse.SUPPRESS, metavar='PATH', help="distil from this frozen snapshot (a <Localizer>_<it>.npz or _ema_ file as this script writes it): loss = (1 - A) CE + A T^2 KL(teacher || student); every rank loads it itself (default: off)")
     parser.add_argument("--teacher-arch", default=argparse.SUPPRESS, choices=['resnet18', 'resnet50'], help="with --teacher: the localizer the snapshot was written by (default resnet50)")
     parser.add_argument("--teacher-dtype", default=argparse.SUPPRESS, choices=['fp32', 'f32', 'bf16'], help="with --teacher: the arithmetic of the teacher's forward (default: the run's --dtype)")
@@ -497,10 +512,11 @@ def parse_args(argv=None):
         check_drop_arguments(args)
         check_accum_arguments(args)
         check_distill_arguments(args)
+        check_se_arguments(args)
         if args.resume is not None:
             check_average_resume(args)
             world = os.environ.get('WORLD_SIZE')        # a rank under a launcher: the group's size, whatever --gpus says
-            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS_WITH_ACCUM)
+            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS_WITH_SE)
     except ValueError as e:
         parser.error(str(e))
     return args
@@ -630,6 +646,19 @@ def check_drop_arguments(args):
         raise ValueError('--drop-path is the largest drop probability of a residual unit: it must lie in [0, 1), got %r' % args.drop_path)
 
 
+def check_se_arguments(args):
+    """ValueError for an --se-ratio that is no reduction ratio, for one together with --drop-path (not built), and for
+    --teacher-se-ratio without --teacher"""
+    for name in ('se_ratio', 'teacher_se_ratio'):
+        r = getattr(args, name)
+        if isinstance(r, bool) or not isinstance(r, int) or r < 0:
+            raise ValueError('--%s is the reduction ratio of the excitation: an integer >= 1, or 0 for none, got %r' % (name.replace('_', '-'), r))
+    if args.se_ratio and args.drop_path > 0:
+        raise ValueError('--se-ratio with --drop-path is not built: the gated junction takes no per-sample keep factor')
+    if args.teacher_se_ratio and args.teacher is None:
+        raise ValueError('--teacher-se-ratio belongs to --teacher: give the snapshot to distil from')
+
+
 def check_accum_arguments(args):
     """ValueError for an --accum-steps that is no number of micro-batches"""
     k = args.accum_steps
@@ -675,7 +704,7 @@ def build_teacher(args):
     localizer_class = loans_amd.SheepLocalizer if args.teacher_arch == 'resnet18' else loans_amd.Resnet50SheepLocalizer
     state = np.random.get_state()           # the initialisers' draws are overwritten: the student's --seed stream stays as it was
     try:
-        teacher = localizer_class((75, 75), train_imagenet=True)
+        teacher = localizer_class((75, 75), train_imagenet=True, se_ratio=args.teacher_se_ratio or None)
         loans_amd.Classifier(teacher).materialize()
     finally:
         np.random.set_state(state)
@@ -723,9 +752,11 @@ RESUME_DEFAULTS_WITH_RA = dict(RESUME_DEFAULTS_WITH_LOSS, **RESUME_DEFAULTS_RA)
 # ... and for --drop-path / --drop-path-seed
 RESUME_DEFAULTS_DROP = {name: getattr(Arguments, name) for name in Arguments._DROP}
 RESUME_DEFAULTS_WITH_DROP = dict(RESUME_DEFAULTS_WITH_RA, **RESUME_DEFAULTS_DROP)
-# ... and for --accum-steps (a checkpoint from before the option ran at 1); this is the table --resume uses
+# ... and for --accum-steps (a checkpoint from before the option ran at 1)
 RESUME_DEFAULTS_ACCUM = {name: getattr(Arguments, name) for name in Arguments._ACCUM}
 RESUME_DEFAULTS_WITH_ACCUM = dict(RESUME_DEFAULTS_WITH_DROP, **RESUME_DEFAULTS_ACCUM)
+# ... and for --se-ratio (a checkpoint from before the option holds the model without); this is the table --resume uses
+RESUME_DEFAULTS_WITH_SE = dict(RESUME_DEFAULTS_WITH_ACCUM, se_ratio=Arguments.se_ratio)
 
 
 def cache_budgets(total_bytes, n_train, n_validation):
@@ -783,7 +814,7 @@ def build_model(args):
         teacher = build_teacher(args)
         teacher.set_precision(*(('bf16', 'bf16') if teacher_dtype == 'bf16' else ('f32', 'f32')))
         distill = dict(teacher=teacher, distill_alpha=alpha, distill_temperature=temperature)
-    model = loans_amd.Classifier(localizer_class((75, 75), train_imagenet=True), label_smoothing=args.label_smoothing,
+    model = loans_amd.Classifier(localizer_class((75, 75), train_imagenet=True, se_ratio=args.se_ratio or None), label_smoothing=args.label_smoothing,
                                  topk=resolved_topk(args), **loss_options(args), **distill)
     model.materialize()         # the ResNet-18 variant's lazily sized fc
     return model
@@ -876,6 +907,7 @@ def run(args, log=print):
     check_drop_arguments(args)
     check_accum_arguments(args)
     check_distill_arguments(args)
+    check_se_arguments(args)
     if args.teacher is not None:                # the values this run distils with, logged in the first entry
         args.distill_alpha, args.distill_temperature, args.teacher_dtype = distill_options(args)
         args.teacher_arch = args.teacher_arch
@@ -1017,7 +1049,7 @@ def run(args, log=print):
         # the run continues in the checkpoint's log directory: no new <time>_<name>
         check_average_resume(args)
         resumed, changed = checkpoint.resolve_resume(args, RESUME_FIXED, log if chief else (lambda line: None), world=comm.size,
-                                                     defaults=RESUME_DEFAULTS_WITH_ACCUM)
+                                                     defaults=RESUME_DEFAULTS_WITH_SE)
         args.log_dir = os.path.dirname(os.path.abspath(args.resume))
         for line in changed if chief else ():
             log(line)
@@ -1051,6 +1083,8 @@ def run(args, log=print):
             continue        # logged where one of them is given
         if argument in Arguments._DISTILL and args.teacher is None:
             continue        # logged with a teacher only
+        if argument in Arguments._SE and argument not in vars(args):
+            continue        # logged where it is given
         # (an entry's ``loss`` is the training loss: the option of that name is logged as ``loss_function``)
         data_to_log['loss_function' if argument == 'loss' else argument] = getattr(args, argument)
     log_entries = []
