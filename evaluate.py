@@ -59,7 +59,8 @@ class Evaluator:
     def __init__(self, args):
         self.args = args
         cls = loans_amd.SheepLocalizer if args.use_resnet_18 else loans_amd.Resnet50SheepLocalizer
-        self.localizer = cls(tuple(args.target_size), se_ratio=getattr(args, 'se_ratio', 0) or None)
+        self.localizer = cls(tuple(args.target_size), se_ratio=getattr(args, 'se_ratio', 0) or None,
+                             blur_pool=getattr(args, 'blur_pool', False))
         self.results_path = os.path.join(args.model_dir, 'eval_results.json')
         if args.synthetic:
             self.dataset = SyntheticLabeled(args.synthetic, tuple(args.image_size))
@@ -129,6 +130,7 @@ def main(argv=None):
     parser.add_argument("--target-size", type=int, nargs=2, default=(75, 75))
     parser.add_argument("--use-resnet-18", action='store_true', default=False)
     parser.add_argument("--se-ratio", type=int, default=0, metavar='R', help="the --se-ratio the snapshots were trained with (default 0: none)")
+    parser.add_argument("--blur-pool", action='store_true', default=False, help="the snapshots were trained with --blur-pool (default: off)")
     parser.add_argument("--force-reset", action='store_true', default=False)
     args = parser.parse_args(argv)
     if not args.synthetic and not args.eval_gt:

@@ -1078,6 +1078,30 @@ int loans_bn_bwd_apply_gate_bf16(const void* gy, const uint8_t* signbits, const 
                                  const float* k2b, const float* k3b, void* gx2, int32_t B, int64_t rows_per_sample, int32_t C,
                                  void* stream);
 
+/* ---- anti-aliased downsampling behind a strided stage of a residual unit (csrc/blur.hip; Zhang 2019).  NHWC tensors; H, W are
+ *      ALWAYS the full resolution (>= 2), the quarter-resolution maps have ceil(H / 2) x ceil(W / 2) positions:
+ *      blur(a)[b,i,j,c] = 1/16 sum_{di,dj in 0..2} w[di] w[dj] a[b, refl(2i + di - 1), refl(2j + dj - 1), c], w = (1, 2, 1),
+ *      refl(-1) = 1, refl(H) = H - 2.  The storage types come as element sizes (4: fp32, 2: bf16), both tensors of a call alike.
+ *      loans_blur_fwd: y = blur(relu(scale x + shift)); scale = shift = NULL: y = blur(x).
+ *      loans_blur_bwd_records: the per-block records of the reduction for this shape, or an error.
+ *      loans_blur_bwd_reduce: with gz = blurT(gy) (scale x + shift > 0), replica 0 of sums (fp64 [replicas][2][C], the other
+ *      replicas stay as the caller zeroed them) = [sum gz | sum gz (x - mean)] for loans_bn_bwd_coeffs_rep_f32 (centred = 1).
+ *      partial: records * 2 * C doubles.
+ *      loans_blur_bwd_apply: gx = k1 gz + k2 x + k3 with the same gz, k = [k1 | k2 | k3][C] as one table.
+ *      loans_blur_bwd_plain: gx = blurT(gy), with addend (may be gx itself): gx = addend + blurT(gy).
+ *      LOANS_EINVAL for null or misaligned pointers, H or W < 2, a channel count that is no multiple of 64 or above 2048, element
+ *      sizes other than 4 / 2 or unequal; LOANS_ERANGE for B > 65535 or H, W > 32768.  No floating-point atomics: two runs give
+ *      the same bits.  Nothing waits for the host. ---- */
+int loans_blur_fwd(const void* x, const float* scale, const float* shift, void* y, int32_t B, int32_t H, int32_t W, int32_t C,
+                   int32_t x_bytes, int32_t y_bytes, void* stream);
+int loans_blur_bwd_records(int32_t B, int32_t H, int32_t W);
+int loans_blur_bwd_reduce(const void* gy, const void* x, const float* scale, const float* shift, const float* mean, double* partial,
+                          double* sums, int32_t B, int32_t H, int32_t W, int32_t C, int32_t gy_bytes, int32_t x_bytes, void* stream);
+int loans_blur_bwd_apply(const void* gy, const void* x, const float* scale, const float* shift, const float* k, void* gx, int32_t B,
+                         int32_t H, int32_t W, int32_t C, int32_t gy_bytes, int32_t x_bytes, void* stream);
+int loans_blur_bwd_plain(const void* gy, const void* addend, void* gx, int32_t B, int32_t H, int32_t W, int32_t C, int32_t gy_bytes,
+                         int32_t gx_bytes, void* stream);
+
 /* library / build identification */
 const char* loans_hip_version(void);
 

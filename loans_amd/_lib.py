@@ -220,12 +220,18 @@ SIGNATURES = {
     'loans_se_excite_bwd_f32': [_p] * 24 + [_i32, _i64, _i32, _i32, _p],
     'loans_bn_bwd_apply_gate_f32': [_p] * 14 + [_i32, _i64, _i32, _p],
     'loans_bn_bwd_apply_gate_bf16': [_p] * 14 + [_i32, _i64, _i32, _p],
+    'loans_blur_fwd': [_p] * 4 + [_i32] * 6 + [_p],
+    'loans_blur_bwd_records': [_i32, _i32, _i32],
+    'loans_blur_bwd_reduce': [_p] * 7 + [_i32] * 6 + [_p],
+    'loans_blur_bwd_apply': [_p] * 6 + [_i32] * 6 + [_p],
+    'loans_blur_bwd_plain': [_p] * 3 + [_i32] * 6 + [_p],
 }
 
 # every entry point returns int (0 / LOANS_E* / hipError_t) except:
 RESTYPES = {'loans_wgrad_bf16s_ws_floats': C.c_int64, 'loans_crop_band_rows': C.c_int, 'loans_momentum_sgd_max_segments': C.c_int,
             'loans_lars_workspace_bytes': C.c_int64, 'loans_photo_workspace_bytes': C.c_int64,
-            'loans_grad_clip_workspace_bytes': C.c_int64, 'loans_ra_workspace_bytes': C.c_int64, 'loans_se_slabs': C.c_int}    # (sizes / counts, not a status)
+            'loans_grad_clip_workspace_bytes': C.c_int64, 'loans_ra_workspace_bytes': C.c_int64, 'loans_se_slabs': C.c_int,
+            'loans_blur_bwd_records': C.c_int}    # (sizes / counts, not a status)
 
 _lib = None
 

@@ -17,7 +17,7 @@ class Conv2DBNActiv(Chain):
 
 class Bottleneck(Chain):
     def __init__(self, in_channels, mid_channels, out_channels, stride=1, initialW=None, residual_conv=False,
-                 stride_first=False, se_ratio=None):
+                 stride_first=False, se_ratio=None, blur_pool=False):
         super().__init__()
         s1, s3 = (stride, 1) if stride_first else (1, stride)
         with self.init_scope():
@@ -28,22 +28,23 @@ class Bottleneck(Chain):
                 self.residual_conv = Conv2DBNActiv(in_channels, out_channels, 1, stride, 0, initialW=initialW)
             self.se = L.squeeze_excite(out_channels, se_ratio)
         self.has_residual_conv = residual_conv
+        self.blur_pool = bool(blur_pool)
 
     def __call__(self, x):
         stages = [(c.conv, c.bn) for c in (self.conv1, self.conv2, self.conv3)]
         sc = (self.residual_conv.conv, self.residual_conv.bn) if self.has_residual_conv else None
-        return blocks.residual_unit(x, stages, sc, drop=drop_path.unit_vector(self), se=self.se)
+        return blocks.residual_unit(x, stages, sc, drop=drop_path.unit_vector(self), se=self.se, blur=self.blur_pool)
 
 
 class ResBlock(Chain):
     def __init__(self, n_layer, in_channels, mid_channels, out_channels, stride, initialW=None, stride_first=False,
-                 se_ratio=None):
+                 se_ratio=None, blur_pool=False):
         super().__init__()
         if in_channels is None:
             raise ValueError('pass in_channels explicitly (the reference relies on lazy initialisation)')
         with self.init_scope():
             self.a = Bottleneck(in_channels, mid_channels, out_channels, stride, initialW, residual_conv=True,
-                                stride_first=stride_first, se_ratio=se_ratio)
+                                stride_first=stride_first, se_ratio=se_ratio, blur_pool=blur_pool)
             self._forward = ['a']
             for i in range(n_layer - 1):
                 name = 'b{}'.format(i + 1)

@@ -28,7 +28,7 @@ class _ConvBN:
     """conv -> BN statistics (train) or running-stat coefficients (test)."""
 
     @staticmethod
-    def forward(x, conv, bn, W, b, gamma, beta):
+    def forward(x, conv, bn, W, b, gamma, beta, stride=None):
         # the stem (fp32 frames) is where the bf16 region of ops.STORAGE == 'bf16' begins: its conv writes bf16
         o16 = ops.STORAGE == 'bf16' and x.dtype == torch.float32
         B, H, Wd, _ = x.shape
@@ -36,7 +36,7 @@ class _ConvBN:
             if not hasattr(x, 'frame_hw'):
                 raise ValueError('a dense-row stem takes the padded frame buffer of ops.prep_images(images, geometry)')
             H, Wd = x.frame_hw
-        geo = conv.geometry(B, H, Wd)
+        geo = conv.geometry(B, H, Wd, stride)       # (stride: a blurred unit's strided convolutions run at stride 1)
         if config.train:
             stats = _zeros_stats(conv.out_channels, x.device)
             c = ops.conv_fprop(x, W, geo, bias=b, stats=stats, out_bf16=o16)
@@ -127,12 +127,25 @@ class ResidualUnitFunction(Function):
     ``se``: squeeze-and-excitation -- the unit's links.SqueezeExcite or None; the inputs then end with its W1, b1, W2, b2 and the
     junction becomes relu(s[b,c] * bn_n(c_n) + shortcut) with s = sigmoid(W2 relu(W1 mean_p bn_n(c_n) + b1) + b2), in training
     and in test mode.  Again only the two junction calls change (ops.se_excite / bn_apply_gate / bn_backward_gate).  Not
-    together with ``drop``."""
+    together with ``drop``.
+    ``blur``: anti-aliased downsampling (Zhang 2019; csrc/blur.hip) -- every convolution of the unit with stride 2 runs at stride 1
+    with its kernel and padding; a strided stage i hands blur(relu(bn_i(c_i))) on (ops.blur_pool in place of bn_apply, its BN's
+    statistics over the full-resolution map; ops.blur_pool_bn_backward in place of the bn_backward* call), a strided shortcut
+    convolution reads blur(x).  The junction, every other stage and every unit without a stride run the launches they always
+    ran; the fast paths that assume the next stage reads the BN's own output (BN on load, the BN sums in the data gradient's
+    epilogue) and the conv1 / shortcut pair launch are skipped at exactly those places.  Composes with ``drop`` and ``se``."""
 
-    def __init__(self, stages, shortcut=None, drop=None, se=None):
+    def __init__(self, stages, shortcut=None, drop=None, se=None, blur=False):
         if se is not None and drop is not None:
             raise ValueError('squeeze-and-excitation together with stochastic depth is not built: use --se-ratio or --drop-path')
         self.stages, self.shortcut, self.drop, self.se = list(stages), shortcut, drop, se
+        # which stages / whether the shortcut are downsampled by the blur instead of by their convolution's stride
+        self.blurred = [bool(blur) and conv.stride != 1 for conv, _ in self.stages]
+        self.blur_shortcut = bool(blur) and shortcut is not None and shortcut[0].stride != 1
+        if blur and any(conv.stride not in (1, 2) for conv, _ in self.stages + ([shortcut] if shortcut is not None else [])):
+            raise ValueError('blur-pool downsamples by two: a unit with another stride is not built')
+        if self.blurred and self.blurred[-1]:
+            raise ValueError('blur-pool behind the last stage of a residual unit is not built: its BN output meets the shortcut')
 
     def forward(self, inputs):
         x = inputs[0]
@@ -140,7 +153,10 @@ class ResidualUnitFunction(Function):
         self.x = x
         self.c, self.st, self.geo, self.h = [None] * n, [None] * n, [None] * n, [None] * n
         h = x
-        paired = self._forward_pair(x, inputs) if self.shortcut is not None else False
+        blur = self.blur_shortcut or any(self.blurred)
+        if blur and ops.VBP_TAPS is not None:
+            raise RuntimeError('VisualBackprop taps on a blur-pool model are not built')
+        paired = self._forward_pair(x, inputs) if self.shortcut is not None and not blur else False
         self.onload = [False] * n       # stage i reads relu(bn_{i-1}(c[i-1])) ON LOAD: h[i-1] is never materialised (ops.BN_ON_LOAD)
         for i, (conv, bn) in enumerate(self.stages):
             W, g, b = inputs[1 + 3 * i:4 + 3 * i]
@@ -152,8 +168,10 @@ class ResidualUnitFunction(Function):
                 self.c[i] = ops.conv_fprop_affine(self.c[i - 1], self.st[i - 1], W, geo, stats=stats)
                 self.st[i] = ops.bn_finalize(stats, geo.B * geo.Ho * geo.Wo, g, b, bn.avg_mean, bn.avg_var)
             elif not (paired and i == 0):
-                self.c[i], self.st[i], self.geo[i] = _ConvBN.forward(h, conv, bn, W, None, g, b)
-            if i < n - 1:
+                self.c[i], self.st[i], self.geo[i] = _ConvBN.forward(h, conv, bn, W, None, g, b, 1 if self.blurred[i] else None)
+            if i < n - 1 and self.blurred[i]:       # the full-resolution activation is never written
+                h = self.h[i] = ops.blur_pool(self.c[i], self.st[i])
+            elif i < n - 1:
                 # bn_i -> relu -> a 1 x 1 convolution the VGPR-fed kernels take (a bottleneck's bn2 -> conv3): the convolution and
                 # its weight gradient apply the BN while they load its input, the backward takes the BN's sums from the data
                 # gradient's epilogue and its mask from the recomputed sign -- nobody reads the activation
@@ -172,7 +190,10 @@ class ResidualUnitFunction(Function):
             self.gate = ops.se_excite(self.c[-1], self.st[-1], W1, b1, W2, b2)
         if self.shortcut is not None:
             W, g, b = inputs[1 + 3 * n:4 + 3 * n]
-            if not paired:
+            if self.blur_shortcut:
+                self.xb = ops.blur_pool(x)
+                self.cs, self.sts, self.geos = _ConvBN.forward(self.xb, self.shortcut[0], self.shortcut[1], W, None, g, b, 1)
+            elif not paired:
                 self.cs, self.sts, self.geos = _ConvBN.forward(x, self.shortcut[0], self.shortcut[1], W, None, g, b)
             if self.se is not None:
                 self.out = ops.bn_apply_gate(self.c[-1], self.st[-1], self.gate.s, x2=self.cs, st2=self.sts)
@@ -244,6 +265,12 @@ class ResidualUnitFunction(Function):
             # that finishes -- it then overlaps the HBM-bound BN passes that follow instead of fighting the dgrad
             # for the matrix pipes
             _, gp, bp = P[1 + 3 * (i - 1):4 + 3 * (i - 1)]
+            if self.blurred[i - 1]:
+                # gh is the gradient of blur(relu(bn(c[i-1]))): the transposed blur is formed inside the BN backward's two passes
+                gh = ops.conv_dgrad(g, W.data, self.geo[i])
+                ops.conv_wgrad(self.h[i - 1], g, W.grad_view, self.geo[i])
+                g = ops.blur_pool_bn_backward(gh, self.c[i - 1], self.st[i - 1], gp.data, gp.grad_view, bp.grad_view)
+                continue
             if ops.bn_sums_ok(self.geo[i], self.c[i - 1]):
                 # the two sums of BN i-1's backward ride in this dgrad's epilogue (its output tile meets the BN's input tile
                 # there): the reduction pass over gh disappears, the BN backward is one pass
@@ -261,7 +288,10 @@ class ResidualUnitFunction(Function):
         W0 = P[1]
         gx = None
         if P[0].requires_grad:
-            if self.shortcut is not None:
+            if self.blur_shortcut:      # the shortcut's gradient is at quarter resolution: blurT(it) joins the main branch's
+                gx = ops.conv_dgrad(g, W0.data, self.geo[0])
+                ops.blur_pool_backward(ops.conv_dgrad(gcs, P[1 + 3 * n].data, self.geos), tuple(gx.shape), addend=gx)
+            elif self.shortcut is not None:
                 gx = ops.conv_dgrad(gcs, P[1 + 3 * n].data, self.geos)
                 ops.conv_dgrad(g, W0.data, self.geo[0], out=gx, addend=gx)
             else:
@@ -269,20 +299,20 @@ class ResidualUnitFunction(Function):
                 gx = ops.conv_dgrad(g, W0.data, self.geo[0], addend=gout, addend_mask_ref=self.out)
         ops.conv_wgrad(self.x, g, W0.grad_view, self.geo[0])
         if self.shortcut is not None:
-            ops.conv_wgrad(self.x, gcs, P[1 + 3 * n].grad_view, self.geos)
+            ops.conv_wgrad(self.xb if self.blur_shortcut else self.x, gcs, P[1 + 3 * n].grad_view, self.geos)
         return (gx,) + (None,) * (len(P) - 1)
 
     def release(self):
-        self.x = self.c = self.h = self.st = self.out = self.cs = self.gate = None
+        self.x = self.c = self.h = self.st = self.out = self.cs = self.gate = self.xb = None
 
 
-def residual_unit(x, stages, shortcut=None, drop=None, se=None):
+def residual_unit(x, stages, shortcut=None, drop=None, se=None, blur=False):
     args = [x]
     for conv, bn in list(stages) + ([shortcut] if shortcut is not None else []):
         args += [conv.W, bn.gamma, bn.beta]
     if se is not None:
         args += [se.down.W, se.down.b, se.up.W, se.up.b]
-    return ResidualUnitFunction(stages, shortcut, drop, se)(*args)
+    return ResidualUnitFunction(stages, shortcut, drop, se, blur)(*args)
 
 
 # --------------------------------------------------------------------------- #

@@ -17,7 +17,7 @@ from ..runtime.core import Chain
 
 
 class BottleneckA(Chain):
-    def __init__(self, in_channels, mid_channels, out_channels, stride=2, initialW=None, se_ratio=None):
+    def __init__(self, in_channels, mid_channels, out_channels, stride=2, initialW=None, se_ratio=None, blur_pool=False):
         super().__init__()
         with self.init_scope():
             self.conv1 = L.Convolution2D(in_channels, mid_channels, 1, stride, 0, initialW=initialW, nobias=True)
@@ -29,10 +29,11 @@ class BottleneckA(Chain):
             self.conv4 = L.Convolution2D(in_channels, out_channels, 1, stride, 0, initialW=initialW, nobias=True)
             self.bn4 = L.BatchNormalization(out_channels)
             self.se = L.squeeze_excite(out_channels, se_ratio)
+        self.blur_pool = bool(blur_pool)
 
     def __call__(self, x):
         return blocks.residual_unit(x, [(self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)],
-                                    (self.conv4, self.bn4), drop=drop_path.unit_vector(self), se=self.se)
+                                    (self.conv4, self.bn4), drop=drop_path.unit_vector(self), se=self.se, blur=self.blur_pool)
 
 
 class BottleneckB(Chain):
@@ -53,10 +54,10 @@ class BottleneckB(Chain):
 
 
 class BuildingBlock(Chain):
-    def __init__(self, n_layer, in_channels, mid_channels, out_channels, stride, initialW=None, se_ratio=None):
+    def __init__(self, n_layer, in_channels, mid_channels, out_channels, stride, initialW=None, se_ratio=None, blur_pool=False):
         super().__init__()
         with self.init_scope():
-            self.a = BottleneckA(in_channels, mid_channels, out_channels, stride, initialW, se_ratio)
+            self.a = BottleneckA(in_channels, mid_channels, out_channels, stride, initialW, se_ratio, blur_pool)
             self._forward = ["a"]
             for i in range(n_layer - 1):
                 name = 'b{}'.format(i + 1)
@@ -70,19 +71,20 @@ class BuildingBlock(Chain):
 
 
 class ResNet50Layers(Chain, drop_path.DropPathOwner):
-    def __init__(self, pretrained_model='auto', se_ratio=None):
+    def __init__(self, pretrained_model='auto', se_ratio=None, blur_pool=False):
         super().__init__()
         w = L.HeNormal(scale=1.0)
         with self.init_scope():
             self.conv1 = L.Convolution2D(3, 64, 7, 2, 3, initialW=w, dense_rows=True)
             self.bn1 = L.BatchNormalization(64)
             self.res2 = BuildingBlock(3, 64, 64, 256, 1, w, se_ratio)
-            self.res3 = BuildingBlock(4, 256, 128, 512, 2, w, se_ratio)
-            self.res4 = BuildingBlock(6, 512, 256, 1024, 2, w, se_ratio)
-            self.res5 = BuildingBlock(3, 1024, 512, 2048, 2, w, se_ratio)
+            self.res3 = BuildingBlock(4, 256, 128, 512, 2, w, se_ratio, blur_pool)
+            self.res4 = BuildingBlock(6, 512, 256, 1024, 2, w, se_ratio, blur_pool)
+            self.res5 = BuildingBlock(3, 1024, 512, 2048, 2, w, se_ratio, blur_pool)
             self.fc6 = L.Linear(2048, 1000)
         self.pretrained_model = pretrained_model
         self.se_ratio = se_ratio
+        self.blur_pool = bool(blur_pool)
 
     exchange_stages = ('res4', 'res5')        # see sheep/resnet.py
 

@@ -90,14 +90,16 @@ class Convolution2D(Link):
             self.__dict__['b'] = None
         self.__dict__['_geo'] = {}
 
-    def geometry(self, B, H, W):
-        key = (B, H, W)
+    def geometry(self, B, H, W, stride=None):
+        """``stride``: another stride than the link's own (a blur-pool unit runs its strided convolutions at 1)"""
+        stride = self.stride if stride is None else stride
+        key = (B, H, W) if stride == self.stride else (B, H, W, stride)
         g = self._geo.get(key)
         if g is None:
             if self.dense_rows:
-                g = ops.ConvGeometry(B, H, W, 3, self.out_channels, self.ksize, self.stride, self.pad, dense=True)
+                g = ops.ConvGeometry(B, H, W, 3, self.out_channels, self.ksize, stride, self.pad, dense=True)
             else:
-                g = ops.ConvGeometry(B, H, W, self.cin_phys, self.out_channels, self.ksize, self.stride, self.pad)
+                g = ops.ConvGeometry(B, H, W, self.cin_phys, self.out_channels, self.ksize, stride, self.pad)
             self._geo[key] = g
         return g
 

@@ -2448,6 +2448,62 @@ def bn_backward_gate(gy, out, se, x, st, gamma, ggamma, gbeta, W1, W2, gW1, gb1,
     return (gx, gx2) if dual else gx
 
 
+def blur_outsize(size):
+    """positions of the anti-aliased downsampling along an axis of ``size``: ceil(size / 2), what a 3 x 3 / 2 / pad 1 and a
+    1 x 1 / 2 / pad 0 convolution give"""
+    return (size + 1) // 2
+
+
+def blur_pool(x, st=None):
+    """y = blur(relu(bn(x))) with ``st`` the BNState of the conv output x, or the plain blur(x) without: the 3 x 3 binomial
+    filter at stride 2 behind reflect padding of one (csrc/blur.hip), [B][ceil(H / 2)][ceil(W / 2)][C] in x's storage type.  The
+    full-resolution activation is never written."""
+    B, H, W, C_ = x.shape
+    y = _empty((B, blur_outsize(H), blur_outsize(W), C_), device=x.device, dtype=x.dtype)
+    if CLASS_COUNT is not None: _acct('bn_fwd', 0, _nbytes(x), _nbytes(y))
+    check(_lib.load().loans_blur_fwd(_ptr(x), _ptr(st.scale if st else None), _ptr(st.shift if st else None), _ptr(y), B, H, W, C_,
+                                     x.element_size(), y.element_size(), _stream()), 'loans_blur_fwd')
+    return y
+
+
+def blur_pool_bn_backward(gy, x, st, gamma, ggamma, gbeta):
+    """The backward of blur_pool(x, st) through the training-mode BN: gy is the quarter-resolution gradient, gz = blurT(gy) *
+    (bn(x) > 0) is formed on the fly in both passes and never written.  Accumulates ggamma / gbeta in place, returns gx at full
+    resolution: reduce (per-block records, folded in order) -> the coefficient launch of bn_backward -> apply."""
+    lib = _lib.load()
+    B, H, W, C_ = x.shape
+    s = _stream()
+    assert tuple(gy.shape) == (B, blur_outsize(H), blur_outsize(W), C_)
+    if CLASS_COUNT is not None: _acct('bn_bwd', 0, 2 * _nbytes(gy, x), _nbytes(x))
+    records = lib.loans_blur_bwd_records(B, H, W)
+    if records < 0:
+        check(records, 'loans_blur_bwd_records')
+    part = _empty((records, 2, C_), device=x.device, dtype=torch.float64)
+    sums = _zeros_f64((STATS_REPLICAS, 2, C_), x.device)
+    check(lib.loans_blur_bwd_reduce(_ptr(gy), _ptr(x), _ptr(st.scale), _ptr(st.shift), _ptr(st.mean), _ptr(part), _ptr(sums), B, H, W,
+                                    C_, gy.element_size(), x.element_size(), s), 'loans_blur_bwd_reduce')
+    k = _empty((3, C_), device=x.device, dtype=torch.float32)
+    check(lib.loans_bn_bwd_coeffs_rep_f32(_ptr(sums), STATS_REPLICAS, 2 * C_, 1, C_, B * H * W, _ptr(gamma), _ptr(st.mean),
+                                          _ptr(st.rstd), _ptr(ggamma), _ptr(gbeta), _ptr(k[0]), _ptr(k[1]), _ptr(k[2]), s),
+          'loans_bn_bwd_coeffs_rep_f32')
+    gx = _empty_like(x)
+    check(lib.loans_blur_bwd_apply(_ptr(gy), _ptr(x), _ptr(st.scale), _ptr(st.shift), _ptr(k), _ptr(gx), B, H, W, C_,
+                                   gy.element_size(), x.element_size(), s), 'loans_blur_bwd_apply')
+    return gx
+
+
+def blur_pool_backward(gy, shape, addend=None):
+    """gx = blurT(gy) [+ addend] at the full resolution ``shape`` = (B, H, W, C): the backward of the plain blur_pool(x).  With
+    ``addend`` the sum is written over it (the shortcut's gradient joins the main branch's: no separate add launch)."""
+    B, H, W, C_ = shape
+    assert tuple(gy.shape) == (B, blur_outsize(H), blur_outsize(W), C_) and (addend is None or tuple(addend.shape) == tuple(shape))
+    gx = addend if addend is not None else _empty(tuple(shape), device=gy.device, dtype=gy.dtype)
+    if CLASS_COUNT is not None: _acct('bn_bwd', 0, _nbytes(gy, addend), _nbytes(gx))
+    check(_lib.load().loans_blur_bwd_plain(_ptr(gy), _ptr(addend), _ptr(gx), B, H, W, C_, gy.element_size(), gx.element_size(),
+                                           _stream()), 'loans_blur_bwd_plain')
+    return gx
+
+
 def bn_backward_from_sums(gy, x, st, sums, gamma, ggamma, gbeta):
     """bn_backward(gy, relu(bn(x)), x, st, ..., mask_is_own_relu=True) with the reduction already done: `sums` are the
     [replicas][2][C] accumulators conv_dgrad(..., bn_sums=(x, st)) filled while gy was in registers.  One pass over the

@@ -16,7 +16,7 @@ from ..runtime.core import Chain, ChainList
 
 class ResNet(Chain, drop_path.DropPathOwner):
 
-    def __init__(self, n_layers, class_labels=None, se_ratio=None):
+    def __init__(self, n_layers, class_labels=None, se_ratio=None, blur_pool=False):
         super(ResNet, self).__init__()
         w = L.HeNormal()
         if n_layers == 18:
@@ -31,18 +31,19 @@ class ResNet(Chain, drop_path.DropPathOwner):
             self.conv1 = L.Convolution2D(3, 64, 7, 2, 3, initialW=w, dense_rows=True)
             self.bn1 = L.BatchNormalization(64)
             self.res2 = BasicBlock(block[0], 64, 1, in_ch=64, se_ratio=se_ratio)
-            self.res3 = BasicBlock(block[1], 128, in_ch=64, se_ratio=se_ratio)
-            self.res4 = BasicBlock(block[2], 256, in_ch=128, se_ratio=se_ratio)
-            self.res5 = BasicBlock(block[3], 512, in_ch=256, se_ratio=se_ratio)
+            self.res3 = BasicBlock(block[1], 128, in_ch=64, se_ratio=se_ratio, blur_pool=blur_pool)
+            self.res4 = BasicBlock(block[2], 256, in_ch=128, se_ratio=se_ratio, blur_pool=blur_pool)
+            self.res5 = BasicBlock(block[3], 512, in_ch=256, se_ratio=se_ratio, blur_pool=blur_pool)
             if n_layers == 20:
-                self.res6 = BasicBlock(block[4], 512, in_ch=512, se_ratio=se_ratio)
-                self.res7 = BasicBlock(block[5], 512, in_ch=512, se_ratio=se_ratio)
+                self.res6 = BasicBlock(block[4], 512, in_ch=512, se_ratio=se_ratio, blur_pool=blur_pool)
+                self.res7 = BasicBlock(block[5], 512, in_ch=512, se_ratio=se_ratio, blur_pool=blur_pool)
             if class_labels is not None:
                 self.fc = L.Linear(None, class_labels)      # Chainer's default initialiser: LeCunNormal, zero bias
 
         self.n_layers = n_layers
         self.class_labels = class_labels
         self.se_ratio = se_ratio
+        self.blur_pool = bool(blur_pool)
 
     # data parallel: the gradient arena is exchanged in three parts, cut in front of these stages -- everything from res5 up
     # (res5 + the head + res6 / res7: 75 % of the bytes at 224 px) as soon as the backward has left res5, res4 (19 %) next,
@@ -82,10 +83,10 @@ class ResNet(Chain, drop_path.DropPathOwner):
 
 class BasicBlock(ChainList):
 
-    def __init__(self, layer, ch, stride=2, in_ch=None, se_ratio=None):
+    def __init__(self, layer, ch, stride=2, in_ch=None, se_ratio=None, blur_pool=False):
         super(BasicBlock, self).__init__()
         in_ch = ch if in_ch is None else in_ch      # the reference infers it lazily (Convolution2D(None, ...))
-        self.add_link(BasicA(ch, stride, in_ch, se_ratio))
+        self.add_link(BasicA(ch, stride, in_ch, se_ratio, blur_pool))
         for i in range(layer - 1):
             self.add_link(BasicB(ch, se_ratio))
 
@@ -97,7 +98,7 @@ class BasicBlock(ChainList):
 
 class BasicA(Chain):
 
-    def __init__(self, ch, stride, in_ch=None, se_ratio=None):
+    def __init__(self, ch, stride, in_ch=None, se_ratio=None, blur_pool=False):
         super(BasicA, self).__init__()
         w = L.HeNormal()
         in_ch = ch if in_ch is None else in_ch
@@ -110,10 +111,12 @@ class BasicA(Chain):
             self.conv3 = L.Convolution2D(in_ch, ch, 3, stride, 1, initialW=w, nobias=True)
             self.bn3 = L.BatchNormalization(ch)
             self.se = L.squeeze_excite(ch, se_ratio)        # (None: no child, no parameters -- the reference's unit)
+        # anti-aliased downsampling (functions/blocks.py, blur=): no parameters, the strided convolutions run at stride 1
+        self.blur_pool = bool(blur_pool)
 
     def __call__(self, x):
         return blocks.residual_unit(x, [(self.conv1, self.bn1), (self.conv2, self.bn2)], (self.conv3, self.bn3),
-                                    drop=drop_path.unit_vector(self), se=self.se)
+                                    drop=drop_path.unit_vector(self), se=self.se, blur=self.blur_pool)
 
 
 class BasicB(Chain):

@@ -34,14 +34,14 @@ def _as_device_batch(images, device):
 
 class SheepLocalizer(Chain, DropPathOwner):
 
-    def __init__(self, out_size, transform_rois_to_grayscale=False, train_imagenet=False, se_ratio=None):
+    def __init__(self, out_size, transform_rois_to_grayscale=False, train_imagenet=False, se_ratio=None, blur_pool=False):
         super().__init__()
         with self.init_scope():
             # se_ratio: squeeze-and-excitation in every residual unit (links.SqueezeExcite); None / 0 builds the reference's model
-            self.feature_extractor = ResNet(18, class_labels=1000 if train_imagenet else None, se_ratio=se_ratio)
+            self.feature_extractor = ResNet(18, class_labels=1000 if train_imagenet else None, se_ratio=se_ratio, blur_pool=blur_pool)
             if not train_imagenet:
-                self.res6 = BasicBlock(2, 512, in_ch=512, se_ratio=se_ratio)
-                self.res7 = BasicBlock(2, 512, in_ch=512, se_ratio=se_ratio)
+                self.res6 = BasicBlock(2, 512, in_ch=512, se_ratio=se_ratio, blur_pool=blur_pool)
+                self.res7 = BasicBlock(2, 512, in_ch=512, se_ratio=se_ratio, blur_pool=blur_pool)
                 self.param_predictor = L.Linear(512, 6)
 
                 transform_bias = self.param_predictor.b.host
@@ -56,6 +56,8 @@ class SheepLocalizer(Chain, DropPathOwner):
         self.transform_rois_to_grayscale = transform_rois_to_grayscale
         self.train_imagenet = train_imagenet
         self.se_ratio = se_ratio
+        # anti-aliased downsampling in the strided residual units (functions/blocks.py, blur=); the stem stays as it is
+        self.blur_pool = bool(blur_pool)
 
     def drop_path_stages(self):
         """the backbone's stages, then res6 / res7 where the localizer has them (``set_drop_path`` counts the units of all of
@@ -160,17 +162,18 @@ class Resnet50SheepLocalizer(SheepLocalizer):
     (taps ``res5`` / ``pool5``), chainercv ``ResBlock`` stages res6 / res7 on frames taller than 224 / 300 px,
     ``Linear(2048, 6)``, the same STN tail."""
 
-    def __init__(self, out_size, transform_rois_to_grayscale=False, train_imagenet=False, se_ratio=None):
+    def __init__(self, out_size, transform_rois_to_grayscale=False, train_imagenet=False, se_ratio=None, blur_pool=False):
         super(SheepLocalizer, self).__init__()
         initialW = L.HeNormal(scale=1., fan_option='fan_out')
         keys_to_remove = ['fc6', 'prob'] if not train_imagenet else ['prob']
         with self.init_scope():
-            self.feature_extractor = MyResNet50Layers(keys_to_remove=keys_to_remove, pretrained_model='auto', se_ratio=se_ratio)
+            self.feature_extractor = MyResNet50Layers(keys_to_remove=keys_to_remove, pretrained_model='auto', se_ratio=se_ratio,
+                                                      blur_pool=blur_pool)
             if not train_imagenet:
                 self.param_predictor = L.Linear(2048, 6)
 
-                self.res6 = ResBlock(2, 2048, 1024, 2048, 2, initialW=initialW, se_ratio=se_ratio)
-                self.res7 = ResBlock(2, 2048, 1024, 2048, 2, initialW=initialW, se_ratio=se_ratio)
+                self.res6 = ResBlock(2, 2048, 1024, 2048, 2, initialW=initialW, se_ratio=se_ratio, blur_pool=blur_pool)
+                self.res7 = ResBlock(2, 2048, 1024, 2048, 2, initialW=initialW, se_ratio=se_ratio, blur_pool=blur_pool)
 
                 transform_bias = self.param_predictor.b.host
                 transform_bias[[0, 4]] = 0.8
@@ -183,6 +186,8 @@ class Resnet50SheepLocalizer(SheepLocalizer):
         self.transform_rois_to_grayscale = transform_rois_to_grayscale
         self.train_imagenet = train_imagenet
         self.se_ratio = se_ratio
+        # anti-aliased downsampling in the strided residual units (functions/blocks.py, blur=); the stem stays as it is
+        self.blur_pool = bool(blur_pool)
 
     def __call__(self, images):
         self.visual_backprop_anchors.clear()

@@ -41,6 +41,7 @@ def main(argv=None):
     ap.add_argument('--label-smoothing', type=float, default=0.0)
     ap.add_argument('--drop-path', type=float, default=0.0, help='stochastic depth at this rate (tools/droppath_bench.py)')
     ap.add_argument('--se-ratio', type=int, default=0, help='squeeze-and-excitation at this reduction ratio (tools/se_bench.py)')
+    ap.add_argument('--blur-pool', action='store_true', help='anti-aliased downsampling in the strided units (tools/blurpool_bench.py)')
     ap.add_argument('--teacher-arch', default=None, choices=['resnet18', 'resnet50'], help='distil from a frozen teacher of this architecture (random weights: the time does not depend on them)')
     ap.add_argument('--teacher-dtype', default=None, choices=['f32', 'bf16'], help='the teacher\'s arithmetic (default: --dtype)')
     ap.add_argument('--distill-alpha', type=float, default=0.5)
@@ -59,7 +60,7 @@ def main(argv=None):
         want = a.teacher_dtype or a.dtype
         teacher.set_precision(want, want)
         options.update(teacher=teacher, distill_alpha=a.distill_alpha, distill_temperature=a.distill_temperature)
-    model = loans_amd.Classifier(localizer((75, 75), train_imagenet=True, **({'se_ratio': a.se_ratio} if a.se_ratio else {})), label_smoothing=a.label_smoothing, **options)
+    model = loans_amd.Classifier(localizer((75, 75), train_imagenet=True, **({'se_ratio': a.se_ratio} if a.se_ratio else {}), **({'blur_pool': True} if a.blur_pool else {})), label_smoothing=a.label_smoothing, **options)
     if a.drop_path > 0:
         model.predictor.set_drop_path(a.drop_path, seed=0)
     if a.dtype == 'bf16':

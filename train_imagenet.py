@@ -192,6 +192,14 @@ logged in the first entry where given and fixed on ``--resume``; ``train_sheep_l
 ``--rl``.  ``--teacher`` models are built without it unless ``--teacher-se-ratio R`` says otherwise.  Not together with
 ``--drop-path``.
 
+``--blur-pool`` builds the backbone with anti-aliased downsampling (Zhang 2019; timm's ``aa_layer=BlurPool2d``): every strided
+convolution of the residual units runs at stride 1, and a fixed 3 x 3 binomial filter at stride 2 behind the BN and the ReLU
+does the downsampling (a strided shortcut convolution reads the blurred unit input) -- csrc/blur.hip, fused into the BN passes.
+No parameters: the snapshot keys are the plain model's.  Logged in the first entry where given and fixed on ``--resume``;
+``train_sheep_localizer.py --blur-pool`` and ``evaluate.py --blur-pool`` build the model the snapshot was trained as;
+``--teacher-blur-pool`` for a ``--teacher`` trained with it.  Works with ``--se-ratio`` and ``--drop-path``.  Not built: the
+stem (7 x 7 / 2 and its max-pool stay), other filter sizes, VisualBackprop on such a model.
+
 ``--teacher PATH`` is knowledge distillation: the model is trained against the logits of a frozen, larger one as well as against
 the labels (Hinton et al. 2015), ``loss = (1 - A) CE + A T^2 KL(softmax(teacher / T) || softmax(student / T))`` -- torch's
 ``kl_div(log_softmax(z / T), softmax(zt / T), reduction='batchmean') * T * T`` beside the cross-entropy.  ``PATH`` is a snapshot
@@ -271,7 +279,8 @@ RESUME_FIXED = ('use_resnet_18', 'dtype', 'optimizer', 'batch_size', 'gpus', 'im
                 'validation_size', 'synthetic_classes', 'data_seed', 'no_shuffle', 'augment', 'rrc_scale', 'rrc_ratio', 'val_crop_pct',
                 'augment_seed', 'seed', 'mixup_alpha', 'cutmix_alpha', 'mix_prob', 'mix_switch_prob', 'mix_seed', 'ema_decay',
                 'color_jitter', 'lighting_std', 'random_erase_prob', 'random_erase_scale', 'random_erase_ratio', 'random_erase_value',
-                'photo_seed', 'rand_augment', 'trivial_augment', 'ra_fill', 'ra_seed', 'drop_path', 'drop_path_seed', 'accum_steps', 'se_ratio')
+                'photo_seed', 'rand_augment', 'trivial_augment', 'ra_fill', 'ra_seed', 'drop_path', 'drop_path_seed', 'accum_steps', 'se_ratio',
+                'blur_pool')
 
 
 class SyntheticClasses:
@@ -399,6 +408,12 @@ class Arguments(argparse.Namespace):
     teacher_se_ratio = 0
     _SE = ('se_ratio', 'teacher_se_ratio')
 
+    # --blur-pool: anti-aliased downsampling in the strided residual units (functions/blocks.py: blur=, csrc/blur.hip); logged
+    # only where given.  teacher_blur_pool: the same for the model of --teacher
+    blur_pool = False
+    teacher_blur_pool = False
+    _BLUR = ('blur_pool', 'teacher_blur_pool')
+
 
 def parse_args(argv=None):
     parser = argparse.ArgumentParser(description="ImageNet pre-training of a localizer backbone (MI355X-native)")
@@ -491,6 +506,8 @@ def parse_args(argv=None):
     parser.add_argument("--accum-steps", type=int, default=argparse.SUPPRESS, metavar='K', help="gradient accumulation: sum the gradients of K micro-batches of -b frames per GPU and step once on their mean; iterations, intervals, --lr and the warm-up count optimiser steps (default 1: off)")
     # knowledge distillation
     parser.add_argument("--se-ratio", type=int, default=argparse.SUPPRESS, metavar='R', help="squeeze-and-excitation in every residual unit of the backbone, with C / R hidden units at C channels (SENet: 16; default 0: off)")
+    parser.add_argument("--blur-pool", action='store_true', default=argparse.SUPPRESS, help="anti-aliased downsampling: the strided convolutions of the residual units run at stride 1 and a 3 x 3 binomial filter at stride 2 downsamples behind BN + ReLU (default: off)")
+    parser.add_argument("--teacher-blur-pool", action='store_true', default=argparse.SUPPRESS, help="with --teacher: the teacher's snapshot was trained with --blur-pool")
     parser.add_argument("--teacher-se-ratio", type=int, default=argparse.SUPPRESS, metavar='R', help="with --teacher: the --se-ratio the teacher's snapshot was trained with (default 0)")
     parser.add_argument("--teacher", default=argparse.SUPPRESS, metavar='PATH', help="distil from this frozen snapshot (a <Localizer>_<it>.npz or _ema_ file as this script writes it): loss = (1 - A) CE + A T^2 KL(teacher || student); every rank loads it itself (default: off)")
     parser.add_argument("--teacher-arch", default=argparse.SUPPRESS, choices=['resnet18', 'resnet50'], help="with --teacher: the localizer the snapshot was written by (default resnet50)")
@@ -516,7 +533,7 @@ def parse_args(argv=None):
         if args.resume is not None:
             check_average_resume(args)
             world = os.environ.get('WORLD_SIZE')        # a rank under a launcher: the group's size, whatever --gpus says
-            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS_WITH_SE)
+            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS_WITH_BLUR)
     except ValueError as e:
         parser.error(str(e))
     return args
@@ -657,6 +674,8 @@ def check_se_arguments(args):
         raise ValueError('--se-ratio with --drop-path is not built: the gated junction takes no per-sample keep factor')
     if args.teacher_se_ratio and args.teacher is None:
         raise ValueError('--teacher-se-ratio belongs to --teacher: give the snapshot to distil from')
+    if args.teacher_blur_pool and args.teacher is None:
+        raise ValueError('--teacher-blur-pool belongs to --teacher: give the snapshot to distil from')
 
 
 def check_accum_arguments(args):
@@ -704,7 +723,7 @@ def build_teacher(args):
     localizer_class = loans_amd.SheepLocalizer if args.teacher_arch == 'resnet18' else loans_amd.Resnet50SheepLocalizer
     state = np.random.get_state()           # the initialisers' draws are overwritten: the student's --seed stream stays as it was
     try:
-        teacher = localizer_class((75, 75), train_imagenet=True, se_ratio=args.teacher_se_ratio or None)
+        teacher = localizer_class((75, 75), train_imagenet=True, se_ratio=args.teacher_se_ratio or None, blur_pool=args.teacher_blur_pool)
         loans_amd.Classifier(teacher).materialize()
     finally:
         np.random.set_state(state)
@@ -755,8 +774,10 @@ RESUME_DEFAULTS_WITH_DROP = dict(RESUME_DEFAULTS_WITH_RA, **RESUME_DEFAULTS_DROP
 # ... and for --accum-steps (a checkpoint from before the option ran at 1)
 RESUME_DEFAULTS_ACCUM = {name: getattr(Arguments, name) for name in Arguments._ACCUM}
 RESUME_DEFAULTS_WITH_ACCUM = dict(RESUME_DEFAULTS_WITH_DROP, **RESUME_DEFAULTS_ACCUM)
-# ... and for --se-ratio (a checkpoint from before the option holds the model without); this is the table --resume uses
+# ... and for --se-ratio (a checkpoint from before the option holds the model without)
 RESUME_DEFAULTS_WITH_SE = dict(RESUME_DEFAULTS_WITH_ACCUM, se_ratio=Arguments.se_ratio)
+# ... and for --blur-pool; this is the table --resume uses
+RESUME_DEFAULTS_WITH_BLUR = dict(RESUME_DEFAULTS_WITH_SE, blur_pool=Arguments.blur_pool)
 
 
 def cache_budgets(total_bytes, n_train, n_validation):
@@ -814,7 +835,7 @@ def build_model(args):
         teacher = build_teacher(args)
         teacher.set_precision(*(('bf16', 'bf16') if teacher_dtype == 'bf16' else ('f32', 'f32')))
         distill = dict(teacher=teacher, distill_alpha=alpha, distill_temperature=temperature)
-    model = loans_amd.Classifier(localizer_class((75, 75), train_imagenet=True, se_ratio=args.se_ratio or None), label_smoothing=args.label_smoothing,
+    model = loans_amd.Classifier(localizer_class((75, 75), train_imagenet=True, se_ratio=args.se_ratio or None, blur_pool=args.blur_pool), label_smoothing=args.label_smoothing,
                                  topk=resolved_topk(args), **loss_options(args), **distill)
     model.materialize()         # the ResNet-18 variant's lazily sized fc
     return model
@@ -1049,7 +1070,7 @@ def run(args, log=print):
         # the run continues in the checkpoint's log directory: no new <time>_<name>
         check_average_resume(args)
         resumed, changed = checkpoint.resolve_resume(args, RESUME_FIXED, log if chief else (lambda line: None), world=comm.size,
-                                                     defaults=RESUME_DEFAULTS_WITH_SE)
+                                                     defaults=RESUME_DEFAULTS_WITH_BLUR)
         args.log_dir = os.path.dirname(os.path.abspath(args.resume))
         for line in changed if chief else ():
             log(line)
@@ -1083,7 +1104,7 @@ def run(args, log=print):
             continue        # logged where one of them is given
         if argument in Arguments._DISTILL and args.teacher is None:
             continue        # logged with a teacher only
-        if argument in Arguments._SE and argument not in vars(args):
+        if argument in Arguments._SE + Arguments._BLUR and argument not in vars(args):
             continue        # logged where it is given
         # (an entry's ``loss`` is the training loss: the option of that name is logged as ``loss_function``)
         data_to_log['loss_function' if argument == 'loss' else argument] = getattr(args, argument)

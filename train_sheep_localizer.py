@@ -72,7 +72,7 @@ SYNTHETIC = 'synthetic'
 # --rd, which freezes the assessor
 RESUME_FIXED = ('use_resnet_18', 'dtype', 'batch_size', 'gpus', 'image_size', 'target_size', 'train_file', 'val_file',
                 'reference_file', 'dataset_size', 'validation_size', 'data_seed', 'no_shuffle', 'use_imgaug', 'seed',
-                'resume_discriminator', 'se_ratio')
+                'resume_discriminator', 'se_ratio', 'blur_pool')
 
 
 class SyntheticFrames:
@@ -168,6 +168,7 @@ def parse_args(argv=None):
     parser.add_argument("--rd", dest="resume_discriminator", help="assessor snapshot (.npz) to start from; also FREEZES the assessor (reference --rd)")
     parser.add_argument("--use-resnet-18", action='store_true', default=False, help="ResNet-18-variant localizer (sheep/resnet.py) instead of the ResNet-50 one")
     parser.add_argument("--se-ratio", type=int, default=0, metavar='R', help="squeeze-and-excitation in the localizer's residual units, as train_imagenet.py --se-ratio R wrote the snapshot of --rl (default 0: off)")
+    parser.add_argument("--blur-pool", action='store_true', default=False, help="anti-aliased downsampling in the localizer's strided residual units, as train_imagenet.py --blur-pool trained the snapshot of --rl (default: off)")
     parser.add_argument("--localizer-target", type=float, default=1.0, help="the IoU score the localizer is trained towards, in [0, 1]")
     parser.add_argument("--no-imgaug", action='store_false', dest='use_imgaug', default=True,
                         help="the naive crop / flip augmentation instead of the imgaug pipeline")
@@ -211,7 +212,7 @@ def parse_args(argv=None):
     if args.resume is not None:
         try:
             world = os.environ.get('WORLD_SIZE')        # a rank under a launcher: the group's size, whatever --gpus says
-            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults={'se_ratio': 0})
+            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults={'se_ratio': 0, 'blur_pool': False})
         except ValueError as e:
             parser.error(str(e))
     return args
@@ -224,7 +225,8 @@ def build_models(args):
     if args.seed is not None:
         np.random.seed(args.seed)
     localizer_class = loans_amd.SheepLocalizer if args.use_resnet_18 else loans_amd.Resnet50SheepLocalizer
-    localizer = localizer_class(tuple(args.target_size), se_ratio=getattr(args, 'se_ratio', 0) or None)
+    localizer = localizer_class(tuple(args.target_size), se_ratio=getattr(args, 'se_ratio', 0) or None,
+                                blur_pool=getattr(args, 'blur_pool', False))
     if args.resume_localizer is not None:
         load_pretrained_model(args.resume_localizer, localizer)
     discriminator = loans_amd.ResnetAssessor(output_dim=1)
@@ -340,7 +342,7 @@ def run(args, log=print):
     if args.resume is not None:
         # the run continues in the checkpoint's log directory: no new <time>_<name>
         resumed, changed = checkpoint.resolve_resume(args, RESUME_FIXED, log if comm.rank == 0 else (lambda line: None), world=comm.size,
-                                                     defaults={'se_ratio': 0})
+                                                     defaults={'se_ratio': 0, 'blur_pool': False})
         args.log_dir = os.path.dirname(os.path.abspath(args.resume))
         for line in changed if comm.rank == 0 else ():
             log(line)
