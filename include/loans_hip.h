@@ -623,6 +623,26 @@ int loans_softmax_distill_fwd_f32(const float* z, const float* zt, const int32_t
 int loans_softmax_xent_eval_f32(const float* z, const int32_t* t, float* rows /* scratch, 3*B floats */,
                                 double* acc /* 5 doubles, read-modify-write */,
                                 int32_t B, int32_t N, int32_t k, void* stream);
+/* Split rows: loans_softmax_xent_mix_fwd_f32 and loans_softmax_xent_eval_f32 for 1 <= N <= 65536 classes (1 <= B <= 65536,
+ * B * N < 2^31): ImageNet-21k.  A row is cut into chunks of 8192 logits, one block per (chunk, row): a first launch leaves per
+ * chunk its maximum and the first index holding it, sum exp(z - maximum), sum z and its share of the rank count in `workspace`, a
+ * second folds a row's records in chunk order (M = max m_c, the first index on a tie; S = sum S_c exp(m_c - M); lse = M + log S)
+ * and writes gz = (exp(z - M) / S - q) / count from a second read of z; the evaluation form folds once per row and reads z once.
+ * Target q, rows that count, count, hits against the dominant label, out[3], rows and acc exactly as for those two entries; the
+ * weights (1, 0) / (0, 1) are the one-label (plain or label-smoothed) loss on ta / on tb, the label of weight zero is not read.
+ * No atomics, every sum in a fixed order: two runs give the same bits.  They are not the bits of the one-block entries (the
+ * exponent shift is per chunk), which keep their limit N <= 8192.
+ * workspace: device memory, 4-byte aligned, at least loans_softmax_xent_split_workspace(B, N) bytes (host arithmetic only; < 0: a
+ * LOANS_E* code for a shape outside the limits); it need not be initialised.  LOANS_EINVAL / LOANS_ERANGE before any launch as
+ * for the mix entry, and LOANS_EINVAL for a workspace that is too small. */
+int64_t loans_softmax_xent_split_workspace(int32_t B, int32_t N);
+int loans_softmax_xent_split_fwd_f32(const float* z, const int32_t* ta, const int32_t* tb, float lam, float oml,
+                                     float* gz, float* row_loss, float* row_hit, float* row_hitk, float* out /* [3] */,
+                                     void* workspace, int64_t workspace_bytes, int32_t B, int32_t N, double eps, int32_t k,
+                                     void* stream);
+int loans_softmax_xent_split_eval_f32(const float* z, const int32_t* t, float* rows /* scratch, 3*B floats */,
+                                      double* acc /* 5 doubles, read-modify-write */, void* workspace, int64_t workspace_bytes,
+                                      int32_t B, int32_t N, int32_t k, void* stream);
 /* y[i] = x[i] * s[0], s on the device (the loss's upstream gradient times gz) */
 int loans_scale_by_scalar_f32(const float* x, const float* s, float* y, int64_t n, void* stream);
 /* y = x * mask (elementwise, n floats) -- RotationDropout forward/backward (functions/rotation_droput.py:26-48) */

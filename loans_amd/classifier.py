@@ -62,6 +62,8 @@ class Classifier(Chain):
             want, have = class_count(predictor), class_count(teacher)
             if want is not None and have is not None and want != have:
                 raise ValueError('the teacher has %d classes, the student %d' % (have, want))
+        if (loss == 'bce' or teacher is not None) and (class_count(predictor) or 0) > ops.XENT_ONE_BLOCK_MAX_N:
+            raise ValueError('loss=\'bce\' and distillation above %d classes are not built' % ops.XENT_ONE_BLOCK_MAX_N)
         self.label_smoothing, self.topk = label_smoothing, topk
         self.loss_name, self.bce_target_threshold, self.bce_sum = loss, bce_target_threshold, bool(bce_sum)
         self.distill_alpha, self.distill_temperature = float(distill_alpha), float(distill_temperature)
@@ -170,7 +172,8 @@ class ClassificationMetrics:
         z = logits.data if isinstance(logits, Variable) else logits
         if self.acc is None:
             self.reset(z.device)
-        ops.softmax_xent_eval(z.contiguous(), _as_labels(z, labels).data.reshape(-1).contiguous(), self.acc, self.topk or 1)
+        evaluate = ops.softmax_xent_split_eval if z.shape[1] > ops.XENT_ONE_BLOCK_MAX_N else ops.softmax_xent_eval
+        evaluate(z.contiguous(), _as_labels(z, labels).data.reshape(-1).contiguous(), self.acc, self.topk or 1)
 
     def result(self, comm=None):
         if self.acc is None:

@@ -1,7 +1,8 @@
 // The ImageNet classification head: a wide Linear layer (9 .. 2^16 outputs) in three directions on the fp32 matrix cores
 // (v_mfma_f32_32x32x2_f32), and softmax cross-entropy with top-1 accuracy in one pass over the logits (and its label-smoothed
 // form with a top-k hit, and the two-label form of a mixup / CutMix batch), and the evaluation form that writes no gradient and
-// adds the batch to running sums in double.
+// adds the batch to running sums in double.  Rows of up to 2^16 logits (ImageNet-21k) take the split-row kernels: chunks of 8192
+// logits, one block each, folded through per-chunk records.
 // No atomics anywhere in this file: every output element is owned by one lane (GEMM) or one block (loss rows) and is summed
 // in an order that depends on the shape alone, so two launches on the same inputs give the same bits.
 #include "common.h"
@@ -655,6 +656,150 @@ __global__ __launch_bounds__(256) void softmax_xent_eval_reduce_kernel(const flo
     }
 }
 
+// ---- split rows: 8193 .. 65536 classes (loans_softmax_xent_split_{fwd,eval}_f32) ----------------------------------------------
+// A row of more than 8192 logits does not fit the one-row-in-LDS kernels above, so it is cut into chunks of SPLIT_CHUNK and the
+// work is split over blocks, c = block % chunks the chunk and b = block / chunks the row (one grid axis: B may be 65536).
+//   pass 1  block (c, b) stages its chunk into LDS once and leaves a record of SPLIT_REC words in the workspace [B][chunks]:
+//           0: m_c = max of the chunk   1: the first index that holds it (int, in the row)   2: S_c = sum exp(z - m_c)
+//           3: sum z (0 when eps == 0)  4: the chunk's share of the rank count against the dominant label (int)   5: z_t
+//           z_t is read straight from global memory by every block: no chunk waits for another.
+//   pass 2  block (c, b) folds the row's records in chunk order -- M = max m_c (strictly greater: the first index wins a tie across
+//           chunks), S = sum S_c exp(m_c - M), lse = M + log S -- and writes its chunk of gz from a second read of z; block (0, b)
+//           writes the row's loss and hits.  The evaluation form folds per row (one thread each) and reads z no second time.
+// Every sum inside a chunk is the fixed tree of block_sum_256 / block_count_256 and every fold runs c = 0, 1, ..: no atomics, two
+// runs give the same bits.  They are NOT the bits of the one-block kernels (the exponent shift is per chunk).  Rows that count,
+// the dominant label and the target are softmax_xent_mix_rows_kernel's; the launcher hands a one-label call the same array twice
+// (w is lam + oml = 1 on the one label), so the label of weight zero is never seen.
+constexpr int SPLIT_CHUNK = 1 << 13;        // 32 KB of LDS, the footprint of the one-block kernels at their limit
+constexpr int SPLIT_REC = 8;                // words per record (32 bytes)
+
+__global__ __launch_bounds__(256) void softmax_split_partial_kernel(const float* __restrict__ z, const int* __restrict__ ta,
+                                                                    const int* __restrict__ tb, float* __restrict__ ws, int N,
+                                                                    int chunks, int dominant_a, int want_sum) {
+    __shared__ __attribute__((aligned(16))) float row[SPLIT_CHUNK];
+    __shared__ float shf[4];
+    __shared__ int shi[4];
+    const int tid = threadIdx.x, c = blockIdx.x % chunks, b = blockIdx.x / chunks;
+    const int la = ta[b], lb = tb[b];
+    if ((unsigned)la >= (unsigned)N || (unsigned)lb >= (unsigned)N) return;    // ignored row (uniform per block): no record is read
+    const int label = dominant_a ? la : lb;
+    const float* zr = z + (int64_t)b * N;
+    const int n0 = c * SPLIT_CHUNK, len = min(SPLIT_CHUNK, N - n0);
+    const float zt = zr[label];
+
+    float m;
+    int am;
+    row_stage_argmax(zr + n0, row, len, shf, shi, m, am);
+    const int ahead = row_rank(row, len, label - n0, zt, shi);      // i < label - n0  <=>  n0 + i < label
+    const float S = row_sum_exp(row, len, m, shf);
+    float zsum = 0.f;
+    if (want_sum) {
+        float zs = 0.f;
+        for (int i = tid; i < len; i += 256) zs += row[i];
+        zsum = block_sum_256(zs, shf);
+    }
+    if (tid == 0) {
+        float* rec = ws + ((int64_t)b * chunks + c) * SPLIT_REC;
+        rec[0] = m; rec[1] = __int_as_float(n0 + am); rec[2] = S; rec[3] = zsum; rec[4] = __int_as_float(ahead); rec[5] = zt;
+    }
+}
+
+struct SplitRow { float M, S, zsum, zt; int am, ahead; };
+
+// the records of one row folded in chunk order (every thread that calls it reads the same words)
+__device__ __forceinline__ SplitRow split_fold(const float* __restrict__ rec, int chunks) {
+    SplitRow r;
+    r.M = rec[0]; r.am = __float_as_int(rec[1]); r.zt = rec[5];
+    for (int c = 1; c < chunks; ++c) {
+        const float mc = rec[c * SPLIT_REC];
+        if (mc > r.M) { r.M = mc; r.am = __float_as_int(rec[c * SPLIT_REC + 1]); }
+    }
+    r.S = 0.f; r.zsum = 0.f; r.ahead = 0;
+    for (int c = 0; c < chunks; ++c) {
+        const float* q = rec + c * SPLIT_REC;
+        r.S += mul_rounded(q[2], expf(q[0] - r.M));
+        r.zsum += q[3];
+        r.ahead += __float_as_int(q[4]);
+    }
+    return r;
+}
+
+__global__ __launch_bounds__(256) void softmax_split_grad_kernel(const float* __restrict__ z, const int* __restrict__ ta,
+                                                                 const int* __restrict__ tb, const float* __restrict__ ws,
+                                                                 float* __restrict__ gz, float* __restrict__ row_loss,
+                                                                 float* __restrict__ row_hit, float* __restrict__ row_hitk,
+                                                                 int B, int N, int chunks, XentMix mx) {
+    __shared__ int shi[4];
+    const int tid = threadIdx.x, c = blockIdx.x % chunks, b = blockIdx.x / chunks;
+    const int n0 = c * SPLIT_CHUNK, len = min(SPLIT_CHUNK, N - n0);
+    const float* zr = z + (int64_t)b * N + n0;
+    float* gr = gz + (int64_t)b * N + n0;
+
+    int valid = 0;
+    for (int i = tid; i < B; i += 256) valid += ((unsigned)ta[i] < (unsigned)N) & ((unsigned)tb[i] < (unsigned)N);
+    const float fc = (float)max(block_count_256(valid, shi), 1);
+
+    const int la = ta[b], lb = tb[b];
+    if ((unsigned)la >= (unsigned)N || (unsigned)lb >= (unsigned)N) {       // ignored row (uniform per block)
+        for (int i = tid; i < len; i += 256) gr[i] = 0.f;
+        if (c == 0 && tid == 0) { row_loss[b] = 0.f; row_hit[b] = 0.f; row_hitk[b] = 0.f; }
+        return;
+    }
+    const SplitRow r = split_fold(ws + (int64_t)b * chunks * SPLIT_REC, chunks);
+    if (c == 0 && tid == 0) {
+        const int label = mx.lam >= mx.oml ? la : lb;
+        const float* zb = z + (int64_t)b * N;
+        const float zmix = mx.lam * zb[la] + mx.oml * zb[lb];
+        const float lse = r.M + logf(r.S);
+        row_loss[b] = mx.ls.eps == 0.f ? lse - zmix : (lse - mx.ls.omeps * zmix) - mx.ls.eps * (r.zsum / (float)N);
+        row_hit[b] = (r.am == label) ? 1.f : 0.f;
+        row_hitk[b] = (r.ahead < mx.ls.k) ? 1.f : 0.f;
+    }
+    // (eps == 0: omeps = 1 and q_off = 0, so q is w itself)
+    const int ia = la - n0, ib = lb - n0;
+    auto grad = [&](int i, float v) {
+        const float p = expf(v - r.M) / r.S;
+        const float w = (i == ia ? mx.lam : 0.f) + (i == ib ? mx.oml : 0.f);
+        return (p - (mx.ls.omeps * w + mx.ls.q_off)) / fc;
+    };
+    // 16-byte accesses over the part of the chunk where z and gz are both aligned: a scalar head up to the boundary, a scalar tail
+    int head = len, body = 0;
+    if ((((uintptr_t)zr ^ (uintptr_t)gr) & 15) == 0 && ((uintptr_t)zr & 3) == 0) {
+        const int h = min(len, (int)(((16 - ((uintptr_t)zr & 15)) & 15) >> 2));
+        if (len - h >= 4) { head = h; body = (len - h) >> 2; }
+    }
+    if (tid < head) gr[tid] = grad(tid, zr[tid]);       // body > 0: head < 4; else the loop below covers the chunk
+    if (body == 0) {
+        for (int i = 256 + tid; i < len; i += 256) gr[i] = grad(i, zr[i]);
+        return;
+    }
+    const float4* z4 = reinterpret_cast<const float4*>(zr + head);
+    float4* g4 = reinterpret_cast<float4*>(gr + head);
+    for (int j = tid; j < body; j += 256) {
+        const float4 v = z4[j];
+        const int i = head + 4 * j;
+        g4[j] = make_float4(grad(i, v.x), grad(i + 1, v.y), grad(i + 2, v.z), grad(i + 3, v.w));
+    }
+    const int done = head + 4 * body;
+    if (tid < len - done) gr[done + tid] = grad(done + tid, zr[done + tid]);
+}
+
+// rows[b], rows[B + b], rows[2B + b] of softmax_xent_eval_rows_kernel from the records: one thread per row, z is not read
+__global__ __launch_bounds__(256) void softmax_split_eval_fold_kernel(const int* __restrict__ t, const float* __restrict__ ws,
+                                                                      float* __restrict__ rows, int B, int N, int chunks, int k) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const int label = t[b];
+    if ((unsigned)label >= (unsigned)N) {
+        rows[b] = 0.f; rows[B + b] = 0.f; rows[2 * B + b] = 0.f;
+        return;
+    }
+    const SplitRow r = split_fold(ws + (int64_t)b * chunks * SPLIT_REC, chunks);
+    rows[b] = (r.M + logf(r.S)) - r.zt;
+    rows[B + b] = (r.am == label) ? 1.f : 0.f;
+    rows[2 * B + b] = (r.ahead < k) ? 1.f : 0.f;
+}
+
 __global__ __launch_bounds__(256) void scale_by_scalar_kernel(const float* __restrict__ x, const float* __restrict__ s,
                                                               float* __restrict__ y, int64_t n) {
     const float g = s[0];
@@ -823,6 +968,58 @@ extern "C" int loans_softmax_xent_eval_f32(const float* z, const int32_t* t, flo
     if (N > XENT_MAX_N || B > XENT_MAX_B) return LOANS_ERANGE;
     hipStream_t st = as_stream(stream);
     hipLaunchKernelGGL(softmax_xent_eval_rows_kernel, dim3(B), dim3(256), (size_t)N * sizeof(float), st, z, t, rows, B, N, k);
+    LOANS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(softmax_xent_eval_reduce_kernel, dim3(1), dim3(256), 0, st, rows, t, acc, B, N);
+    LOANS_LAUNCH_CHECK();
+    return LOANS_OK;
+}
+
+extern "C" int64_t loans_softmax_xent_split_workspace(int32_t B, int32_t N) {
+    if (B <= 0 || N <= 0) return LOANS_EINVAL;
+    if (N > WIDE_MAX || B > XENT_MAX_B || (int64_t)B * N >= (1ll << 31)) return LOANS_ERANGE;
+    return (int64_t)B * ((N + SPLIT_CHUNK - 1) / SPLIT_CHUNK) * SPLIT_REC * (int64_t)sizeof(float);
+}
+
+extern "C" int loans_softmax_xent_split_fwd_f32(const float* z, const int32_t* ta, const int32_t* tb, float lam, float oml,
+                                                float* gz, float* row_loss, float* row_hit, float* row_hitk, float* out,
+                                                void* workspace, int64_t workspace_bytes, int32_t B, int32_t N, double eps,
+                                                int32_t k, void* stream) {
+    if (!z || !ta || !tb || !gz || !row_loss || !row_hit || !row_hitk || !out || !workspace || B <= 0 || N <= 0) return LOANS_EINVAL;
+    if (!(eps >= 0.0 && eps < 1.0) || k < 1 || !__builtin_isfinite(lam) || !__builtin_isfinite(oml)) return LOANS_EINVAL;
+    const int64_t need = loans_softmax_xent_split_workspace(B, N);
+    if (need < 0) return (int)need;
+    if (((uintptr_t)workspace & 3) || workspace_bytes < need) return LOANS_EINVAL;
+    // one label per row: the array that carries the whole weight in both places, so the other one is not read
+    if (lam == 1.f && oml == 0.f) tb = ta;
+    if (lam == 0.f && oml == 1.f) ta = tb;
+    XentMix mx;
+    mx.ls.eps = (float)eps; mx.ls.omeps = (float)(1.0 - eps); mx.ls.q_off = (float)(eps / N); mx.ls.q_on = mx.ls.omeps + mx.ls.q_off;
+    mx.ls.k = k; mx.lam = lam; mx.oml = oml;
+    const int chunks = (N + SPLIT_CHUNK - 1) / SPLIT_CHUNK;
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(softmax_split_partial_kernel, dim3(B * chunks), dim3(256), 0, st, z, ta, tb, (float*)workspace, N, chunks,
+                       (int)(lam >= oml), (int)(mx.ls.eps != 0.f));
+    LOANS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(softmax_split_grad_kernel, dim3(B * chunks), dim3(256), 0, st, z, ta, tb, (const float*)workspace, gz, row_loss,
+                       row_hit, row_hitk, B, N, chunks, mx);
+    LOANS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(softmax_xent_mix_reduce_kernel, dim3(1), dim3(256), 0, st, row_loss, row_hit, row_hitk, ta, tb, out, B, N);
+    LOANS_LAUNCH_CHECK();
+    return LOANS_OK;
+}
+
+extern "C" int loans_softmax_xent_split_eval_f32(const float* z, const int32_t* t, float* rows, double* acc, void* workspace,
+                                                 int64_t workspace_bytes, int32_t B, int32_t N, int32_t k, void* stream) {
+    if (!z || !t || !rows || !acc || !workspace || B <= 0 || N <= 0 || k < 1) return LOANS_EINVAL;
+    const int64_t need = loans_softmax_xent_split_workspace(B, N);
+    if (need < 0) return (int)need;
+    if (((uintptr_t)workspace & 3) || workspace_bytes < need) return LOANS_EINVAL;
+    const int chunks = (N + SPLIT_CHUNK - 1) / SPLIT_CHUNK;
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(softmax_split_partial_kernel, dim3(B * chunks), dim3(256), 0, st, z, t, t, (float*)workspace, N, chunks, 1, 0);
+    LOANS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(softmax_split_eval_fold_kernel, dim3((B + 255) / 256), dim3(256), 0, st, t, (const float*)workspace, rows, B,
+                       N, chunks, k);
     LOANS_LAUNCH_CHECK();
     hipLaunchKernelGGL(softmax_xent_eval_reduce_kernel, dim3(1), dim3(256), 0, st, rows, t, acc, B, N);
     LOANS_LAUNCH_CHECK();

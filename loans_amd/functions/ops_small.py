@@ -138,6 +138,9 @@ class SoftmaxCrossEntropy(Function):
 
     def forward(self, inputs):
         x, t = inputs[0].contiguous(), inputs[1].contiguous()
+        if x.shape[1] > ops.XENT_ONE_BLOCK_MAX_N:       # a wide head (ImageNet-21k): the split-row kernels, the weights (1, 0)
+            out, self.gz = ops.softmax_xent_split_fwd(x, t, t, 1.0, 0.0, 0.0, 1)[:2]
+            return out[0], out[1]
         out, self.gz, _, _ = ops.softmax_xent_fwd(x, t)
         return out[0], out[1]
 
@@ -159,6 +162,9 @@ class SoftmaxCrossEntropyTopK(SoftmaxCrossEntropy):
 
     def forward(self, inputs):
         x, t = inputs[0].contiguous(), inputs[1].contiguous()
+        if x.shape[1] > ops.XENT_ONE_BLOCK_MAX_N:
+            out, self.gz = ops.softmax_xent_split_fwd(x, t, t, 1.0, 0.0, self.label_smoothing, self.topk)[:2]
+            return out[0], out[1], out[2]
         out, self.gz, _, _, _ = ops.softmax_xent_ls_fwd(x, t, self.label_smoothing, self.topk)
         return out[0], out[1], out[2]
 
@@ -174,7 +180,8 @@ class SoftmaxCrossEntropyMixed(SoftmaxCrossEntropyTopK):
 
     def forward(self, inputs):
         x, ta, tb = (a.contiguous() for a in inputs)
-        out, self.gz, _, _, _ = ops.softmax_xent_mix_fwd(x, ta, tb, self.lam32, self.oml32, self.label_smoothing, self.topk)
+        fwd = ops.softmax_xent_split_fwd if x.shape[1] > ops.XENT_ONE_BLOCK_MAX_N else ops.softmax_xent_mix_fwd
+        out, self.gz, _, _, _ = fwd(x, ta, tb, self.lam32, self.oml32, self.label_smoothing, self.topk)
         return out[0], out[1], out[2]
 
 

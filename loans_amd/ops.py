@@ -2928,6 +2928,56 @@ def softmax_xent_eval(z, t, acc, k=1):
     return acc
 
 
+XENT_ONE_BLOCK_MAX_N = 1 << 13          # the widest row of the one-block loss entries; wider rows take the split-row entries
+
+
+def _split_workspace(z):
+    """the record buffer of the split-row loss entries for the logits ``z``, from the step arena -> (tensor, bytes)"""
+    B, N = z.shape
+    nbytes = int(_lib.load().loans_softmax_xent_split_workspace(B, N))
+    if nbytes < 0:
+        check(nbytes, 'loans_softmax_xent_split_workspace')
+    return _empty((nbytes // 4,), device=z.device, dtype=torch.float32), nbytes
+
+
+def softmax_xent_split_fwd(z, ta, tb, lam, oml, eps, k):
+    """softmax_xent_mix_fwd for rows of up to 65536 logits (ImageNet-21k), by the split-row kernels: the same arguments and the
+    same five results, against float64 and not with the one-block entry's bits.  The weights (1, 0) are the plain / label-smoothed
+    one-label loss on ``ta`` (``tb`` is not read).  No host synchronisation."""
+    assert z.dtype == torch.float32 and z.dim() == 2 and z.is_contiguous(), 'logits must be a contiguous (B, N) fp32 array'
+    for t in (ta, tb):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == z.shape[0] and t.device == z.device, \
+            'labels must be int32, one per row, on the logits\' device'
+    B, N = z.shape
+    ws, ws_bytes = _split_workspace(z)
+    gz = _empty_like(z)
+    row_loss = _empty((B,), device=z.device, dtype=torch.float32)
+    row_hit = _empty((B,), device=z.device, dtype=torch.float32)
+    row_hitk = _empty((B,), device=z.device, dtype=torch.float32)
+    out = _empty((3,), device=z.device, dtype=torch.float32)
+    if CLASS_COUNT is not None: _acct('heads', 0, 2 * _nbytes(z), _nbytes(gz))
+    check(_lib.load().loans_softmax_xent_split_fwd_f32(_ptr(z), _ptr(ta), _ptr(tb), float(lam), float(oml), _ptr(gz), _ptr(row_loss),
+                                                       _ptr(row_hit), _ptr(row_hitk), _ptr(out), _ptr(ws), ws_bytes, B, N,
+                                                       float(eps), int(k), _stream()), 'loans_softmax_xent_split_fwd_f32')
+    return out, gz, row_loss, row_hit, row_hitk
+
+
+def softmax_xent_split_eval(z, t, acc, k=1):
+    """softmax_xent_eval for rows of up to 65536 logits, by the split-row kernels.  No host synchronisation."""
+    assert z.dtype == torch.float32 and z.dim() == 2 and z.is_contiguous(), 'logits must be a contiguous (B, N) fp32 array'
+    assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == z.shape[0] and t.device == z.device, \
+        'labels must be int32, one per row, on the logits\' device'
+    assert acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() >= 5 and acc.device == z.device, \
+        'the accumulator is 5 float64 on the logits\' device'
+    B, N = z.shape
+    ws, ws_bytes = _split_workspace(z)
+    rows = _empty((3 * B,), device=z.device, dtype=torch.float32)
+    if CLASS_COUNT is not None: _acct('heads', 0, _nbytes(z), _nbytes(rows))
+    check(_lib.load().loans_softmax_xent_split_eval_f32(_ptr(z), _ptr(t), _ptr(rows), _ptr(acc), _ptr(ws), ws_bytes, B, N, int(k),
+                                                        _stream()), 'loans_softmax_xent_split_eval_f32')
+    return acc
+
+
 def scale_by_scalar(x, s):
     """x * s[0] with s a one-element device tensor"""
     assert s.dtype == torch.float32 and s.numel() == 1 and s.device == x.device

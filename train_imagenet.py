@@ -200,6 +200,15 @@ No parameters: the snapshot keys are the plain model's.  Logged in the first ent
 ``--teacher-blur-pool`` for a ``--teacher`` trained with it.  Works with ``--se-ratio`` and ``--drop-path``.  Not built: the
 stem (7 x 7 / 2 and its max-pool stay), other filter sizes, VisualBackprop on such a model.
 
+``--num-classes N`` (default 1000; 9 .. 65536, the wide head's range) sets the width of the classification head: ImageNet-21k
+pre-training is ``--num-classes 10450`` (ImageNet-21k-P, Ridnik et al. 2021) or ``21841`` (the full set).  Up to 8192 classes
+every loss runs the launches it ran; above, the softmax loss -- plain, label-smoothed, mixed -- and the validation metrics take
+the split-row kernels (csrc/classify.hip, ``loans_softmax_xent_split_*``: a row in chunks of 8192 logits, one block each).
+Logged in the first entry where given and fixed on ``--resume`` (a checkpoint from before the option holds 1000 classes);
+``--synthetic-classes`` must not exceed it.  ``train_sheep_localizer.py --rl`` loads the snapshot whatever the width: the head
+is no part of the localizer.  A ``--teacher`` is built at the same width.  Not built above 8192 classes (refused): ``--loss
+bce`` and ``--teacher``.
+
 ``--teacher PATH`` is knowledge distillation: the model is trained against the logits of a frozen, larger one as well as against
 the labels (Hinton et al. 2015), ``loss = (1 - A) CE + A T^2 KL(softmax(teacher / T) || softmax(student / T))`` -- torch's
 ``kl_div(log_softmax(z / T), softmax(zt / T), reduction='batchmean') * T * T`` beside the cross-entropy.  ``PATH`` is a snapshot
@@ -234,7 +243,7 @@ stream, order, position, the crop / mirror draw stream, the RandAugment, the pho
 its log directory: the ``log`` file is read back and appended to, ``elapsed_time`` and the snapshot names count on.  Fixed on
 resume (one error lists every one that differs): the architecture, ``--dtype``, ``--optimizer``, ``-b``, ``--gpus``,
 ``--image-size``, the dataset files or the synthetic sizes, classes and ``--data-seed``, ``--no-shuffle``, ``--augment`` /
-``--rrc-*`` / ``--val-crop-pct`` / ``--augment-seed``, ``--mixup-alpha`` / ``--cutmix-alpha`` / ``--mix-*``, ``--color-jitter`` / ``--lighting-std`` / ``--random-erase-*`` / ``--photo-seed``, ``--rand-augment`` / ``--trivial-augment`` / ``--ra-fill`` / ``--ra-seed``, ``--drop-path`` / ``--drop-path-seed``, ``--accum-steps``, ``--ema-decay`` (a checkpoint from
+``--rrc-*`` / ``--val-crop-pct`` / ``--augment-seed``, ``--mixup-alpha`` / ``--cutmix-alpha`` / ``--mix-*``, ``--color-jitter`` / ``--lighting-std`` / ``--random-erase-*`` / ``--photo-seed``, ``--rand-augment`` / ``--trivial-augment`` / ``--ra-fill`` / ``--ra-seed``, ``--drop-path`` / ``--drop-path-seed``, ``--accum-steps``, ``--num-classes``, ``--ema-decay`` (a checkpoint from
 before these options existed ran at their defaults), ``--seed``.  Taken from the new command line (each one that differs is
 printed once): ``--num-epoch``, ``--iterations``, the log, snapshot and checkpoint intervals, ``--loader-threads``, the frame
 cache options, ``--lr``, ``--weight-decay``, ``--momentum``, ``--lr-drop-*``, ``--lr-schedule``, ``--lr-min``, ``--no-decay-1d``, ``--lars-eta``, ``--lars-eps``, ``--lamb-beta1``, ``--lamb-beta2``, ``--lamb-eps``, ``--clip-grad-norm``, ``--warmup-*``, ``--label-smoothing``, ``--topk``, ``--loss``, ``--bce-target-thresh``, ``--bce-sum``, ``--teacher`` with ``--teacher-arch``, ``--teacher-dtype``, ``--distill-alpha`` and ``--distill-temperature``.  The
@@ -280,7 +289,7 @@ RESUME_FIXED = ('use_resnet_18', 'dtype', 'optimizer', 'batch_size', 'gpus', 'im
                 'augment_seed', 'seed', 'mixup_alpha', 'cutmix_alpha', 'mix_prob', 'mix_switch_prob', 'mix_seed', 'ema_decay',
                 'color_jitter', 'lighting_std', 'random_erase_prob', 'random_erase_scale', 'random_erase_ratio', 'random_erase_value',
                 'photo_seed', 'rand_augment', 'trivial_augment', 'ra_fill', 'ra_seed', 'drop_path', 'drop_path_seed', 'accum_steps', 'se_ratio',
-                'blur_pool')
+                'blur_pool', 'num_classes')
 
 
 class SyntheticClasses:
@@ -414,6 +423,11 @@ class Arguments(argparse.Namespace):
     teacher_blur_pool = False
     _BLUR = ('blur_pool', 'teacher_blur_pool')
 
+    # --num-classes: the width of the classification head (ImageNet-21k: 10450 / 21841); above 8192 the loss runs the split-row
+    # kernels (csrc/classify.hip: loans_softmax_xent_split_*); logged only where given
+    num_classes = 1000
+    _CLASSES = ('num_classes',)
+
 
 def parse_args(argv=None):
     parser = argparse.ArgumentParser(description="ImageNet pre-training of a localizer backbone (MI355X-native)")
@@ -514,6 +528,7 @@ def parse_args(argv=None):
     parser.add_argument("--teacher-dtype", default=argparse.SUPPRESS, choices=['fp32', 'f32', 'bf16'], help="with --teacher: the arithmetic of the teacher's forward (default: the run's --dtype)")
     parser.add_argument("--distill-alpha", type=float, default=argparse.SUPPRESS, metavar='A', help="with --teacher: the weight of the distillation term, A in (0, 1] (default 0.5)")
     parser.add_argument("--distill-temperature", type=float, default=argparse.SUPPRESS, metavar='T', help="with --teacher: the temperature both logit rows are divided by, T in [2^-6, 2^6] (default 1)")
+    parser.add_argument("--num-classes", type=int, default=argparse.SUPPRESS, metavar='N', help="classes of the head, 9 .. 65536 (ImageNet-21k: 10450 or 21841; default 1000); above 8192 the softmax loss takes the split-row kernels, and --loss bce / --teacher are not built")
     checkpoint.add_arguments(parser, argparse.SUPPRESS)
     args = parser.parse_args(argv, namespace=Arguments())
     try:
@@ -530,10 +545,11 @@ def parse_args(argv=None):
         check_accum_arguments(args)
         check_distill_arguments(args)
         check_se_arguments(args)
+        check_class_arguments(args)
         if args.resume is not None:
             check_average_resume(args)
             world = os.environ.get('WORLD_SIZE')        # a rank under a launcher: the group's size, whatever --gpus says
-            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS_WITH_BLUR)
+            checkpoint.resolve_resume(args, RESUME_FIXED, world=None if world is None else int(world), defaults=RESUME_DEFAULTS_WITH_CLASSES)
     except ValueError as e:
         parser.error(str(e))
     return args
@@ -678,6 +694,24 @@ def check_se_arguments(args):
         raise ValueError('--teacher-blur-pool belongs to --teacher: give the snapshot to distil from')
 
 
+NUM_CLASSES_RANGE = (9, 1 << 16)          # the outputs loans_linear_wide_*_f32 takes
+ONE_BLOCK_CLASSES = 1 << 13             # the widest row of the BCE and distillation kernels (one row in LDS)
+
+
+def check_class_arguments(args):
+    """ValueError for a --num-classes outside the head kernel's range, for fewer classes than the synthetic set draws, and for
+    --loss bce / --teacher above 8192 classes (not built)"""
+    n = args.num_classes
+    if isinstance(n, bool) or not isinstance(n, int) or not NUM_CLASSES_RANGE[0] <= n <= NUM_CLASSES_RANGE[1]:
+        raise ValueError('--num-classes is the width of the head: an integer in [%d, %d], got %r' % (NUM_CLASSES_RANGE + (n,)))
+    if args.train_file == SYNTHETIC and args.synthetic_classes > n:
+        raise ValueError('--synthetic-classes %d does not fit a head of --num-classes %d' % (args.synthetic_classes, n))
+    if n > ONE_BLOCK_CLASSES and args.loss == 'bce':
+        raise ValueError('--loss bce above %d classes is not built: --num-classes %d' % (ONE_BLOCK_CLASSES, n))
+    if n > ONE_BLOCK_CLASSES and args.teacher is not None:
+        raise ValueError('--teacher above %d classes is not built: --num-classes %d' % (ONE_BLOCK_CLASSES, n))
+
+
 def check_accum_arguments(args):
     """ValueError for an --accum-steps that is no number of micro-batches"""
     k = args.accum_steps
@@ -723,7 +757,8 @@ def build_teacher(args):
     localizer_class = loans_amd.SheepLocalizer if args.teacher_arch == 'resnet18' else loans_amd.Resnet50SheepLocalizer
     state = np.random.get_state()           # the initialisers' draws are overwritten: the student's --seed stream stays as it was
     try:
-        teacher = localizer_class((75, 75), train_imagenet=True, se_ratio=args.teacher_se_ratio or None, blur_pool=args.teacher_blur_pool)
+        teacher = localizer_class((75, 75), train_imagenet=True, se_ratio=args.teacher_se_ratio or None, blur_pool=args.teacher_blur_pool,
+                                  class_labels=args.num_classes)
         loans_amd.Classifier(teacher).materialize()
     finally:
         np.random.set_state(state)
@@ -776,8 +811,10 @@ RESUME_DEFAULTS_ACCUM = {name: getattr(Arguments, name) for name in Arguments._A
 RESUME_DEFAULTS_WITH_ACCUM = dict(RESUME_DEFAULTS_WITH_DROP, **RESUME_DEFAULTS_ACCUM)
 # ... and for --se-ratio (a checkpoint from before the option holds the model without)
 RESUME_DEFAULTS_WITH_SE = dict(RESUME_DEFAULTS_WITH_ACCUM, se_ratio=Arguments.se_ratio)
-# ... and for --blur-pool; this is the table --resume uses
+# ... and for --blur-pool
 RESUME_DEFAULTS_WITH_BLUR = dict(RESUME_DEFAULTS_WITH_SE, blur_pool=Arguments.blur_pool)
+# ... and for --num-classes (a checkpoint from before the option holds the 1000-way head); this is the table --resume uses
+RESUME_DEFAULTS_WITH_CLASSES = dict(RESUME_DEFAULTS_WITH_BLUR, num_classes=Arguments.num_classes)
 
 
 def cache_budgets(total_bytes, n_train, n_validation):
@@ -835,7 +872,8 @@ def build_model(args):
         teacher = build_teacher(args)
         teacher.set_precision(*(('bf16', 'bf16') if teacher_dtype == 'bf16' else ('f32', 'f32')))
         distill = dict(teacher=teacher, distill_alpha=alpha, distill_temperature=temperature)
-    model = loans_amd.Classifier(localizer_class((75, 75), train_imagenet=True, se_ratio=args.se_ratio or None, blur_pool=args.blur_pool), label_smoothing=args.label_smoothing,
+    model = loans_amd.Classifier(localizer_class((75, 75), train_imagenet=True, se_ratio=args.se_ratio or None, blur_pool=args.blur_pool,
+                                                 class_labels=args.num_classes), label_smoothing=args.label_smoothing,
                                  topk=resolved_topk(args), **loss_options(args), **distill)
     model.materialize()         # the ResNet-18 variant's lazily sized fc
     return model
@@ -1070,7 +1108,7 @@ def run(args, log=print):
         # the run continues in the checkpoint's log directory: no new <time>_<name>
         check_average_resume(args)
         resumed, changed = checkpoint.resolve_resume(args, RESUME_FIXED, log if chief else (lambda line: None), world=comm.size,
-                                                     defaults=RESUME_DEFAULTS_WITH_BLUR)
+                                                     defaults=RESUME_DEFAULTS_WITH_CLASSES)
         args.log_dir = os.path.dirname(os.path.abspath(args.resume))
         for line in changed if chief else ():
             log(line)
@@ -1104,7 +1142,7 @@ def run(args, log=print):
             continue        # logged where one of them is given
         if argument in Arguments._DISTILL and args.teacher is None:
             continue        # logged with a teacher only
-        if argument in Arguments._SE + Arguments._BLUR and argument not in vars(args):
+        if argument in Arguments._SE + Arguments._BLUR + Arguments._CLASSES and argument not in vars(args):
             continue        # logged where it is given
         # (an entry's ``loss`` is the training loss: the option of that name is logged as ``loss_function``)
         data_to_log['loss_function' if argument == 'loss' else argument] = getattr(args, argument)

@@ -137,7 +137,14 @@ def load_train_paths(train_file, with_label=False):
 
 
 def load_pretrained_model(model_file, model):
-    loans_amd.load_npz(model_file, model, strict=False)       # NpzDeserializer(strict=False), reference :45-47
+    # NpzDeserializer(strict=False), reference :45-47.  The classification head is no part of the localizer: the fc6 of a snapshot
+    # pre-trained with another --num-classes than the ResNet-50 localizer's unused 1000-way one is left out
+    with np.load(model_file) as handle:
+        state = {key: handle[key] for key in handle.files}
+    for key, param in model.namedparams():
+        if '/fc6/' in key and key[1:] in state and tuple(state[key[1:]].shape) != param.logical_shape:
+            del state[key[1:]]
+    model.load_state_dict_chainer(state, strict=False)
 
 
 def parse_args(argv=None):
