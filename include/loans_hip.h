@@ -562,6 +562,25 @@ int loans_linear_wide_fwd_f32(const float* x, const float* W, const float* b, fl
  * W is needed for gx, x for gW. */
 int loans_linear_wide_bwd_f32(const float* x, const float* W, const float* gy, float* gx, float* gW, float* gb,
                               int32_t B, int32_t K, int32_t N, void* stream);
+/* The same layer on the bf16 matrix cores (v_mfma_f32_32x32x16_bf16), for heads where the three GEMMs weigh: ImageNet-21k.  Every
+ * tensor stays fp32 in memory and no bf16 copy of W is kept; with r() = fp32 -> bf16, round to nearest even, applied to each
+ * operand element as it is staged, and products and sums in fp32:
+ *   y = r(x) r(W)^T + b (the bias added in fp32);   gx = r(gy) r(W);   gW += r(gy)^T r(x);   gb += colsum(gy) from the unrounded
+ *   gy in increasing b -- the kernel and the bits of loans_linear_wide_bwd_f32.
+ * Limits, refusals and the rules for NULL b / gx / gW / gb are those of the fp32 entries above.  No atomics, every sum in an
+ * order fixed by (B, K, N): two runs give the same bits.
+ * The data gradient reduces over N into few output tiles, so the class axis is cut into S slices whose partial results go to
+ * slabs [S][B][K] in `workspace` and are summed in slice order by a second launch.  With chunks = ceil(N / 32),
+ * tiles = ceil(B / 128) * ceil(K / 128), want = max(1, min(ceil(256 / tiles), ceil(chunks / 4))), per = ceil(chunks / want):
+ * S = ceil(chunks / per), slice s covers classes [32 * per * s, 32 * per * (s + 1)).  loans_linear_wide16_workspace returns
+ * S * B * K * 4 bytes, 0 when S == 1 (gx is then written directly), or a LOANS_E* code (< 0) for a shape outside the limits; host
+ * arithmetic only.  workspace: device memory, 16-byte aligned, need not be initialised; it is read only where gx is asked for and
+ * S > 1, and one that is missing or too small then is LOANS_EINVAL before any launch. */
+int loans_linear_wide16_fwd_f32(const float* x, const float* W, const float* b, float* y,
+                                int32_t B, int32_t K, int32_t N, void* stream);
+int64_t loans_linear_wide16_workspace(int32_t B, int32_t K, int32_t N);
+int loans_linear_wide16_bwd_f32(const float* x, const float* W, const float* gy, float* gx, float* gW, float* gb,
+                                void* workspace, int64_t workspace_bytes, int32_t B, int32_t K, int32_t N, void* stream);
 /* F.softmax_cross_entropy(z, t, normalize=True, ignore_label=-1) and F.accuracy(z, t) in one pass over z [B][N] (N <= 8192,
  * B <= 65536).  t: int32 labels; a label outside [0, N) -- -1 or anything else -- marks an ignored row (loss 0, gz row 0).
  * count = max(#rows not ignored, 1).  gz[B][N] = (softmax(z) - onehot(t)) / count;  row_loss[B], row_hit[B]: per-row loss and

@@ -163,6 +163,9 @@ SIGNATURES = {
     'loans_linear_bwd_f32': [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p],
     'loans_linear_wide_fwd_f32': [_p, _p, _p, _p, _i32, _i32, _i32, _p],
     'loans_linear_wide_bwd_f32': [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p],
+    'loans_linear_wide16_fwd_f32': [_p, _p, _p, _p, _i32, _i32, _i32, _p],
+    'loans_linear_wide16_workspace': [_i32, _i32, _i32],
+    'loans_linear_wide16_bwd_f32': [_p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _p],
     'loans_softmax_xent_fwd_f32': [_p, _p, _p, _p, _p, _p, _i32, _i32, _p],
     'loans_softmax_xent_ls_fwd_f32': [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _f64, _i32, _p],
     'loans_softmax_xent_mix_fwd_f32': [_p, _p, _p, _f32, _f32, _p, _p, _p, _p, _p, _i32, _i32, _f64, _i32, _p],
@@ -234,7 +237,8 @@ SIGNATURES = {
 RESTYPES = {'loans_wgrad_bf16s_ws_floats': C.c_int64, 'loans_crop_band_rows': C.c_int, 'loans_momentum_sgd_max_segments': C.c_int,
             'loans_lars_workspace_bytes': C.c_int64, 'loans_photo_workspace_bytes': C.c_int64,
             'loans_grad_clip_workspace_bytes': C.c_int64, 'loans_ra_workspace_bytes': C.c_int64, 'loans_se_slabs': C.c_int,
-            'loans_blur_bwd_records': C.c_int, 'loans_softmax_xent_split_workspace': C.c_int64}    # (sizes / counts, not a status)
+            'loans_blur_bwd_records': C.c_int, 'loans_softmax_xent_split_workspace': C.c_int64,
+            'loans_linear_wide16_workspace': C.c_int64}  # (sizes / counts, not a status)
 
 _lib = None
 

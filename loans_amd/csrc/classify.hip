@@ -821,6 +821,14 @@ dim3 tiles(int M, int C) { return dim3((C + GT - 1) / GT, (M + GT - 1) / GT); }
 
 }  // namespace
 
+int loans_wide_shape_ok(int32_t B, int32_t K, int32_t N) { return wide_shape_ok(B, K, N); }
+
+int loans_colsum_ordered_launch(const float* gy, float* gb, int B, int N, hipStream_t st) {
+    hipLaunchKernelGGL(colsum_ordered_kernel, dim3((N + 255) / 256), dim3(256), 0, st, gy, gb, B, N);
+    LOANS_LAUNCH_CHECK();
+    return LOANS_OK;
+}
+
 extern "C" int loans_linear_wide_fwd_f32(const float* x, const float* W, const float* b, float* y, int32_t B, int32_t K,
                                          int32_t N, void* stream) {
     if (!x || !W || !y) return LOANS_EINVAL;

@@ -142,6 +142,11 @@ int loans_halo16_launch(const void* in, const void* w, void* out, const float* b
 // reached through loans_igemm_bf16s; `w` in loans_pw_pack_bf16's fragment order)
 int loans_pw16_launch(const void* in, const void* w, void* out, double* stats, const float* aff, const loans_igemm_desc* d, hipStream_t st);
 
+// classify.hip: the shape rule of the wide Linear entries and their ordered bias gradient, shared with head_bf16.hip (the bf16
+// arm of the same layer; internal)
+int loans_wide_shape_ok(int32_t B, int32_t K, int32_t N);
+int loans_colsum_ordered_launch(const float* gy, float* gb, int B, int N, hipStream_t st);
+
 // wgrad_halo_f32.hip: weight gradient of stride-1 3 x 3 convolutions on fp32 tensors with all taps in one block
 // (LOANS_TILE_WGHALO_64; internal, reached through loans_wgrad_f32)
 int loans_wgrad_halo32_launch(const float* x, const float* gy, float* dw, const loans_igemm_desc* d, int splits,

@@ -27,10 +27,11 @@ def global_average_pooling_2d(x):
 
 class LinearFunction(Function):
     """y = act_out(act_in(x) W^T + b); accumulates gW / gb into the arena itself.  More than ``ops.LINEAR_SMALL_N`` outputs
-    (the ImageNet heads) run on the GEMM kernels of classify.hip, which have no fused activations."""
+    (the ImageNet heads) run on the GEMM kernels of classify.hip, which have no fused activations; ``compute='bf16'`` takes such
+    a layer to the bf16 matrix cores instead (head_bf16.hip: operands rounded as they are staged, every tensor still fp32)."""
 
-    def __init__(self, act_in=False, act_out=False):
-        self.act_in, self.act_out = act_in, act_out
+    def __init__(self, act_in=False, act_out=False, compute='f32'):
+        self.act_in, self.act_out, self.compute = act_in, act_out, compute
 
     def forward(self, inputs):
         x, W = inputs[0], inputs[1]
@@ -39,7 +40,9 @@ class LinearFunction(Function):
         if self.wide:
             if self.act_in or self.act_out:
                 raise ValueError('a Linear layer with more than %d outputs has no fused activation' % ops.LINEAR_SMALL_N)
-            return ops.linear_wide_fwd(x.contiguous(), W, b)
+            return ops.linear_wide_fwd(x.contiguous(), W, b, compute=self.compute)
+        if self.compute != 'f32':
+            raise ValueError('compute=%r needs a Linear layer with more than %d outputs' % (self.compute, ops.LINEAR_SMALL_N))
         self.y = ops.linear_fwd(x, W, b, self.act_in, self.act_out)
         return self.y
 
@@ -51,7 +54,7 @@ class LinearFunction(Function):
         if self.wide:
             gx = ops.linear_wide_bwd(x.contiguous(), W, gys[0].contiguous(), gW=Wp.grad_view if wgrad else None,
                                      gb=bp.grad_view if (bp is not None and wgrad) else None,
-                                     need_gx=self.inputs[0].requires_grad)
+                                     need_gx=self.inputs[0].requires_grad, compute=self.compute)
             return (gx,) + (None,) * (len(inputs) - 1)
         gx = ops.linear_bwd(x, W, self.y, gys[0].contiguous(),
                             gW=Wp.grad_view if wgrad else None,
@@ -63,9 +66,9 @@ class LinearFunction(Function):
         self.y = None
 
 
-def linear(x, W, b=None):
+def linear(x, W, b=None, compute='f32'):
     args = (x, W) if b is None else (x, W, b)
-    return LinearFunction()(*args)
+    return LinearFunction(compute=compute)(*args)
 
 
 def sigmoid_linear_head(x, W):

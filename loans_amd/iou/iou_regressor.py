@@ -71,7 +71,7 @@ class BuildingBlock(Chain):
 
 
 class ResNet50Layers(Chain, drop_path.DropPathOwner):
-    def __init__(self, pretrained_model='auto', se_ratio=None, blur_pool=False, class_labels=1000):
+    def __init__(self, pretrained_model='auto', se_ratio=None, blur_pool=False, class_labels=1000, head_dtype='fp32'):
         super().__init__()
         w = L.HeNormal(scale=1.0)
         with self.init_scope():
@@ -81,7 +81,7 @@ class ResNet50Layers(Chain, drop_path.DropPathOwner):
             self.res3 = BuildingBlock(4, 256, 128, 512, 2, w, se_ratio, blur_pool)
             self.res4 = BuildingBlock(6, 512, 256, 1024, 2, w, se_ratio, blur_pool)
             self.res5 = BuildingBlock(3, 1024, 512, 2048, 2, w, se_ratio, blur_pool)
-            self.fc6 = L.Linear(2048, class_labels)
+            self.fc6 = L.Linear(2048, class_labels, compute=L.head_compute(head_dtype))
         self.class_labels = class_labels        # the head's width (classifier.class_count)
         self.pretrained_model = pretrained_model
         self.se_ratio = se_ratio
@@ -111,7 +111,7 @@ class ResNet50Layers(Chain, drop_path.DropPathOwner):
         ])
 
     def _fc6(self, x):
-        return linear(x, self.fc6.W, self.fc6.b)
+        return linear(x, self.fc6.W, self.fc6.b, compute=self.fc6.compute)
 
     def _prob(self, x):
         raise NotImplementedError("the 'prob' tap (a softmax over fc6) is not built: the classification loss takes the logits")

@@ -123,13 +123,18 @@ class Linear(Link):
     """``L.Linear(in_size, out_size, nobias, initialW)``.  ``in_size=None`` is resolved at the
     first call like Chainer.  ``nhwc_input=(H, W, C)`` declares that the kernels feed an
     NHWC-flattened activation, so W is stored in (h, w, c) order and exposed in Chainer's
-    (c, h, w) order."""
+    (c, h, w) order.  ``compute='bf16'`` (more than ``ops.LINEAR_SMALL_N`` outputs only) is the arithmetic
+    ``functions.linear`` is asked for by the layer's owner: bf16 operands on the matrix cores, fp32 tensors and sums."""
 
-    def __init__(self, in_size, out_size=None, nobias=False, initialW=None):
+    def __init__(self, in_size, out_size=None, nobias=False, initialW=None, compute='f32'):
         super().__init__()
         if out_size is None:
             in_size, out_size = None, in_size
-        self.out_size, self.nobias = out_size, nobias
+        if compute not in ('f32', 'bf16'):
+            raise ValueError("compute must be 'f32' or 'bf16', not %r" % (compute,))
+        if compute == 'bf16' and out_size <= ops.LINEAR_SMALL_N:
+            raise ValueError('compute=\'bf16\' needs more than %d outputs, not %d' % (ops.LINEAR_SMALL_N, out_size))
+        self.out_size, self.nobias, self.compute = out_size, nobias, compute
         self._initialW = initialW if initialW is not None else LeCunNormal()
         self.__dict__['W'] = None
         self.__dict__['b'] = None
@@ -179,6 +184,15 @@ class SqueezeExcite(Chain):
         with self.init_scope():
             self.down = Linear(channels, hidden, initialW=HeNormal())
             self.up = Linear(hidden, channels)
+
+
+def head_compute(head_dtype, train_imagenet=True):
+    """``head_dtype`` ('fp32' | 'bf16') of a model constructor as the ``compute`` of its classification head's Linear"""
+    if head_dtype not in ('fp32', 'bf16'):
+        raise ValueError("head_dtype must be 'fp32' or 'bf16', not %r" % (head_dtype,))
+    if head_dtype == 'bf16' and not train_imagenet:
+        raise ValueError("head_dtype='bf16' needs the classification head (train_imagenet=True)")
+    return 'bf16' if head_dtype == 'bf16' else 'f32'
 
 
 def squeeze_excite(channels, ratio):

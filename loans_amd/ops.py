@@ -2637,21 +2637,36 @@ def linear_bwd(x, W, y, gy, gW=None, gb=None, need_gx=True, act_in=False, act_ou
 LINEAR_SMALL_N = 8       # loans_linear_*: one block per sample walks N <= 8 outputs; wider layers are the GEMM of classify.hip
 
 
-def linear_wide_fwd(x, W, b=None):
-    """y = x W^T + b for 9 <= N <= 65536 outputs, fp32 (the pooled features are fp32 in both storage arms)"""
+WIDE16_TILE, WIDE16_CHUNK = 128, 32       # csrc/head_bf16.hip: the block tile's edge and the reduction chunk (HT, HK)
+
+
+def _wide_entry(compute):
+    if compute not in ('f32', 'bf16'):
+        raise ValueError("compute must be 'f32' or 'bf16', not %r" % (compute,))
+    return compute == 'bf16'
+
+
+def linear_wide_fwd(x, W, b=None, compute='f32'):
+    """y = x W^T + b for 9 <= N <= 65536 outputs, fp32 tensors (the pooled features are fp32 in both storage arms).
+    compute='bf16': operands rounded to bf16 on the way into the bf16 matrix cores, fp32 sums (loans_linear_wide16_fwd_f32)"""
     assert x.dtype == torch.float32 and W.dtype == torch.float32, 'the wide Linear is fp32 only'
+    wide16 = _wide_entry(compute)
     B = x.shape[0]
     K = x.numel() // B
     N = W.numel() // K
     y = _empty((B, N), device=x.device, dtype=torch.float32)
     if CLASS_COUNT is not None: _acct('heads', 2 * B * K * N, _nbytes(x, W), _nbytes(y))
-    check(_lib.load().loans_linear_wide_fwd_f32(_ptr(x), _ptr(W), _ptr(b), _ptr(y), B, K, N, _stream()), 'loans_linear_wide_fwd_f32')
+    lib = _lib.load()
+    fn = lib.loans_linear_wide16_fwd_f32 if wide16 else lib.loans_linear_wide_fwd_f32
+    check(fn(_ptr(x), _ptr(W), _ptr(b), _ptr(y), B, K, N, _stream()), 'loans_linear_wide16_fwd_f32' if wide16 else 'loans_linear_wide_fwd_f32')
     return y
 
 
-def linear_wide_bwd(x, W, gy, gW=None, gb=None, need_gx=True):
-    """gx = gy W (returned, or None); gW += gy^T x and gb += colsum(gy) in place"""
+def linear_wide_bwd(x, W, gy, gW=None, gb=None, need_gx=True, compute='f32'):
+    """gx = gy W (returned, or None); gW += gy^T x and gb += colsum(gy) in place.  compute='bf16': loans_linear_wide16_bwd_f32,
+    the slabs of its data gradient from the step arena"""
     assert x.dtype == torch.float32 and gy.dtype == torch.float32, 'the wide Linear is fp32 only'
+    wide16 = _wide_entry(compute)
     B = x.shape[0]
     K = x.numel() // B
     N = W.numel() // K
@@ -2659,7 +2674,16 @@ def linear_wide_bwd(x, W, gy, gW=None, gb=None, need_gx=True):
     if gx is None and gW is None and gb is None:
         return None
     if CLASS_COUNT is not None: _acct('heads', (4 if need_gx else 2) * B * K * N, _nbytes(x, W, gy), _nbytes(gx, gW))
-    check(_lib.load().loans_linear_wide_bwd_f32(_ptr(x), _ptr(W), _ptr(gy), _ptr(gx), _ptr(gW), _ptr(gb), B, K, N, _stream()),
+    lib = _lib.load()
+    if wide16:
+        nbytes = int(lib.loans_linear_wide16_workspace(B, K, N)) if need_gx else 0
+        if nbytes < 0:
+            check(nbytes, 'loans_linear_wide16_workspace')
+        ws = _empty((nbytes // 4,), device=x.device, dtype=torch.float32) if nbytes else None
+        check(lib.loans_linear_wide16_bwd_f32(_ptr(x), _ptr(W), _ptr(gy), _ptr(gx), _ptr(gW), _ptr(gb), _ptr(ws), nbytes, B, K, N, _stream()),
+              'loans_linear_wide16_bwd_f32')
+        return gx
+    check(lib.loans_linear_wide_bwd_f32(_ptr(x), _ptr(W), _ptr(gy), _ptr(gx), _ptr(gW), _ptr(gb), B, K, N, _stream()),
           'loans_linear_wide_bwd_f32')
     return gx
 

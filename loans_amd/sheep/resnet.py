@@ -16,8 +16,9 @@ from ..runtime.core import Chain, ChainList
 
 class ResNet(Chain, drop_path.DropPathOwner):
 
-    def __init__(self, n_layers, class_labels=None, se_ratio=None, blur_pool=False):
+    def __init__(self, n_layers, class_labels=None, se_ratio=None, blur_pool=False, head_dtype='fp32'):
         super(ResNet, self).__init__()
+        compute = L.head_compute(head_dtype, class_labels is not None)
         w = L.HeNormal()
         if n_layers == 18:
             block = [2, 2, 2, 2]
@@ -38,7 +39,7 @@ class ResNet(Chain, drop_path.DropPathOwner):
                 self.res6 = BasicBlock(block[4], 512, in_ch=512, se_ratio=se_ratio, blur_pool=blur_pool)
                 self.res7 = BasicBlock(block[5], 512, in_ch=512, se_ratio=se_ratio, blur_pool=blur_pool)
             if class_labels is not None:
-                self.fc = L.Linear(None, class_labels)      # Chainer's default initialiser: LeCunNormal, zero bias
+                self.fc = L.Linear(None, class_labels, compute=compute)      # Chainer's default initialiser: LeCunNormal, zero bias
 
         self.n_layers = n_layers
         self.class_labels = class_labels
@@ -77,7 +78,7 @@ class ResNet(Chain, drop_path.DropPathOwner):
             h = self.res7(h)
         if self.class_labels is not None:
             h = global_average_pooling_2d(h)        # average_pooling_2d(h, (H, W), stride=1)
-            h = linear(h, self.fc.W, self.fc.b)
+            h = linear(h, self.fc.W, self.fc.b, compute=self.fc.compute)
         return h
 
 

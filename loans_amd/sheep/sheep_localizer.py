@@ -35,11 +35,13 @@ def _as_device_batch(images, device):
 class SheepLocalizer(Chain, DropPathOwner):
 
     def __init__(self, out_size, transform_rois_to_grayscale=False, train_imagenet=False, se_ratio=None, blur_pool=False,
-                 class_labels=1000):
+                 class_labels=1000, head_dtype='fp32'):
         super().__init__()
+        L.head_compute(head_dtype, train_imagenet)      # 'bf16': the classification head on the bf16 matrix cores
         with self.init_scope():
             # se_ratio: squeeze-and-excitation in every residual unit (links.SqueezeExcite); None / 0 builds the reference's model
-            self.feature_extractor = ResNet(18, class_labels=class_labels if train_imagenet else None, se_ratio=se_ratio, blur_pool=blur_pool)
+            self.feature_extractor = ResNet(18, class_labels=class_labels if train_imagenet else None, se_ratio=se_ratio, blur_pool=blur_pool,
+                                            head_dtype=head_dtype)
             if not train_imagenet:
                 self.res6 = BasicBlock(2, 512, in_ch=512, se_ratio=se_ratio, blur_pool=blur_pool)
                 self.res7 = BasicBlock(2, 512, in_ch=512, se_ratio=se_ratio, blur_pool=blur_pool)
@@ -164,13 +166,14 @@ class Resnet50SheepLocalizer(SheepLocalizer):
     ``Linear(2048, 6)``, the same STN tail."""
 
     def __init__(self, out_size, transform_rois_to_grayscale=False, train_imagenet=False, se_ratio=None, blur_pool=False,
-                 class_labels=1000):
+                 class_labels=1000, head_dtype='fp32'):
         super(SheepLocalizer, self).__init__()
+        L.head_compute(head_dtype, train_imagenet)
         initialW = L.HeNormal(scale=1., fan_option='fan_out')
         keys_to_remove = ['fc6', 'prob'] if not train_imagenet else ['prob']
         with self.init_scope():
             self.feature_extractor = MyResNet50Layers(keys_to_remove=keys_to_remove, pretrained_model='auto', se_ratio=se_ratio,
-                                                      blur_pool=blur_pool, class_labels=class_labels)
+                                                      blur_pool=blur_pool, class_labels=class_labels, head_dtype=head_dtype)
             if not train_imagenet:
                 self.param_predictor = L.Linear(2048, 6)
 

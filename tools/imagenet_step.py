@@ -47,6 +47,7 @@ def main(argv=None):
     ap.add_argument('--distill-alpha', type=float, default=0.5)
     ap.add_argument('--distill-temperature', type=float, default=1.0)
     ap.add_argument('--num-classes', type=int, default=1000, help='the head\'s width (tools/split_xent_bench.py)')
+    ap.add_argument('--head-dtype', default='fp32', choices=['fp32', 'bf16'], help='the classification head\'s arithmetic (tools/head_bench.py)')
     ap.add_argument('--forward-only', action='store_true', help='time the test-mode forward without backprop instead of the step')
     ap.add_argument('--out', default=None, help='also write the JSON result here')
     a = ap.parse_args(argv)
@@ -62,7 +63,8 @@ def main(argv=None):
         teacher.set_precision(want, want)
         options.update(teacher=teacher, distill_alpha=a.distill_alpha, distill_temperature=a.distill_temperature)
     model = loans_amd.Classifier(localizer((75, 75), train_imagenet=True, **({'se_ratio': a.se_ratio} if a.se_ratio else {}), **({'blur_pool': True} if a.blur_pool else {}),
-                                           **({'class_labels': a.num_classes} if a.num_classes != 1000 else {})), label_smoothing=a.label_smoothing, **options)
+                                           **({'class_labels': a.num_classes} if a.num_classes != 1000 else {}),
+                                           **({'head_dtype': a.head_dtype} if a.head_dtype != 'fp32' else {})), label_smoothing=a.label_smoothing, **options)
     if a.drop_path > 0:
         model.predictor.set_drop_path(a.drop_path, seed=0)
     if a.dtype == 'bf16':
@@ -89,7 +91,7 @@ def main(argv=None):
         e1.synchronize()
         times.append(e0.elapsed_time(e1))
     head_flop = 3 * 2 * B * (2048 if a.resnet_50 else 512) * a.num_classes
-    res = {'what': 'imagenet_forward' if a.forward_only else 'imagenet_step', 'dtype': a.dtype, 'teacher': a.teacher_arch, 'localizer': localizer.__name__, 'loss_function': a.loss, 'drop_path': a.drop_path, 'batch': B, 'image_size': [H, W], 'steps': a.steps,
+    res = {'what': 'imagenet_forward' if a.forward_only else 'imagenet_step', 'dtype': a.dtype, 'head_dtype': a.head_dtype, 'teacher': a.teacher_arch, 'localizer': localizer.__name__, 'loss_function': a.loss, 'drop_path': a.drop_path, 'batch': B, 'image_size': [H, W], 'steps': a.steps,
            'step_ms_median': float(np.median(times)), 'step_ms_min': float(min(times)), 'step_ms_max': float(max(times)),
            'images_per_s': B / (float(np.median(times)) * 1e-3), 'head_gflop': head_flop / 1e9,
            'loss': float(loans_amd.reporter.observation.get('loss', float('nan'))),

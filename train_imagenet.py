@@ -209,6 +209,15 @@ Logged in the first entry where given and fixed on ``--resume`` (a checkpoint fr
 is no part of the localizer.  A ``--teacher`` is built at the same width.  Not built above 8192 classes (refused): ``--loss
 bce`` and ``--teacher``.
 
+``--head-dtype {fp32,bf16}`` (default ``fp32``) is the arithmetic of the classification head, the one layer ``--dtype`` does not
+reach (the pooled features are fp32 in both storage arms).  ``bf16`` runs its forward, data gradient and weight gradient on the
+bf16 matrix cores (csrc/head_bf16.hip, ``loans_linear_wide16_*``): every operand element is rounded to bf16, nearest even, as it
+is staged, products and sums are fp32, and the features, the fp32 master weights, the logits and all gradients stay fp32 in
+memory -- no bf16 copy of the weights is kept.  The bias gradient is the fp32 head's, bit for bit.  Works with every ``--dtype``,
+``--loss``, ``--optimizer``, the mixes, ``--accum-steps``, ``--gpus N`` and every ``--num-classes``.  Logged in the first entry where
+given; parameters, snapshot keys and optimiser state are what they were, so it is not fixed on ``--resume``.  Not built: the head
+of a ``--teacher`` model (fp32), bf16 logits, the loss fused into the GEMM, heads of 8 outputs or fewer.
+
 ``--teacher PATH`` is knowledge distillation: the model is trained against the logits of a frozen, larger one as well as against
 the labels (Hinton et al. 2015), ``loss = (1 - A) CE + A T^2 KL(softmax(teacher / T) || softmax(student / T))`` -- torch's
 ``kl_div(log_softmax(z / T), softmax(zt / T), reduction='batchmean') * T * T`` beside the cross-entropy.  ``PATH`` is a snapshot
@@ -428,6 +437,12 @@ class Arguments(argparse.Namespace):
     num_classes = 1000
     _CLASSES = ('num_classes',)
 
+    # --head-dtype: the arithmetic of the classification head's three GEMMs (csrc/head_bf16.hip for bf16: operands rounded as
+    # they are staged, fp32 tensors and sums); parameters and state do not depend on it, so it may change on --resume; logged
+    # only where given
+    head_dtype = 'fp32'
+    _HEAD = ('head_dtype',)
+
 
 def parse_args(argv=None):
     parser = argparse.ArgumentParser(description="ImageNet pre-training of a localizer backbone (MI355X-native)")
@@ -528,6 +543,7 @@ def parse_args(argv=None):
     parser.add_argument("--teacher-dtype", default=argparse.SUPPRESS, choices=['fp32', 'f32', 'bf16'], help="with --teacher: the arithmetic of the teacher's forward (default: the run's --dtype)")
     parser.add_argument("--distill-alpha", type=float, default=argparse.SUPPRESS, metavar='A', help="with --teacher: the weight of the distillation term, A in (0, 1] (default 0.5)")
     parser.add_argument("--distill-temperature", type=float, default=argparse.SUPPRESS, metavar='T', help="with --teacher: the temperature both logit rows are divided by, T in [2^-6, 2^6] (default 1)")
+    parser.add_argument("--head-dtype", default=argparse.SUPPRESS, choices=['fp32', 'bf16'], help="arithmetic of the classification head: bf16 rounds the operands of its three GEMMs to bf16 on the matrix cores, with fp32 sums, logits, weights and gradients (default fp32)")
     parser.add_argument("--num-classes", type=int, default=argparse.SUPPRESS, metavar='N', help="classes of the head, 9 .. 65536 (ImageNet-21k: 10450 or 21841; default 1000); above 8192 the softmax loss takes the split-row kernels, and --loss bce / --teacher are not built")
     checkpoint.add_arguments(parser, argparse.SUPPRESS)
     args = parser.parse_args(argv, namespace=Arguments())
@@ -873,7 +889,7 @@ def build_model(args):
         teacher.set_precision(*(('bf16', 'bf16') if teacher_dtype == 'bf16' else ('f32', 'f32')))
         distill = dict(teacher=teacher, distill_alpha=alpha, distill_temperature=temperature)
     model = loans_amd.Classifier(localizer_class((75, 75), train_imagenet=True, se_ratio=args.se_ratio or None, blur_pool=args.blur_pool,
-                                                 class_labels=args.num_classes), label_smoothing=args.label_smoothing,
+                                                 class_labels=args.num_classes, head_dtype=args.head_dtype), label_smoothing=args.label_smoothing,
                                  topk=resolved_topk(args), **loss_options(args), **distill)
     model.materialize()         # the ResNet-18 variant's lazily sized fc
     return model
@@ -1142,7 +1158,7 @@ def run(args, log=print):
             continue        # logged where one of them is given
         if argument in Arguments._DISTILL and args.teacher is None:
             continue        # logged with a teacher only
-        if argument in Arguments._SE + Arguments._BLUR + Arguments._CLASSES and argument not in vars(args):
+        if argument in Arguments._SE + Arguments._BLUR + Arguments._CLASSES + Arguments._HEAD and argument not in vars(args):
             continue        # logged where it is given
         # (an entry's ``loss`` is the training loss: the option of that name is logged as ``loss_function``)
         data_to_log['loss_function' if argument == 'loss' else argument] = getattr(args, argument)
